@@ -18,9 +18,15 @@ rank processes ITSELF (fresh children of a parent that never touches the GPU); u
 
 Steady state: the timed region starts after an UNTIMED pre-roll (--preroll, default 300 steps)
 whatever --warmup says, so that the batch holds its stationary mix of episode phases (traffic blocks
-triggered, envs resetting at the stationary rate), and lasts at least 50 ms (the K steps are repeated
-R times; `timed_steps` = R*K).  The per-launch kernel duration in `roofline` is taken with HIP events
-over that SAME region, and the line is refused (exit 3) if the two disagree.
+triggered, envs resetting at the stationary rate), and holds exactly K = --steps steps (`timed_steps`);
+`ms_per_step` is its wall time per step.  The per-launch kernel duration in `roofline` is taken with
+HIP events over that SAME region, and the line is refused (exit 3) if the two disagree.
+
+--dump-outputs DIR: after the timed region, what its last step handed the caller (obs, reward, cost,
+terminated, truncated, step flags, step info of the engine) is written as DIR/<name>.npy, float32, at
+most 64 MB in all (above that, a fixed seeded sample of the envs, listed in env_index.npy).  Maps,
+actions and seeds depend on the arguments only, so two builds run with the same arguments can be
+compared array for array.
 
 Extra objects in the JSON line:
   roofline     the fused step kernel: algorithmic bytes per launch / average launch duration
@@ -50,7 +56,8 @@ sys.path.insert(0, ROOT)
 
 FP32_PEAK_TFLOPS = 157.3   # vector FP32, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy rate
-MIN_TIMED_S = 0.05
+MIN_TIMED_S = 0.05      # the env_api leg's shortest timed run
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files together
 SHARED_MAPS = (1, 64)   # distinct maps of the shared-maps operating points
 
 
@@ -78,7 +85,12 @@ def parse():
     p.add_argument("--host-cache", default="",
                    help="pickle of the host-side scenes (written if absent, read if present): profiled runs load it "
                         "instead of forking map-builder workers from a process whose GPU the profiler has initialised")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write the step outputs of the last timed step as DIR/<name>.npy (float32, <= 64 MB in all)")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    return args
 
 
 def cs_dist():
@@ -134,10 +146,21 @@ def cpu_threads():
 
 def build_fast_oracle():
     """The CPU baseline's build of the oracle: -O3 -march=native for THIS host (the parity tests keep the -O2 build;
-    -ffp-contract=off stays, so the numbers do not change).  Built at bench time: -march=native code must not travel."""
-    out = os.path.join(ROOT, "oracle", "_build", "libmdoracle_native.so")
-    subprocess.check_call(["make", "-s", "-B", "-C", os.path.join(ROOT, "oracle"), "native"])
-    return out
+    -ffp-contract=off stays, so the numbers do not change).  Built at bench time: -march=native code must not travel.
+    The checkout may be read-only to whoever runs the bench, so oracle/ and include/ are copied to a private temporary
+    directory (removed at exit) and oracle/Makefile's `native` target runs there."""
+    import atexit
+    import shutil
+    import tempfile
+    tmp = tempfile.mkdtemp(prefix="md_bench_oracle_")
+    atexit.register(shutil.rmtree, tmp, True)
+    for sub in ("oracle", "include"):       # the files only (not oracle/_build, oracle/gen), without the checkout's modes
+        os.makedirs(os.path.join(tmp, sub))
+        for name in os.listdir(os.path.join(ROOT, sub)):
+            if os.path.isfile(os.path.join(ROOT, sub, name)):
+                shutil.copyfile(os.path.join(ROOT, sub, name), os.path.join(tmp, sub, name))
+    subprocess.check_call(["make", "-s", "-B", "-C", os.path.join(tmp, "oracle"), "native"])
+    return os.path.join(tmp, "oracle", "_build", "libmdoracle_native.so")
 
 
 def host_cache_key(args, rank, world):
@@ -170,6 +193,30 @@ def load_or_build_hosts(path, build, key):
         with open(path, "wb") as fh:
             pickle.dump(dict(key=key, hosts=hosts), fh, protocol=4)
     return hosts
+
+
+def dump_outputs(eng, out_dir, rank, world):
+    """--dump-outputs: the engine's step outputs as they stand (the last step's), float32 .npy files, <= DUMP_MAX_BYTES in
+    all over the ranks.  A batch too large for that is written for a fixed seeded sample of its envs (env_index.npy)."""
+    import numpy as np
+    arrays = OrderedDict(obs=eng.obs, reward=eng.reward, cost=eng.cost)
+    if eng.done_tt is not None:
+        arrays.update(terminated=eng.done_tt[..., 0], truncated=eng.done_tt[..., 1], step_flags=eng.step_flags)
+    arrays["step_info"] = eng.step_info
+    E = eng.E
+    per_env = sum(t[0].numel() for t in arrays.values()) * 4 + 8       # float32 arrays + the float64 env index
+    n = min(E, (DUMP_MAX_BYTES // world - 256 * (len(arrays) + 1)) // per_env)     # 256: room for each .npy header
+    idx = np.arange(E) if n == E else np.sort(np.random.default_rng(1234).choice(E, n, replace=False))
+    torch_index = None
+    if n < E:
+        import torch
+        torch_index = torch.from_numpy(idx).to(eng.device)
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = "rank%d_" % rank if world > 1 else ""
+    np.save(os.path.join(out_dir, prefix + "env_index.npy"), idx.astype(np.float64))
+    for name, t in arrays.items():
+        sel = t if torch_index is None else t.index_select(0, torch_index)
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), sel.float().cpu().numpy())
 
 
 def main():
@@ -366,12 +413,7 @@ def main():
     run(max(args.preroll, 0))
     torch.cuda.synchronize()
     est = (time.perf_counter() - tp) / max(args.preroll, 1) if args.preroll > 0 else 1e-4
-    repeats = max(1, int(math.ceil(MIN_TIMED_S / max(args.steps * est, 1e-9))))
-    rep_t = torch.tensor([repeats], dtype=torch.int64, device="cpu" if (rehearse or world == 1) else dev)
-    if world > 1:
-        dist.all_reduce(rep_t, op=dist.ReduceOp.MAX)    # every rank times the same number of steps
-    repeats = int(rep_t.item())
-    timed_steps = args.steps * repeats
+    timed_steps = args.steps
 
     run(args.warmup)
     ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -403,6 +445,8 @@ def main():
         sys.stderr.write("bench.py: inconsistent timing: wall %.4f ms/step < HIP-event %.4f ms/launch over the same %d "
                          "steps; refusing to print a line\n" % (ms_per_step, step_ms_avg, timed_steps))
         sys.exit(3)
+    if args.dump_outputs:       # before any other leg steps or resets this engine
+        dump_outputs(eng, args.dump_outputs, rank, world)
 
     # present movers per env right now (alive, kind != none)
     flags = eng.shape_f.view(torch.int32)[..., 6]

@@ -1,5 +1,5 @@
-import time, torch, sys
-sys.path.insert(0, "/root/repo")
+import time, torch, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from metadrive_ped_amd.config import make_config
 from metadrive_ped_amd.engine import BatchedEngine
 cfg = make_config(dict(num_envs=64, num_scenarios=64))

@@ -1,5 +1,5 @@
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from metadrive_ped_amd.envs import BatchedMultiAgentTollgateEnv, BatchedMultiAgentBottleneckEnv
 from metadrive_ped_amd.engine import HostScene
