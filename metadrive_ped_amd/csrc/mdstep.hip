@@ -80,10 +80,10 @@ __device__ const int* g_env_order = nullptr;
 #ifndef MD_ENV_SKIP
 #define MD_ENV_SKIP 0
 #endif
-// the single-agent kernels' lidar sectors by ticket as well (the waves that idle beside the observation / IDM stage take them all)
-#ifndef MD_LEAN_LIDAR_TICKETS
-#define MD_LEAN_LIDAR_TICKETS 1
-#endif
+
+// LDS images: every kernel with dynamic LDS has ONE layout function (<kernel>_lds below) that both its launcher (for the size)
+// and the kernel (to carve smem) call.  Offsets are in bytes from the start of the dynamic LDS, which is 16-B aligned.
+__host__ __device__ constexpr uint32_t align_up(uint32_t b, uint32_t a) { return (b + a - 1) & ~(a - 1); }
 
 __device__ __forceinline__ float bcast_f(float v, int src) { return __shfl(v, src, 64); }
 __device__ __forceinline__ int bcast_i(int v, int src) { return __shfl(v, src, 64); }
@@ -588,6 +588,18 @@ __device__ __forceinline__ void detector_wave2(const MdWorld& w, const MdShape& 
 __device__ __host__ inline int detector_parts(int A) { return (A >= kBlock / 64) ? 1 : kBlock / 64; }
 __device__ __host__ inline int detector_groups(int A) { return (A * detector_parts(A) + kBlock / 64 - 1) / (kBlock / 64); }
 
+// LDS image of line_detector_kernel for nb beams (both fans)
+struct LineDetectorLds { uint32_t best, beams, pairs, bytes; };
+__host__ __device__ inline LineDetectorLds line_detector_lds(int nb) {
+    constexpr int kW = kBlock / 64;
+    LineDetectorLds L;
+    L.best = 0;                                                  // [kW][nb] bit patterns of the closest fractions
+    L.beams = L.best + (uint32_t)kW * nb * sizeof(int);            // [nb][2] the beam tables, fan 0 then fan 1
+    L.pairs = L.beams + (uint32_t)nb * 2 * sizeof(float);          // [kW][kDetPairs] each wave's pair list
+    L.bytes = L.pairs + (uint32_t)kW * kDetPairs * sizeof(int);
+    return L;
+}
+
 __global__ __launch_bounds__(kBlock) void line_detector_kernel(MdWorld w, MdState s, MdConfig c,
                                                                const float* __restrict__ beam_cs, int n_beams,
                                                                float range, uint32_t kind_mask, float* out,
@@ -595,14 +607,15 @@ __global__ __launch_bounds__(kBlock) void line_detector_kernel(MdWorld w, MdStat
                                                                const float* __restrict__ beam_cs1, int n_beams1, float range1,
                                                                uint32_t kind_mask1, int out_offset1) {
     // (beam_cs1, n_beams1 > 0, ...): a SECOND fan evaluated in the same pass over the quads (md_line_detectors)
-    extern __shared__ int l_ld[];
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int kW = kBlock / 64;
     const int A = c.agents_per_env;
     const int nb = n_beams + n_beams1;
     const int parts = detector_parts(A), groups = detector_groups(A);
-    int* l_best = l_ld;                                              // [kW * nb] bit patterns of the closest fractions
-    float* l_bm = reinterpret_cast<float*>(l_ld + kW * nb);          // [nb][2] the beam tables, fan 0 then fan 1
-    int* l_pairs = reinterpret_cast<int*>(l_bm + 2 * nb);            // [kW][kDetPairs]
+    const LineDetectorLds L = line_detector_lds(nb);
+    int* l_best = reinterpret_cast<int*>(smem + L.best);
+    float* l_bm = reinterpret_cast<float*>(smem + L.beams);
+    int* l_pairs = reinterpret_cast<int*>(smem + L.pairs);
     const int e = blockIdx.x / groups, grp = blockIdx.x - e * groups;
     if (e >= c.n_envs) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -1541,6 +1554,33 @@ constexpr uint32_t kRemovedMark = 0xFFFFFFFFu;  // l_cfl value of a traffic slot
 template <int PH, bool RESPAWN, bool MULTI>
 constexpr int env_waves_per_eu() { return (PH == PH_ALL && !RESPAWN && !MULTI && MD_ENV_BLOCK >= 128) ? MD_ENV_WAVES_EU : 0; }
 
+// LDS image of one env in env_kernel: its dynamic state, the staged map tables (n_lanes / n_roads: 0 when not staged) and the
+// stages' scratch.  The lidar-only kernel stages nothing but the shapes: asking for the full image would cost it occupancy.
+struct EnvLds { uint32_t shape, dyn, nav, pid, action, flags, lanes, roads, scratch, param, final_lane, det, onlane, cfl, tk, bytes; };
+__host__ __device__ inline EnvLds env_lds(int cap, int agents, int n_lanes, int n_roads, int waves, bool multi, bool lidar_only) {
+    EnvLds L;
+    L.shape = 0;                                                     // the 16-B records are staged as uint4
+    L.dyn = L.shape + (uint32_t)cap * sizeof(MdShape);
+    L.nav = L.dyn + (uint32_t)cap * sizeof(MdDyn);
+    L.pid = L.nav + (uint32_t)cap * sizeof(MdNav);
+    L.action = L.pid + (uint32_t)cap * sizeof(MdPid);                  // [cap][2] floats
+    L.flags = L.action + (uint32_t)cap * 2 * sizeof(float);
+    L.lanes = align_up(L.flags + (uint32_t)cap * sizeof(uint32_t), 16);  // map tables: copy16
+    L.roads = L.lanes + (uint32_t)n_lanes * sizeof(MdLane);
+    L.scratch = L.roads + (uint32_t)n_roads * sizeof(MdRoad);         // [waves][kObsScratch or 48] floats: per-wave observe results
+    L.param = L.scratch + (uint32_t)waves * (multi ? kObsScratch : 48) * sizeof(float);   // 16-B aligned like the map tables
+    L.final_lane = L.param + (uint32_t)cap * sizeof(MdParam);
+    L.det = L.final_lane + align_up(cap, 2) * sizeof(int32_t);      // [agents][2] detected sets (8-B aligned)
+    // the fused step's localize / contacts results ([cap] each, merged into flags afterwards) share their words with the
+    // lifecycle's 8 scratch words, which run before them (MULTI)
+    L.onlane = L.det + (uint32_t)agents * 2 * sizeof(unsigned long long);
+    L.cfl = L.onlane + (uint32_t)cap * sizeof(uint32_t);
+    const uint32_t shared_words = 2 * cap > 8 ? 2 * cap : 8;
+    L.tk = L.onlane + shared_words * sizeof(uint32_t);               // ticket counters of the locate / observe / lidar stages
+    L.bytes = lidar_only ? L.dyn : L.tk + 3 * sizeof(int);
+    return L;
+}
+
 // BLK: threads of the workgroup (MD_ENV_BLOCK; multi-agent batches small enough to stay resident are also instantiated with 512:
 // eight waves share an env's 20-40 agents -- lifecycle search, contacts, observe groups, lidar sectors -- instead of four).
 template <int PH, bool STAGE_MAP, bool RESPAWN = false, bool MULTI = false, int BLK = MD_ENV_BLOCK>
@@ -1561,36 +1601,34 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     const int wave = tid >> 6, lane = tid & 63;
     const int cap = c.cap;
 
-    // ---- LDS image of this env's dynamic state (dynamic LDS: cap * 172 B + 16 B) ----
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    MdShape* l_shape = reinterpret_cast<MdShape*>(smem);
-    MdDyn* l_dyn = reinterpret_cast<MdDyn*>(l_shape + cap);
-    MdNav* l_nav = reinterpret_cast<MdNav*>(l_dyn + cap);
-    MdPid* l_pid = reinterpret_cast<MdPid*>(l_nav + cap);
-    float* l_action = reinterpret_cast<float*>(l_pid + cap);
-    uint32_t* l_flags = reinterpret_cast<uint32_t*>(l_action + 2 * cap);
+    // ---- LDS image of this env (env_lds) ----
     // static tables of this env's map: read many times by the serial per-vehicle logic, so (small maps) they sit in
     // LDS too (a dependent chain of HBM/L2 round trips otherwise).  The movers' routes stay in global memory: the two
     // road ids the step needs are cached in MdNav (road0 / road1), the arrays are touched only when a cursor advances.
     const int n_stage_lanes = STAGE_MAP ? w.max_lanes : 0, n_stage_roads = STAGE_MAP ? w.max_roads : 0;
-    MdLane* l_lanes = reinterpret_cast<MdLane*>(l_flags + ((cap + 3) & ~3));
-    MdRoad* l_roads = reinterpret_cast<MdRoad*>(l_lanes + n_stage_lanes);
-    constexpr int kScratch = MULTI ? kObsScratch : 48;  // floats per wave (launch<> sizes the LDS image the same way)
-    float* l_scratch = reinterpret_cast<float*>(l_roads + n_stage_roads) + wave * kScratch;  // per-wave observe results
-    MdParam* l_param = reinterpret_cast<MdParam*>(reinterpret_cast<float*>(l_roads + n_stage_roads) + kWaves * kScratch);
-    int32_t* l_final = reinterpret_cast<int32_t*>(l_param + cap);
-    unsigned long long* l_det = reinterpret_cast<unsigned long long*>(l_final + ((cap + 1) & ~1));  // [A][2] detected sets
-    uint32_t* l_onlane = reinterpret_cast<uint32_t*>(l_det + 2 * c.agents_per_env);  // fused step: localize / contacts results,
-    uint32_t* l_cfl = l_onlane + cap;                                                  // merged into flags afterwards
-    // MULTI: ticket counters of the locate / observe / lidar stages -- behind the lifecycle's 8 scratch words, which start at l_onlane
-    // and reach past l_cfl + cap in an env of fewer than four slots
-    int* l_tk = reinterpret_cast<int*>(l_onlane + (2 * cap > 8 ? 2 * cap : 8));
+    constexpr bool kLidarOnly = (PH == PH_LIDAR);
+    const EnvLds L = env_lds(cap, c.agents_per_env, n_stage_lanes, n_stage_roads, kWaves, MULTI, kLidarOnly);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    MdShape* l_shape = reinterpret_cast<MdShape*>(smem + L.shape);
+    MdDyn* l_dyn = reinterpret_cast<MdDyn*>(smem + L.dyn);
+    MdNav* l_nav = reinterpret_cast<MdNav*>(smem + L.nav);
+    MdPid* l_pid = reinterpret_cast<MdPid*>(smem + L.pid);
+    float* l_action = reinterpret_cast<float*>(smem + L.action);
+    uint32_t* l_flags = reinterpret_cast<uint32_t*>(smem + L.flags);
+    MdLane* l_lanes = reinterpret_cast<MdLane*>(smem + L.lanes);
+    MdRoad* l_roads = reinterpret_cast<MdRoad*>(smem + L.roads);
+    float* l_scratch = reinterpret_cast<float*>(smem + L.scratch) + wave * (MULTI ? kObsScratch : 48);
+    MdParam* l_param = reinterpret_cast<MdParam*>(smem + L.param);
+    int32_t* l_final = reinterpret_cast<int32_t*>(smem + L.final_lane);
+    unsigned long long* l_det = reinterpret_cast<unsigned long long*>(smem + L.det);
+    uint32_t* l_onlane = reinterpret_cast<uint32_t*>(smem + L.onlane);
+    uint32_t* l_cfl = reinterpret_cast<uint32_t*>(smem + L.cfl);
+    int* l_tk = reinterpret_cast<int*>(smem + L.tk);
     // detected sets: only the RESPAWN ("everything else") and MULTI variants carry the tracking code; launch<> picks
     // one of them whenever MdState.detected is set, so the lean trigger-mode kernel pays nothing for it
     const bool track_det = (PH == PH_ALL) && (RESPAWN || MULTI) && g.detected != nullptr;
 
     const MdState gv = md_env_view(&g, &c, e);  // this env's slices of the global arrays
-    constexpr bool kLidarOnly = (PH == PH_LIDAR);
     // The reset flag is loaded first but nothing below waits for it: the live state is staged
     // unconditionally (one round trip) and only a resetting env re-stages from the snapshot.
     const int reset_flag = (PH & PH_RESET) ? gv.need_reset[0] : 0;
@@ -1723,7 +1761,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         s.param = l_param;
         s.final_lane = l_final;
     }
-    if ((MULTI || (MD_LEAN_LIDAR_TICKETS && PH == PH_ALL)) && tid == 0) l_tk[0] = l_tk[1] = l_tk[2] = 0;
+    if ((MULTI || PH == PH_ALL) && tid == 0) l_tk[0] = l_tk[1] = l_tk[2] = 0;
     __syncthreads();
     MD_STAMP_AT(1);
 
@@ -1909,7 +1947,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         // lidar only reads shapes; observe writes obs[0:19] / flags / nav / pid -- no barrier needed in between
     }
     if ((PH & PH_LIDAR) && !(PH == PH_ALL && (MD_ENV_SKIP & 1))) {
-        if (c.n_beams > 0) phase_lidar(w, s, c, e, tid, kWaves, lidar_out, lidar_stride, lidar_offset, track_det ? l_det : nullptr, (PH == PH_ALL && (MULTI || MD_LEAN_LIDAR_TICKETS)) ? &l_tk[2] : nullptr);
+        if (c.n_beams > 0) phase_lidar(w, s, c, e, tid, kWaves, lidar_out, lidar_stride, lidar_offset, track_det ? l_det : nullptr, PH == PH_ALL ? &l_tk[2] : nullptr);
     }
 
     MD_STAMP_AT(9);
@@ -1996,12 +2034,27 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__host__ __device__ inline int wave_env_lds_bytes(int cap, int agents) {
-    // shape dyn pid param (32 B) + nav (64 B) per slot, then action (8) flags final onlane cfl (4 each), the wave's
-    // scratch (48 floats) and the detected sets (16 B per agent); rounded to 16 B
-    const int b = cap * (4 * 32 + 64) + cap * (8 + 4 * 4) + 48 * 4 + 16 * agents;
-    return (b + 15) & ~15;
+// LDS image of one env (= one wave) in wave_step_kernel; the images of a workgroup's envs follow each other every `bytes`
+struct WaveEnvLds { uint32_t shape, dyn, pid, param, nav, action, flags, final_lane, onlane, cfl, scratch, det, bytes; };
+__host__ __device__ inline WaveEnvLds wave_env_lds(int cap, int agents) {
+    WaveEnvLds L;
+    L.shape = 0;                                                     // the 16-B records are staged as uint4
+    L.dyn = L.shape + (uint32_t)cap * sizeof(MdShape);
+    L.pid = L.dyn + (uint32_t)cap * sizeof(MdDyn);
+    L.param = L.pid + (uint32_t)cap * sizeof(MdPid);
+    L.nav = L.param + (uint32_t)cap * sizeof(MdParam);
+    L.action = L.nav + (uint32_t)cap * sizeof(MdNav);                  // [cap][2] floats
+    L.flags = L.action + (uint32_t)cap * 2 * sizeof(float);
+    L.final_lane = L.flags + (uint32_t)cap * sizeof(uint32_t);
+    L.onlane = L.final_lane + (uint32_t)cap * sizeof(int32_t);         // localize / contacts results, merged into flags afterwards
+    L.cfl = L.onlane + (uint32_t)cap * sizeof(uint32_t);
+    L.scratch = L.cfl + (uint32_t)cap * sizeof(uint32_t);             // 48 floats: the wave's observe results
+    L.det = L.scratch + 48 * sizeof(float);                         // [agents][2] detected sets: 8-B aligned (see below)
+    L.bytes = align_up(L.det + (uint32_t)agents * 2 * sizeof(unsigned long long), 16);   // the next env's shapes: uint4
+    return L;
 }
+static_assert((sizeof(MdShape) + sizeof(MdDyn) + sizeof(MdPid) + sizeof(MdParam) + sizeof(MdNav) + 6 * 4) % 8 == 0 && 48 * 4 % 8 == 0,
+              "wave_env_lds: the detected sets need 8-B alignment");
 
 // k-th set bit of (hi:lo), -1 if there is none
 __device__ __forceinline__ int kth_bit(unsigned long long lo, unsigned long long hi, int k) {
@@ -2031,19 +2084,20 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
     const int A = c.agents_per_env;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* base = smem + (size_t)(threadIdx.x >> 6) * wave_env_lds_bytes(cap, A);
-    MdShape* l_shape = reinterpret_cast<MdShape*>(base);
-    MdDyn* l_dyn = reinterpret_cast<MdDyn*>(l_shape + cap);
-    MdPid* l_pid = reinterpret_cast<MdPid*>(l_dyn + cap);
-    MdParam* l_param = reinterpret_cast<MdParam*>(l_pid + cap);
-    MdNav* l_nav = reinterpret_cast<MdNav*>(l_param + cap);
-    float* l_action = reinterpret_cast<float*>(l_nav + cap);
-    uint32_t* l_flags = reinterpret_cast<uint32_t*>(l_action + 2 * cap);
-    int32_t* l_final = reinterpret_cast<int32_t*>(l_flags + cap);
-    uint32_t* l_onlane = reinterpret_cast<uint32_t*>(l_final + cap);
-    uint32_t* l_cfl = l_onlane + cap;
-    float* l_scratch = reinterpret_cast<float*>(l_cfl + cap);
-    unsigned long long* l_det = reinterpret_cast<unsigned long long*>(l_scratch + 48);
+    const WaveEnvLds L = wave_env_lds(cap, A);
+    unsigned char* base = smem + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * L.bytes;   // wave-uniform: kept in SGPRs
+    MdShape* l_shape = reinterpret_cast<MdShape*>(base + L.shape);
+    MdDyn* l_dyn = reinterpret_cast<MdDyn*>(base + L.dyn);
+    MdPid* l_pid = reinterpret_cast<MdPid*>(base + L.pid);
+    MdParam* l_param = reinterpret_cast<MdParam*>(base + L.param);
+    MdNav* l_nav = reinterpret_cast<MdNav*>(base + L.nav);
+    float* l_action = reinterpret_cast<float*>(base + L.action);
+    uint32_t* l_flags = reinterpret_cast<uint32_t*>(base + L.flags);
+    int32_t* l_final = reinterpret_cast<int32_t*>(base + L.final_lane);
+    uint32_t* l_onlane = reinterpret_cast<uint32_t*>(base + L.onlane);
+    uint32_t* l_cfl = reinterpret_cast<uint32_t*>(base + L.cfl);
+    float* l_scratch = reinterpret_cast<float*>(base + L.scratch);
+    unsigned long long* l_det = reinterpret_cast<unsigned long long*>(base + L.det);
     const bool track_det = RESPAWN && g.detected != nullptr;
 
     const MdState gv = md_env_view(&g, &c, e);
@@ -2531,12 +2585,6 @@ struct DecideLds {
 constexpr int kPairCap = 256;
 constexpr uint32_t kNullPair = 0xffffffffu;
 constexpr unsigned long long kNoFront = ~0ull;
-__host__ __device__ constexpr size_t decide_lds_bytes(int cap) { return (size_t)cap * 16 + (size_t)kPairCap * 4 + 16; }
-// the scratch both users share: the route builder's [seg_cap + 1] doubles, [seg_cap][2] floats, [seg_cap] ints
-__host__ __device__ constexpr size_t sc_scratch_bytes(bool routes, int seg_cap, int cap) {
-    const size_t a = routes ? (size_t)seg_cap * 20 + 8 : 0, b = decide_lds_bytes(cap);
-    return ((a > b ? a : b) + 15) & ~(size_t)15;
-}
 
 // One (speed-control vehicle, near mover) pair of get_find_front_back_objs_single_lane (md_tidm_front_gap), by one wave: the chassis
 // corners inside the outline's bounding box against the outline (lanes = polygon edges, all corners in one pass), then the
@@ -2866,6 +2914,46 @@ __device__ __forceinline__ void build_route_wave(int32_t* rn, MdSeg* segs, int s
 #ifndef MD_SC_WAVES_EU
 #define MD_SC_WAVES_EU 8
 #endif
+// LDS image of one scene in scenario_step_kernel.  n_det = n_side + n_lane_line (the detectors' share is there whenever the
+// config has beams); routes: the scene builds routes (MdState.route_n set), each of at most seg_cap pieces.
+struct ScenarioLds {
+    uint32_t shape, dyn, pid, param, nav, action, flags, cfl, loc, count, dbest, beams, pairs;
+    uint32_t key, cur_long, heading, dpairs, ctl;   // the decision stage's scratch (DecideLds) ...
+    uint32_t len, pts, link;                        // ... and the route builder's, at the same offset (the traffic manager builds later)
+    uint32_t rn, shape_ct, desc, bytes;
+};
+__host__ __device__ inline ScenarioLds scenario_lds(int cap, int agents, int n_det, bool routes, int seg_cap) {
+    ScenarioLds L;
+    L.shape = 0;                                                     // the 16-B records are staged as uint4
+    L.dyn = L.shape + (uint32_t)cap * sizeof(MdShape);
+    L.pid = L.dyn + (uint32_t)cap * sizeof(MdDyn);
+    L.param = L.pid + (uint32_t)cap * sizeof(MdPid);
+    L.nav = L.param + (uint32_t)cap * sizeof(MdParam);
+    L.action = L.nav + (uint32_t)cap * sizeof(MdNav);                  // [cap][2] floats
+    L.flags = L.action + (uint32_t)cap * 2 * sizeof(float);
+    L.cfl = L.flags + (uint32_t)cap * sizeof(uint32_t);
+    L.loc = L.cfl + (uint32_t)((cap + 3) & ~3) * sizeof(uint32_t);    // [agents]
+    L.count = L.loc + (uint32_t)agents * sizeof(MdTrajLoc);           // 4 ints: next_agent_id, the traffic manager's two counters, route length
+    L.dbest = L.count + 4 * sizeof(int);                             // [agents][n_det] detector fractions (bit patterns)
+    L.beams = L.dbest + (uint32_t)agents * n_det * sizeof(int);        // [n_det][2] the beam tables
+    L.pairs = L.beams + (uint32_t)n_det * 2 * sizeof(float);           // [2][kDetPairs] pair lists of the two detector waves
+    const uint32_t shared = align_up(L.pairs + (n_det > 0 ? 2 * (uint32_t)kDetPairs * sizeof(int) : 0), 8);
+    L.key = shared;                                                  // [cap] unsigned long long
+    L.cur_long = L.key + (uint32_t)cap * sizeof(unsigned long long);
+    L.heading = L.cur_long + (uint32_t)cap * sizeof(float);
+    L.dpairs = L.heading + (uint32_t)cap * sizeof(float);              // [kPairCap]
+    L.ctl = L.dpairs + (uint32_t)kPairCap * sizeof(uint32_t);          // 2 ints
+    const uint32_t decide_end = L.ctl + 2 * sizeof(int);
+    L.len = shared;                                                  // [seg_cap + 1] doubles
+    L.pts = L.len + (uint32_t)(seg_cap + 1) * sizeof(double);          // [seg_cap][2] floats
+    L.link = L.pts + (uint32_t)seg_cap * 2 * sizeof(float);            // [seg_cap] ints
+    const uint32_t build_end = routes ? L.link + (uint32_t)seg_cap * sizeof(int) : shared;
+    L.rn = decide_end > build_end ? decide_end : build_end;          // [cap][4] route_n of the scene, when it builds routes
+    L.shape_ct = align_up(L.rn + (routes ? (uint32_t)cap * 4 * sizeof(int32_t) : 0), 16);   // [cap], copied as uint4
+    L.desc = L.shape_ct + (uint32_t)cap * sizeof(MdShape);             // [cap] RouteDesc (16-B aligned)
+    L.bytes = L.desc + (uint32_t)cap * sizeof(RouteDesc);
+    return L;
+}
 __global__ __launch_bounds__(256)
 #if MD_SC_WAVES_EU
 __attribute__((amdgpu_waves_per_eu(MD_SC_WAVES_EU, MD_SC_WAVES_EU)))
@@ -2877,38 +2965,37 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
     if (e >= c.n_envs) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int cap = c.cap, A = c.agents_per_env;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    MdShape* l_shape = reinterpret_cast<MdShape*>(smem);
-    MdDyn* l_dyn = reinterpret_cast<MdDyn*>(l_shape + cap);
-    MdPid* l_pid = reinterpret_cast<MdPid*>(l_dyn + cap);
-    MdParam* l_param = reinterpret_cast<MdParam*>(l_pid + cap);
-    MdNav* l_nav = reinterpret_cast<MdNav*>(l_param + cap);
-    float* l_action = reinterpret_cast<float*>(l_nav + cap);
-    uint32_t* l_flags = reinterpret_cast<uint32_t*>(l_action + 2 * cap);
-    uint32_t* l_cfl = l_flags + cap;
-    MdTrajLoc* l_loc = reinterpret_cast<MdTrajLoc*>(l_cfl + ((cap + 3) & ~3));   // [A]
-    int* l_count = reinterpret_cast<int*>(l_loc + A);
-    int* l_dbest = l_count + 4;   // [A][n_side + n_lane_line] detector fractions (bit patterns), when md_step runs the detectors
     const bool fused_det = (w.side_beam_cs != nullptr && c.n_side > 0) || (w.ll_beam_cs != nullptr && c.n_lane_line > 0);
     const int n_det = (w.side_beam_cs ? c.n_side : 0) + (w.ll_beam_cs ? c.n_lane_line : 0);
-    // [route_seg_cap][2]: the positions a route cut at a spawn frame is built from (behind the detectors' share, as md_step sizes it)
-    // and the builder's scratch: [seg_cap + 1] doubles, [seg_cap] ints
-    double* l_len = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(l_count + 4 + (A + 2) * (c.n_side + c.n_lane_line) +
-                                                                          ((c.n_side + c.n_lane_line) > 0 ? 2 * kDetPairs : 0)) + 7) & ~(uintptr_t)7);
-    float* l_pts = reinterpret_cast<float*>(l_len + c.route_seg_cap + 1);
-    int* l_link = reinterpret_cast<int*>(l_pts + 2 * c.route_seg_cap);
-    // the decision stage's scratch shares the builder's (the traffic manager builds routes later in the step)
-    DecideLds dl;
-    dl.key = reinterpret_cast<unsigned long long*>(l_len);
-    dl.cur_long = reinterpret_cast<float*>(dl.key + cap);
-    dl.heading = dl.cur_long + cap;
-    dl.pairs = reinterpret_cast<uint32_t*>(dl.heading + cap);
-    dl.ctl = reinterpret_cast<int*>(dl.pairs + kPairCap);
-    unsigned char* l_scratch_end = reinterpret_cast<unsigned char*>(l_len) + sc_scratch_bytes(g.route_n != nullptr, c.route_seg_cap, cap);
-    int32_t* l_rn = reinterpret_cast<int32_t*>(l_scratch_end);   // [cap][4]: route_n of the scene (the decisions read it first: not a global round trip)
+    const ScenarioLds L = scenario_lds(cap, A, c.n_side + c.n_lane_line, g.route_n != nullptr, c.route_seg_cap);
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    MdShape* l_shape = reinterpret_cast<MdShape*>(smem + L.shape);
+    MdDyn* l_dyn = reinterpret_cast<MdDyn*>(smem + L.dyn);
+    MdPid* l_pid = reinterpret_cast<MdPid*>(smem + L.pid);
+    MdParam* l_param = reinterpret_cast<MdParam*>(smem + L.param);
+    MdNav* l_nav = reinterpret_cast<MdNav*>(smem + L.nav);
+    float* l_action = reinterpret_cast<float*>(smem + L.action);
+    uint32_t* l_flags = reinterpret_cast<uint32_t*>(smem + L.flags);
+    uint32_t* l_cfl = reinterpret_cast<uint32_t*>(smem + L.cfl);
+    MdTrajLoc* l_loc = reinterpret_cast<MdTrajLoc*>(smem + L.loc);
+    int* l_count = reinterpret_cast<int*>(smem + L.count);
+    int* l_dbest = reinterpret_cast<int*>(smem + L.dbest);   // [A][n_det] when md_step runs the detectors
+    float* l_beams = reinterpret_cast<float*>(smem + L.beams);   // [n_det][2]: read n_beams times per quad
+    int* l_det_pairs = reinterpret_cast<int*>(smem + L.pairs);
+    // the positions, lengths and links a route cut at a spawn frame is built from
+    double* l_len = reinterpret_cast<double*>(smem + L.len);
+    float* l_pts = reinterpret_cast<float*>(smem + L.pts);
+    int* l_link = reinterpret_cast<int*>(smem + L.link);
+    DecideLds dl;   // on the builder's words
+    dl.key = reinterpret_cast<unsigned long long*>(smem + L.key);
+    dl.cur_long = reinterpret_cast<float*>(smem + L.cur_long);
+    dl.heading = reinterpret_cast<float*>(smem + L.heading);
+    dl.pairs = reinterpret_cast<uint32_t*>(smem + L.dpairs);
+    dl.ctl = reinterpret_cast<int*>(smem + L.ctl);
+    int32_t* l_rn = reinterpret_cast<int32_t*>(smem + L.rn);   // [cap][4]: route_n of the scene (the decisions read it first: not a global round trip)
     // [cap] the movers as the agent's contact test sees them: after the integration, BEFORE the traffic manager's after_step
-    MdShape* l_shape_ct = reinterpret_cast<MdShape*>((reinterpret_cast<uintptr_t>(g.route_n != nullptr ? (void*)(l_rn + 4 * cap) : (void*)l_scratch_end) + 15) & ~(uintptr_t)15);
-    RouteDesc* l_desc = reinterpret_cast<RouteDesc*>(l_shape_ct + cap);   // [cap] what the decisions know about each slot's route
+    MdShape* l_shape_ct = reinterpret_cast<MdShape*>(smem + L.shape_ct);
+    RouteDesc* l_desc = reinterpret_cast<RouteDesc*>(smem + L.desc);   // [cap] what the decisions know about each slot's route
 
     MD_STAMP_AT(0);
     const MdState gv = md_env_view(&g, &c, e);
@@ -3025,7 +3112,6 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
             l_flags[j] = 0u;
         }
     }
-    float* l_beams = reinterpret_cast<float*>(l_dbest + A * n_det);   // [n_det][2]: the beam tables, read n_beams times per quad
     if (fused_det) {
         const int ns = w.side_beam_cs ? c.n_side : 0;
         for (int it = tid; it < A * n_det; it += kBlock) l_dbest[it] = __float_as_int(1.0f);
@@ -3209,7 +3295,7 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
                 const int qa = q0 + (wave - 2) * half, qb = min(qa + half, q1);
                 int* best = l_dbest + a * n_det;
                 const int ns = w.side_beam_cs ? c.n_side : 0;
-                int* pairs = reinterpret_cast<int*>(l_beams + 2 * n_det) + (wave - 2) * kDetPairs;   // this wave's pair list
+                int* pairs = l_det_pairs + (wave - 2) * kDetPairs;   // this wave's pair list
                 if (w.side_beam_cs && c.n_side > 0)
                     detector_wave(w, me, qa, qb, l_beams, c.n_side, c.side_range, c.side_mask, best, pairs, lane);
                 if (w.ll_beam_cs && c.n_lane_line > 0)
@@ -3270,14 +3356,23 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
 
 // Lidar.perceive as a sensor on its own (md_lidar_detect): cloud points AND the detected-object sets, from nothing but
 // the shape table.  One workgroup per env, shapes + sets in LDS, (agent, sector) items dealt to the waves.
+struct LidarDetectLds { uint32_t shape, det, bytes; };
+__host__ __device__ inline LidarDetectLds lidar_detect_lds(int cap, int agents) {
+    LidarDetectLds L;
+    L.shape = 0;                                                     // copy16
+    L.det = L.shape + (uint32_t)cap * sizeof(MdShape);                 // [agents][2] detected sets
+    L.bytes = L.det + (uint32_t)agents * 2 * sizeof(unsigned long long);
+    return L;
+}
 __global__ __launch_bounds__(256) void lidar_detect_kernel(MdWorld w, MdState g, MdConfig c, float* out, int out_stride, int out_offset,
                                                           unsigned long long* detected) {
     const int e = blockIdx.x;
     if (e >= c.n_envs) return;
     const int tid = threadIdx.x;
+    const LidarDetectLds L = lidar_detect_lds(c.cap, c.agents_per_env);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    MdShape* l_shape = reinterpret_cast<MdShape*>(smem);
-    unsigned long long* l_det = reinterpret_cast<unsigned long long*>(l_shape + c.cap);
+    MdShape* l_shape = reinterpret_cast<MdShape*>(smem + L.shape);
+    unsigned long long* l_det = reinterpret_cast<unsigned long long*>(smem + L.det);
     copy16(l_shape, g.shape + (size_t)e * c.cap, c.cap * (int)sizeof(MdShape), tid, 256);
     for (int j = tid; j < 2 * c.agents_per_env; j += 256) l_det[j] = 0ull;
     __syncthreads();
@@ -3374,6 +3469,14 @@ int need(const void* p, const char* name) {
     return MD_EINVAL;
 }
 
+// after a hipLaunchKernelGGL: MD_OK, or MD_ELAUNCH with the HIP error in g_err
+int launch_status() {
+    const hipError_t err = hipGetLastError();
+    if (err == hipSuccess) return MD_OK;
+    snprintf(g_err, sizeof g_err, "kernel launch failed: %s", hipGetErrorString(err));
+    return MD_ELAUNCH;
+}
+
 // md_step of the single-agent envs has two kernels: env_kernel (one 4-wave workgroup per env) and wave_step_kernel (one
 // wave per env), chosen by MdConfig.step_kernel alone (0 = workgroup, 1 = wave): the host decides -- it knows how many
 // distinct maps the batch shares, which is what tips the balance (metadrive_ped_amd/engine.py) -- and the library reads no
@@ -3382,7 +3485,7 @@ bool use_wave_kernel(const MdConfig* c) { return !c->is_multi_agent && c->step_k
 
 int launch_wave_step(const MdWorld* w, const MdState* s, const MdConfig* c, float* lidar_out, int stride, int offset,
                      void* stream) {
-    const size_t per_env = (size_t)wave_env_lds_bytes(c->cap, c->agents_per_env);
+    const size_t per_env = wave_env_lds(c->cap, c->agents_per_env).bytes;
     int per_wg = kWaveEnvs;   // envs per workgroup: as many as fit 64 KB of LDS (capacity-128 accident scenes: 2)
     while (per_wg > 1 && per_wg * per_env > 64 * 1024) per_wg >>= 1;
     const size_t lds = per_wg * per_env;
@@ -3395,12 +3498,7 @@ int launch_wave_step(const MdWorld* w, const MdState* s, const MdConfig* c, floa
     const bool general = c->traffic_mode != 0 || c->agent_idm != 0 || s->detected != nullptr;
     if (general) hipLaunchKernelGGL((wave_step_kernel<true>), grid, dim3(64 * per_wg), lds, st, *w, *s, *c, lidar_out, stride, offset);
     else hipLaunchKernelGGL((wave_step_kernel<false>), grid, dim3(64 * per_wg), lds, st, *w, *s, *c, lidar_out, stride, offset);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        snprintf(g_err, sizeof g_err, "kernel launch failed: %s", hipGetErrorString(err));
-        return MD_ELAUNCH;
-    }
-    return MD_OK;
+    return launch_status();
 }
 
 template <int PH>
@@ -3408,20 +3506,16 @@ int launch(const MdWorld* w, const MdState* s, const MdConfig* c, float* lidar_o
            void* stream) {
     if (PH == PH_ALL && use_wave_kernel(c)) return launch_wave_step(w, s, c, lidar_out, stride, offset, stream);
     const bool stage = w->max_lanes <= kStageMaxLanes;
-    constexpr bool kCanMultiLds = (PH & (PH_LIFECYCLE | PH_RESET)) != 0;  // same rule as the MULTI kernel variant below
+    constexpr bool kCanRespawn = (PH & (PH_TRAFFIC | PH_RESET | PH_INTEGRATE)) != 0;
+    constexpr bool kCanMulti = (PH & (PH_LIFECYCLE | PH_RESET)) != 0;
     // Multi-agent md_step: eight waves per env while every workgroup of the batch is resident at once at that size (the MULTI
     // kernel's 92 VGPRs allow 5 waves per SIMD = 640 eight-wave workgroups on the 256 CUs); larger batches keep four, which
     // then fill the chip by themselves.  Measured: 512 tollgate envs x 40 agents, 1024 roundabout envs (profiles/r03_*).
-    const bool wide = (PH == PH_ALL) && kCanMultiLds && c->is_multi_agent && c->n_envs <= kWideMaxEnvs && MD_ENV_BLOCK == 256 &&
+    const bool wide = (PH == PH_ALL) && kCanMulti && c->is_multi_agent && c->n_envs <= kWideMaxEnvs && MD_ENV_BLOCK == 256 &&
                       c->agents_per_env > 8;
     const int blk = wide ? 512 : MD_ENV_BLOCK;
-    // the lidar-only kernel stages nothing but the shapes: asking for the full image would cost it occupancy
-    const size_t lds = (PH == PH_LIDAR) ? (size_t)c->cap * sizeof(MdShape) + 16 :
-                       (size_t)c->cap * (sizeof(MdShape) + sizeof(MdDyn) + sizeof(MdNav) + sizeof(MdPid) + 8) +
-                       (size_t)((c->cap + 3) & ~3) * 4 +
-                       (stage ? (size_t)w->max_lanes * sizeof(MdLane) + (size_t)w->max_roads * sizeof(MdRoad) : 0) +
-                       (blk / 64) * (kCanMultiLds && c->is_multi_agent ? kObsScratch : 48) * 4 + (size_t)c->cap * (sizeof(MdParam) + 4) + 16 + (size_t)c->agents_per_env * 16 + 8 +
-                       (size_t)c->cap * 8 + 32 + 16;   // + 32: the lifecycle's 8 scratch words sit at the start of the last region; + 16: ticket counters
+    const size_t lds = env_lds(c->cap, c->agents_per_env, stage ? w->max_lanes : 0, stage ? w->max_roads : 0, blk / 64,
+                               kCanMulti && c->is_multi_agent, PH == PH_LIDAR).bytes;
     if (lds > 64 * 1024 || ((PH != PH_LIDAR) && (w->max_lanes <= 0 || w->max_roads <= 0))) {
         snprintf(g_err, sizeof g_err, "LDS image of one env needs %zu B (cap=%d, max_lanes=%d, max_roads=%d); limit 65536",
                  lds, c->cap, w->max_lanes, w->max_roads);
@@ -3429,8 +3523,6 @@ int launch(const MdWorld* w, const MdState* s, const MdConfig* c, float* lidar_o
     }
     const dim3 grid(c->n_envs);
     const hipStream_t st = (hipStream_t)stream;
-    constexpr bool kCanRespawn = (PH & (PH_TRAFFIC | PH_RESET | PH_INTEGRATE)) != 0;
-    constexpr bool kCanMulti = (PH & (PH_LIFECYCLE | PH_RESET)) != 0;
 #define MD_LAUNCH(STAGE, RESP, MUL) \
     hipLaunchKernelGGL((env_kernel<PH, STAGE, RESP, MUL>), grid, dim3(MD_ENV_BLOCK), lds, st, *w, *s, *c, lidar_out, stride, offset)
 #define MD_LAUNCH_WIDE(STAGE) \
@@ -3451,12 +3543,7 @@ int launch(const MdWorld* w, const MdState* s, const MdConfig* c, float* lidar_o
     }
 #undef MD_LAUNCH
 #undef MD_LAUNCH_WIDE
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        snprintf(g_err, sizeof g_err, "kernel launch failed: %s", hipGetErrorString(err));
-        return MD_ELAUNCH;
-    }
-    return MD_OK;
+    return launch_status();
 }
 
 #define NEED(p)                                  \
@@ -3557,12 +3644,7 @@ __attribute__((visibility("default"))) int md_probe_stream_copy(void* dst, const
     if (blocks > 2048u) blocks = 2048u;  // 8 workgroups per CU, tile-stride beyond
     hipLaunchKernelGGL(stream_copy_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (u32x4*)dst,
                        (const u32x4*)src, n16);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        snprintf(g_err, sizeof g_err, "kernel launch failed: %s", hipGetErrorString(err));
-        return MD_ELAUNCH;
-    }
-    return MD_OK;
+    return launch_status();
 }
 
 __attribute__((visibility("default"))) int md_probe_math(int op, const float* a, const float* b, float* out, int n,
@@ -3572,12 +3654,7 @@ __attribute__((visibility("default"))) int md_probe_math(int op, const float* a,
         return MD_EINVAL;
     }
     hipLaunchKernelGGL(probe_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, op, a, b, out, n);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        snprintf(g_err, sizeof g_err, "kernel launch failed: %s", hipGetErrorString(err));
-        return MD_ELAUNCH;
-    }
-    return MD_OK;
+    return launch_status();
 }
 
 __attribute__((visibility("default"))) int md_lidar(const MdWorld* w, const MdState* s, const MdConfig* c, float* out,
@@ -3601,15 +3678,9 @@ __attribute__((visibility("default"))) int md_lidar_detect(const MdWorld* w, con
         snprintf(g_err, sizeof g_err, "md_lidar_detect: n_beams=%d stride=%d offset=%d", c->n_beams, out_stride, out_offset);
         return MD_EINVAL;
     }
-    const size_t lds = (size_t)c->cap * sizeof(MdShape) + (size_t)c->agents_per_env * 16 + 16;
-    hipLaunchKernelGGL(lidar_detect_kernel, dim3(c->n_envs), dim3(256), lds, (hipStream_t)stream, *w, *s, *c, out, out_stride,
+    hipLaunchKernelGGL(lidar_detect_kernel, dim3(c->n_envs), dim3(256), lidar_detect_lds(c->cap, c->agents_per_env).bytes, (hipStream_t)stream, *w, *s, *c, out, out_stride,
                        out_offset, (unsigned long long*)detected);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        snprintf(g_err, sizeof g_err, "kernel launch failed: %s", hipGetErrorString(err));
-        return MD_ELAUNCH;
-    }
-    return MD_OK;
+    return launch_status();
 }
 
 static int line_detector_launch(const MdWorld* w, const MdState* s, const MdConfig* c, const float* beam_cs, int n_beams, float range,
@@ -3629,15 +3700,9 @@ static int line_detector_launch(const MdWorld* w, const MdState* s, const MdConf
         snprintf(g_err, sizeof g_err, "%s: %zu beams > 255", who, nb);
         return MD_EINVAL;
     }
-    const size_t lds_ld = ((kBlock / 64) * nb + 2 * nb + (kBlock / 64) * (size_t)kDetPairs) * sizeof(int);
-    hipLaunchKernelGGL(line_detector_kernel, dim3(c->n_envs * detector_groups(c->agents_per_env)), dim3(kBlock), lds_ld, (hipStream_t)stream, *w, *s, *c, beam_cs,
+    hipLaunchKernelGGL(line_detector_kernel, dim3(c->n_envs * detector_groups(c->agents_per_env)), dim3(kBlock), line_detector_lds((int)nb).bytes, (hipStream_t)stream, *w, *s, *c, beam_cs,
                        n_beams, range, kind_mask, out, out_stride, out_offset, beam_cs1, n_beams1 > 0 ? n_beams1 : 0, range1, kind_mask1, out_offset1);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        snprintf(g_err, sizeof g_err, "kernel launch failed: %s", hipGetErrorString(err));
-        return MD_ELAUNCH;
-    }
-    return MD_OK;
+    return launch_status();
 }
 
 __attribute__((visibility("default"))) int md_line_detector(const MdWorld* w, const MdState* s, const MdConfig* c,
@@ -3669,12 +3734,7 @@ __attribute__((visibility("default"))) int md_swap_draw(const MdState* s, const 
         return MD_EINVAL;
     }
     hipLaunchKernelGGL(swap_draw_kernel, dim3(c->n_envs), dim3(256), 0, (hipStream_t)stream, *s, *staged, *c, n_draws, draw_idx);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        snprintf(g_err, sizeof g_err, "kernel launch failed: %s", hipGetErrorString(err));
-        return MD_ELAUNCH;
-    }
-    return MD_OK;
+    return launch_status();
 }
 
 __attribute__((visibility("default"))) int md_line_detectors(const MdWorld* w, const MdState* s, const MdConfig* c,
@@ -3818,13 +3878,7 @@ __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdSta
                      md_sc_obs_lidar(c), c->n_beams);
             return MD_EINVAL;
         }
-        const size_t lds = (size_t)c->cap * (4 * 32 + 64 + 8 + 4) + (size_t)((c->cap + 3) & ~3) * 4 +
-                           (size_t)c->agents_per_env * sizeof(MdTrajLoc) + 16 +
-                           (size_t)(c->agents_per_env + 2) * (size_t)(c->n_side + c->n_lane_line) * sizeof(int) +
-                           ((c->n_side + c->n_lane_line) > 0 ? 2 * (size_t)kDetPairs * sizeof(int) : 0) +
-                           sc_scratch_bytes(s->route_n != nullptr, c->route_seg_cap, c->cap) + 16 +   // the decision stage's scratch / positions, links, lengths of a route being built
-                           (s->route_n ? (size_t)c->cap * 16 : 0) +   // route_n
-                           (size_t)c->cap * (sizeof(MdShape) + sizeof(RouteDesc)) + 32;   // the shapes the contact test sees; the route records
+        const size_t lds = scenario_lds(c->cap, c->agents_per_env, c->n_side + c->n_lane_line, s->route_n != nullptr, c->route_seg_cap).bytes;
         if (s->route_n) {
             NEED(s->route_segs); NEED(s->route_verts); NEED(s->route_aux); NEED(w->run_off); NEED(w->runs);
             if (c->route_seg_cap < 1 || c->route_vert_cap < 8) {
@@ -3839,12 +3893,7 @@ __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdSta
         }
         hipLaunchKernelGGL(scenario_step_kernel, dim3(c->n_envs), dim3(256), lds, (hipStream_t)stream, *w, *s, *c, s->obs, c->obs_dim,
                            md_sc_obs_lidar(c));
-        hipError_t err4 = hipGetLastError();
-        if (err4 != hipSuccess) {
-            snprintf(g_err, sizeof g_err, "kernel launch failed: %s", hipGetErrorString(err4));
-            return MD_ELAUNCH;
-        }
-        return MD_OK;
+        return launch_status();
     }
     if (c->obs_dim != md_obs_lidar(c) + c->n_beams + md_obs_tail(c)) {
         snprintf(g_err, sizeof g_err, "obs_dim=%d != %d state/navi dims + n_beams=%d + %d", c->obs_dim, md_obs_lidar(c), c->n_beams,
@@ -3864,12 +3913,7 @@ __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdSta
     if (r != MD_OK || c->num_others <= 0) return r;
     const int n = c->n_envs * c->agents_per_env;
     hipLaunchKernelGGL(others_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, *w, *s, *c);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        snprintf(g_err, sizeof g_err, "kernel launch failed: %s", hipGetErrorString(err));
-        return MD_ELAUNCH;
-    }
-    return MD_OK;
+    return launch_status();
 }
 
 }  // extern "C"
