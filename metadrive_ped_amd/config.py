@@ -22,7 +22,7 @@ BASE_DEFAULT_CONFIG = dict(
     allow_respawn=False,
     delay_done=0,
     # ===== action =====
-    agent_policy="EnvInputPolicy",   # or "IDMPolicy" (the class of that name is accepted too): envs/base_env.py:53
+    agent_policy="EnvInputPolicy",   # or "IDMPolicy" / "ExpertPolicy" (the class of that name is accepted too): envs/base_env.py:53
     discrete_action=False,
     use_multi_discrete=False,
     discrete_steering_dim=5,
@@ -124,6 +124,8 @@ BATCH_DEFAULT_CONFIG = dict(
     step_kernel="auto",     # single-agent md_step: "wg" = one 4-wave workgroup per env, "wave" = one wave per env, "auto" = by
                             # the number of distinct maps the batch shares (engine.WAVE_KERNEL_MAX_MAPS) (same
                             # results bit for bit; a machine-mapping choice)
+    expert_weights=None,    # agent_policy="ExpertPolicy" / expert.expert(): path of the reference's ppo_expert/expert_weights.npz;
+                            # None = found in an installed reference package (metadrive_ped_amd/expert.py)
 )
 
 # Keys of the reference's BASE_DEFAULT_CONFIG (envs/base_env.py:32-266) that only concern rendering, cameras, the GUI,
@@ -177,6 +179,30 @@ def _merge(dst, src, path=""):
             dst[k] = v
 
 
+def expert_config_problem(cfg):
+    """None if the PPO expert can drive envs of this config, else why not.  numpy_expert.py:58-62 rewrites the vehicle's
+    config to lidar (240 beams, 50 m, num_others=0, no noise, no dropout) and random_agent_model=False on every call, and
+    its observation must be 275-dim (:48): only the configs where that rewrite changes nothing are taken."""
+    why = "the reference's expert (examples/ppo_expert/numpy_expert.py) rewrites the vehicle config to this on every call"
+    if cfg.get("scenario_mode"):
+        return "agent_policy=ExpertPolicy / expert(): not in BatchedScenarioEnv (single-agent PG envs only)"
+    if cfg["is_multi_agent"]:
+        return "agent_policy=ExpertPolicy / expert(): not in the multi-agent envs (single-agent PG envs only)"
+    vc = cfg["vehicle_config"]
+    li = vc["lidar"]
+    want = dict(num_lasers=240, distance=50, num_others=0, gaussian_noise=0.0, dropout_prob=0.0, add_others_navi=False)
+    for k, v in want.items():
+        if li[k] != v:
+            return "vehicle_config['lidar']['{}']={!r}: the expert needs {!r} ({})".format(k, li[k], v, why)
+    for det in ("side_detector", "lane_line_detector"):
+        if vc[det]["num_lasers"] > 0 and vc[det]["distance"] > 0:
+            return ("vehicle_config['{}'] is on: the expert's observation would not be 275-dim ('Observation not match', "
+                    "numpy_expert.py:48)".format(det))
+    if cfg["random_agent_model"]:
+        return "random_agent_model=True: the expert needs False ({})".format(why)
+    return None
+
+
 def make_config(user=None):
     cfg = copy.deepcopy(BASE_DEFAULT_CONFIG)
     cfg.update(copy.deepcopy(METADRIVE_DEFAULT_CONFIG))
@@ -223,10 +249,14 @@ def make_config(user=None):
     # agent_policy: the reference takes a policy CLASS; here its name (or a class of that name)
     pol = cfg["agent_policy"]
     pol = pol if isinstance(pol, str) else getattr(pol, "__name__", repr(pol))
-    if pol not in ("EnvInputPolicy", "IDMPolicy"):
-        raise NotImplementedError("agent_policy={!r}: built are EnvInputPolicy (actions from step()), IDMPolicy and, in "
-                                  "BatchedScenarioEnv only, ReplayEgoCarPolicy".format(pol))
+    if pol not in ("EnvInputPolicy", "IDMPolicy", "ExpertPolicy"):
+        raise NotImplementedError("agent_policy={!r}: built are EnvInputPolicy (actions from step()), IDMPolicy, ExpertPolicy and, "
+                                  "in BatchedScenarioEnv only, ReplayEgoCarPolicy".format(pol))
     cfg["agent_policy"] = pol
+    if pol == "ExpertPolicy":
+        problem = expert_config_problem(cfg)
+        if problem:
+            raise ValueError(problem)
     if cfg["num_agents"] == -1:
         # "infinite agents" (spawn_manager.py:74-78, agent_manager.py:272-279, multi_agent_metadrive.py:86-92): every spawn
         # point holds an agent at reset and a new agent enters whenever a spawn region is clear, whatever the number on

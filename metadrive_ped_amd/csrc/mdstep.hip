@@ -19,13 +19,15 @@
 //   * trigger   : wavefront min-reduce (DPP shuffles) over the pending traffic blocks.
 //   * integrate / observe / IDM : one thread per entity over include/md_entity.h.
 //
-// There is no dense contraction anywhere on this path, hence no MFMA.  The arithmetic formulas are
-// the shared include/md_geom.h / md_entity.h ones (bit-exact vs the CPU oracle, -ffp-contract=off).
+// There is no dense contraction on the step path, hence no MFMA there; the one exception is md_expert (the PPO expert's
+// MLP, include/md_expert.h), which runs on v_mfma_f32_16x16x4_f32.  The arithmetic formulas are the shared
+// include/md_geom.h / md_entity.h ones (bit-exact vs the CPU oracle, -ffp-contract=off).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "md_expert.h"
 #include "md_scenario.h"
 
 namespace {
@@ -3429,6 +3431,132 @@ __global__ __launch_bounds__(64) void others_kernel(MdWorld w, MdState g, MdConf
                     s.obs + (size_t)a * c.obs_dim + md_obs_others(&c));
 }
 
+// ----------------------------------------------------------------------------------------------------------------------------
+// md_expert: the PPO expert (numpy_expert.py:34-77) over the batch.  One workgroup of 4 waves per tile of 16 envs:
+//   1. x = the expert's 275-vector of each env in LDS (the env's obs row + the "others" block of md_others_block with
+//      num_others = 4), corrected; rows past the last env stay zero and are never written out;
+//   2. h1 = tanh(x W1 + b1), h2 = tanh(h1 W2 + b2): wave w owns the output columns [64w, 64w + 64) as four 16x16 tiles,
+//      every tile ONE accumulator chained over the k-steps in order (A = 16 env rows from LDS, B = one 16-byte load per
+//      lane per four k-steps from the packed weights, which stay in L2), bias as the accumulator's start value;
+//   3. out = h2 W3 + b3 on wave 0 (one tile, N padded to 16), then mean / log_std / action.
+// Each output element is the k-ordered fmaf chain of include/md_expert.h: v_mfma_f32_16x16x4_f32 rounds once per product
+// in k order, and nothing else touches the accumulator.
+constexpr int kExpM = 16;                                  // envs per workgroup (the MFMA's M)
+constexpr int kExpXS = MD_EXPERT_IN_PAD + 4;               // LDS row strides: = 4 mod 32, so the 16 rows x 4 k of one
+constexpr int kExpHS = MD_EXPERT_HID + 4;                  //   A-operand read spread over the banks
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// acc[j] (+)= A[16 rows][K] . W[K][tile nt0 + j], j < NT; A row r at a + r * lda, W packed (md_expert_widx)
+template <int NT>
+__device__ __forceinline__ void expert_tiles(const float* __restrict__ W, int K, int nt0, const float* a, int lda, int lane,
+                                             f32x4* acc) {
+    const int G = K >> 4;
+    const float* arow = a + (lane & 15) * lda + (lane >> 4);
+    const f32x4* wp[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) wp[j] = reinterpret_cast<const f32x4*>(W + (size_t)(nt0 + j) * G * 256) + lane;
+    f32x4 cur[NT], nxt[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) cur[j] = wp[j][0];
+    for (int g = 0; g < G; ++g) {
+        if (g + 1 < G) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j) nxt[j] = wp[j][(size_t)(g + 1) * 64];
+        }
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            const float av = arow[16 * g + 4 * st];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, cur[j][st], acc[j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) cur[j] = nxt[j];
+    }
+}
+
+// one hidden layer: out[r][n] = tanh(in[r] . W[:, n] + b[n]) for the 64 columns of this wave
+__device__ __forceinline__ void expert_hidden(const float* __restrict__ W, const float* __restrict__ b, int K, const float* in,
+                                              int lds_in, float* out, int wave, int lane) {
+    f32x4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float bv = b[(4 * wave + j) * 16 + (lane & 15)];
+        acc[j] = f32x4{bv, bv, bv, bv};
+    }
+    expert_tiles<4>(W, K, 4 * wave, in, lds_in, lane, acc);
+    // C/D layout of the 16x16 MFMAs: column = lane & 15, row = (lane >> 4) * 4 + register
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) out[((lane >> 4) * 4 + r) * kExpHS + (4 * wave + j) * 16 + (lane & 15)] = md_tanh(acc[j][r]);
+}
+
+__global__ __launch_bounds__(256) void expert_kernel(MdWorld w, MdState g, MdConfig c, const float* __restrict__ wts,
+                                                     const float* __restrict__ noise, float* __restrict__ action_out,
+                                                     float* __restrict__ mlp_out, float* __restrict__ obs_out) {
+    __shared__ __attribute__((aligned(16))) float l_x[kExpM * kExpXS];   // x; later h2 (stride kExpHS)
+    __shared__ __attribute__((aligned(16))) float l_h[kExpM * kExpHS];   // h1
+    __shared__ float l_out[kExpM * MD_EXPERT_OUT];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int e0 = blockIdx.x * kExpM;
+    const int n_here = min(kExpM, c.n_envs - e0);
+    const int od = c.obs_dim;   // 259: state 19 | cloud 240
+    // 1. the expert's observation
+    for (int i = tid; i < kExpM * kExpXS; i += 256) {
+        const int r = i / kExpXS, k = i - r * kExpXS;
+        float v = 0.0f;
+        if (r < n_here && k < MD_EXPERT_IN) {
+            const float* o = g.obs + (size_t)(e0 + r) * od;
+            if (k < MD_EXPERT_STATE) v = o[k];
+            else if (k >= MD_EXPERT_STATE + 4 * MD_EXPERT_OTHERS) v = o[k - 4 * MD_EXPERT_OTHERS];
+        }
+        l_x[i] = v;
+    }
+    __syncthreads();
+    if (tid < n_here) {
+        MdConfig cc = c;                          // the expert's lidar: num_others = 4, no navigation dims of the others
+        cc.num_others = MD_EXPERT_OTHERS;
+        cc.add_others_navi = 0;
+        const int e = e0 + tid;
+        const MdState s = md_env_view(&g, &c, e);
+        const int m = w.env_map[e];
+        float* x = l_x + tid * kExpXS;
+        md_others_block(w.lanes + w.lane_off[m], w.roads + w.road_off[m], &s, &cc, 0, s.detected[0], s.detected[1],
+                        x + MD_EXPERT_STATE);
+        md_expert_correct(x);
+    }
+    __syncthreads();
+    if (obs_out)
+        for (int i = tid; i < n_here * MD_EXPERT_IN; i += 256) {
+            const int r = i / MD_EXPERT_IN, k = i - r * MD_EXPERT_IN;
+            obs_out[(size_t)e0 * MD_EXPERT_IN + i] = l_x[r * kExpXS + k];
+        }
+    // 2. hidden layers
+    expert_hidden(wts + MD_EXPERT_W1, wts + MD_EXPERT_B1, MD_EXPERT_IN_PAD, l_x, kExpXS, l_h, wave, lane);
+    __syncthreads();
+    expert_hidden(wts + MD_EXPERT_W2, wts + MD_EXPERT_B2, MD_EXPERT_HID, l_h, kExpHS, l_x, wave, lane);
+    __syncthreads();
+    // 3. output layer (one 16x16 tile; columns 4..15 are zero padding)
+    if (wave == 0) {
+        const float bv = wts[MD_EXPERT_B3 + (lane & 15)];
+        f32x4 acc[1] = {f32x4{bv, bv, bv, bv}};
+        expert_tiles<1>(wts + MD_EXPERT_W3, MD_EXPERT_HID, 0, l_x, kExpHS, lane, acc);
+        if ((lane & 15) < MD_EXPERT_OUT)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) l_out[((lane >> 4) * 4 + r) * MD_EXPERT_OUT + (lane & 15)] = acc[0][r];
+    }
+    __syncthreads();
+    if (tid < n_here * MD_EXPERT_OUT) {
+        const int r = tid >> 2, q = tid & 3;
+        const size_t e = (size_t)(e0 + r);
+        if (mlp_out) mlp_out[e * MD_EXPERT_OUT + q] = l_out[tid];
+        if (q < 2) {
+            const float mean = l_out[r * MD_EXPERT_OUT + q];
+            action_out[e * 2 + q] = noise ? md_expert_sample(mean, l_out[r * MD_EXPERT_OUT + 2 + q], noise[e * 2 + q]) : mean;
+        }
+    }
+}
+
 __global__ void probe_kernel(int op, const float* a, const float* b, float* out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = md_probe_eval(op, a[i], b[i]);
@@ -3913,6 +4041,30 @@ __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdSta
     if (r != MD_OK || c->num_others <= 0) return r;
     const int n = c->n_envs * c->agents_per_env;
     hipLaunchKernelGGL(others_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, *w, *s, *c);
+    return launch_status();
+}
+
+__attribute__((visibility("default"))) int md_expert(const MdWorld* w, const MdState* s, const MdConfig* c, const float* weights,
+                                                    const float* noise, float* action_out, float* mlp_out, float* obs_out,
+                                                    void* stream) {
+    int r = check_common(w, s, c);
+    if (r != MD_OK) return r;
+    NEED(weights); NEED(action_out); NEED(s->obs); NEED(s->detected); NEED(s->dyn); NEED(s->param); NEED(s->nav);
+    NEED(w->env_map); NEED(w->lanes); NEED(w->lane_off); NEED(w->roads); NEED(w->road_off);
+    // the configs where the reference's rewrite of the vehicle config (numpy_expert.py:58-62) changes nothing
+    if (c->is_multi_agent || c->agents_per_env != 1 || c->traffic_mode == 4 || c->n_beams != 240 || c->lidar_range != 50.0f ||
+        c->num_others != 0 || c->n_side != 0 || c->n_lane_line != 0 || c->random_agent_model != 0 ||
+        c->obs_dim != MD_EXPERT_IN - 4 * MD_EXPERT_OTHERS) {
+        snprintf(g_err, sizeof g_err, "md_expert: needs a single-agent batch with the expert's lidar (240 beams, 50 m, num_others 0), "
+                 "no side / lane-line detector and random_agent_model off (obs_dim 259)");
+        return MD_EINVAL;
+    }
+    if ((uintptr_t)weights & 15) {
+        snprintf(g_err, sizeof g_err, "md_expert: the packed weights must be 16-byte aligned");
+        return MD_EINVAL;
+    }
+    hipLaunchKernelGGL(expert_kernel, dim3((c->n_envs + kExpM - 1) / kExpM), dim3(256), 0, (hipStream_t)stream, *w, *s, *c, weights,
+                       noise, action_out, mlp_out, obs_out);
     return launch_status();
 }
 

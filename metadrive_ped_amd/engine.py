@@ -309,7 +309,9 @@ class HostScene:
             st["env_steps"] = np.zeros(E, np.int32)
             st["agent_id"] = np.tile(np.arange(cap, dtype=np.int32), E)
             st["next_agent_id"] = np.full(E, cfg["initial_agents"] or A, np.int32)   # names agent0 .. agent{n-1} are taken
-        if self.num_others > 0:
+        if self.num_others > 0 or cfg["agent_policy"] == "ExpertPolicy":
+            # ExpertPolicy: the expert's own "others" block (num_others=4) is computed by md_expert from these sets; the env's
+            # obs keeps its 259 dims (md_step tracks the sets whenever the array is there)
             st["detected"] = np.zeros((E * A, 2), np.uint64)
         if cfg["is_multi_agent"] and cfg["marl_map"] == "racing":
             st["idle_ring"] = np.zeros((E * A, abi.MD_IDLE_WINDOW), np.float32)     # movement_between_steps of every agent
@@ -415,6 +417,9 @@ class BatchedEngine:
                                    "fallback".format(cfg["device"]))
         self.host = host
         self._noise_gen = None
+        self._expert_gen = None
+        self._expert_w = None
+        self._track_det = False
         self._rec = None
         self._tracks = None
         if self.device.index is None:
@@ -462,6 +467,8 @@ class BatchedEngine:
             draws = [HostScene(self._draw_cfg(k, self.host.cap)) for k in range(1, K)]
         self.draw_hosts_ = [self.host] + (draws or [])
         h = self.host
+        if self._track_det and "detected" not in h.state:       # expert() was called on this engine before a rebuild
+            h.state["detected"] = np.zeros((h.E * h.A, 2), np.uint64)
         self.E, self.A, self.cap = h.E, h.A, h.cap
         self.n_beams, self.obs_dim = h.n_beams, h.obs_dim
         self.world_dev = {k: self._to_dev(v) for k, v in h.world.arrays.items()}
@@ -655,14 +662,68 @@ class BatchedEngine:
                                               n, C.c_float(dist), C.c_uint32(mask), C.c_void_p(out.data_ptr()), stride, offset,
                                               self._stream()), "md_line_detector")
 
+    # -- the PPO expert (metadrive_ped_amd/expert.py, md_expert) -----------------------------------------------------------
+    def _track_detected(self):
+        """expert() on an engine that does not keep the lidar's detected sets (agent_policy other than ExpertPolicy): from
+        now on md_step keeps them (its general variant: same results), and md_lidar_detect fills them for the current state."""
+        if "detected" in self.state_dev:
+            return
+        self._track_det = True
+        h = self.host
+        h.state["detected"] = np.zeros((h.E * h.A, 2), np.uint64)
+        self.state_dev["detected"] = self._to_dev(h.state["detected"])
+        self.s.detected = self.state_dev["detected"].data_ptr()
+        scratch = self.torch.empty((self.E * self.A, self.n_beams), dtype=self.torch.float32, device=self.device)
+        with self._on_device():
+            self._check(self.lib.md_lidar_detect(C.byref(self.w), C.byref(self.s), C.byref(self.k), C.c_void_p(scratch.data_ptr()),
+                                                 self.n_beams, 0, C.c_void_p(self.state_dev["detected"].data_ptr()), self._stream()),
+                        "md_lidar_detect")
+
+    def expert_weights(self):
+        """The packed expert weights on the device (uploaded once per engine)."""
+        if self._expert_w is None:
+            from metadrive_ped_amd.expert import load_expert_weights
+            self._expert_w = self.torch.from_numpy(load_expert_weights(self.cfg.get("expert_weights"))).to(self.device)
+        return self._expert_w
+
+    def expert_forward(self, deterministic=False, need_obs=False, action_out=None, mlp_out=None):
+        """ONE md_expert launch on the current observation -> action [E, 2] (+ the corrected expert obs [E, 275] with
+        need_obs).  deterministic=False: action = mean + exp(log_std) * N(0, 1), one [E, 2] draw of the engine's expert
+        generator (seeded with start_seed + env_seed_offset)."""
+        torch = self.torch
+        if self.A != 1:
+            raise ValueError("the expert drives single-agent envs")
+        self._track_detected()
+        w = self.expert_weights()
+        noise = None
+        if not deterministic:
+            if self._expert_gen is None:
+                self._expert_gen = torch.Generator(device=self.device)
+                self._expert_gen.manual_seed(int(self.cfg["start_seed"]) + int(self.cfg["env_seed_offset"]))
+            noise = torch.randn((self.E, 2), dtype=torch.float32, device=self.device, generator=self._expert_gen)
+        if action_out is None:
+            action_out = torch.empty((self.E, 2), dtype=torch.float32, device=self.device)
+        obs = torch.empty((self.E, 275), dtype=torch.float32, device=self.device) if need_obs else None
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+        with self._on_device():
+            self._check(self.lib.md_expert(C.byref(self.w), C.byref(self.s), C.byref(self.k), ptr(w), ptr(noise), ptr(action_out),
+                                           ptr(mlp_out), ptr(obs), self._stream()), "md_expert")
+        return (action_out, obs) if need_obs else action_out
+
     def step(self, actions):
         """actions: tensor [E, A, 2] (or [E, 2] when A == 1), float32, on the engine's device.  With agent_policy =
         IDMPolicy the agents drive themselves: `actions` is ignored (None is fine), as the reference's IDMPolicy ignores
-        what env.step() is given."""
+        what env.step() is given.  With agent_policy = ExpertPolicy likewise: the expert acts on the state the previous
+        step left (ExpertPolicy.act in before_step), then the world steps with that action.  An env that auto-resets in
+        this step discards it (md_step restores the env instead of moving it); its next action comes from the reset state."""
         if self.k.agent_idm:
             self.s.agent_action = None
             self.step_raw()
             return
+        if self.cfg["agent_policy"] == "ExpertPolicy":
+            if getattr(self, "_expert_action", None) is None or self._expert_action.shape[0] != self.E:
+                self._expert_action = self.torch.empty((self.E, 2), dtype=self.torch.float32, device=self.device)
+            actions = self.expert_forward(deterministic=False, action_out=self._expert_action)
         a = actions
         if a.dim() == 2:
             a = a.unsqueeze(1)

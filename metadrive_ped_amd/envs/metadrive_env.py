@@ -126,7 +126,7 @@ class BatchedMetaDriveEnv:
             raise RuntimeError("call reset() before step()")
         torch = self.engine.torch
         a = actions
-        if self.config["agent_policy"] == "IDMPolicy":     # the agents drive themselves; `actions` is ignored
+        if self.config["agent_policy"] in ("IDMPolicy", "ExpertPolicy"):     # the agents drive themselves; `actions` is ignored
             self.engine.step(None)
             terminated, truncated = self._done_flags()
             return self._obs(), self.engine.reward[:, 0], terminated, truncated, self._info()

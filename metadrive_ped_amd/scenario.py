@@ -63,6 +63,8 @@ def make_scenario_config(user=None):
     pol = user.get("agent_policy", "EnvInputPolicy")
     pol = pol if isinstance(pol, str) else getattr(pol, "__name__", repr(pol))
     ego_replay = pol == "ReplayEgoCarPolicy"
+    if pol == "ExpertPolicy":
+        raise NotImplementedError("agent_policy=ExpertPolicy: not in BatchedScenarioEnv (single-agent PG envs only)")
     if ego_replay:
         user.pop("agent_policy")
     own = {}
