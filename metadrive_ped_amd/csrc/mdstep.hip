@@ -1539,6 +1539,71 @@ constexpr int kStageMaxLanes = 64;
 constexpr int kWideMaxEnvs = 640;   // multi-agent batches up to this many envs step with eight waves per env (see launch<>)
 constexpr uint32_t kRemovedMark = 0xFFFFFFFFu;  // l_cfl value of a traffic slot removed in this step
 
+// k-th set bit of (hi:lo), -1 if there is none
+__device__ __forceinline__ int kth_bit(unsigned long long lo, unsigned long long hi, int k) {
+    int slot = -1;
+    while (k >= 0) {
+        if (lo) {
+            slot = __ffsll((long long)lo) - 1;
+            lo &= lo - 1;
+        } else if (hi) {
+            slot = 64 + __ffsll((long long)hi) - 1;
+            hi &= hi - 1;
+        } else {
+            return -1;
+        }
+        --k;
+    }
+    return slot;
+}
+
+// The staged records of one env in LDS, at the offsets of the kernel's layout (env_lds, wave_env_lds, scenario_lds).
+struct EnvImage {
+    MdShape* shape;
+    MdDyn* dyn;
+    MdPid* pid;
+    MdParam* param;
+    MdNav* nav;
+    float* action;  // [cap][2]
+    uint32_t* flags;
+    int32_t* final_lane;  // nullptr where the kernel does not stage it (scenes)
+};
+
+// The env-local view of the state: gv with its hot arrays in the image
+__device__ __forceinline__ MdState local_view(const MdState& gv, const EnvImage& img) {
+    MdState s = gv;
+    s.shape = img.shape;
+    s.dyn = img.dyn;
+    s.nav = img.nav;
+    s.pid = img.pid;
+    s.action = img.action;
+    s.flags = img.flags;
+    s.param = img.param;
+    s.final_lane = img.final_lane;
+    return s;
+}
+
+// The slots that drive (md_drives), as a mask of up to 128 slots (hi:lo), the same in every lane of the wave
+struct SlotMask { unsigned long long lo, hi; };
+static_assert(MD_MAX_CAP <= 128, "drive_mask: two 64-bit words per env");
+__device__ __forceinline__ SlotMask drive_mask(const MdShape* shape, int cap, int lane) {
+    SlotMask m = {0ull, 0ull};
+    for (int j0 = 0; j0 < cap; j0 += 64) {
+        const int j = j0 + lane;
+        const unsigned long long mk = __ballot(j < cap && md_drives(shape[j < cap ? j : 0].flags));
+        if (j0 == 0) m.lo = mk;
+        else m.hi = mk;
+    }
+    return m;
+}
+// ... its agents' share (slots [0, agents): the ones whose contacts are tested)
+__device__ __forceinline__ SlotMask agent_share(SlotMask m, int agents) {
+    m.lo &= agents >= 64 ? ~0ull : ((1ull << agents) - 1ull);
+    m.hi &= agents <= 64 ? 0ull : (agents >= 128 ? ~0ull : ((1ull << (agents - 64)) - 1ull));
+    return m;
+}
+__device__ __forceinline__ int popc(SlotMask m) { return __popcll(m.lo) + __popcll(m.hi); }
+
 // RESPAWN: the variant for everything off the headline path -- traffic modes respawn / hybrid / replay, detected
 // sets for the `num_others` block (compiled apart: its slot-rewriting code costs the common trigger-mode
 // kernel 8 VGPRs and one wave of occupancy when it is merely branched around).
@@ -1623,6 +1688,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     MdParam* l_param = reinterpret_cast<MdParam*>(smem + L.param);
     int32_t* l_final = reinterpret_cast<int32_t*>(smem + L.final_lane);
     unsigned long long* l_det = reinterpret_cast<unsigned long long*>(smem + L.det);
+    const EnvImage img = {l_shape, l_dyn, l_pid, l_param, l_nav, l_action, l_flags, l_final};
     uint32_t* l_onlane = reinterpret_cast<uint32_t*>(smem + L.onlane);
     uint32_t* l_cfl = reinterpret_cast<uint32_t*>(smem + L.cfl);
     int* l_tk = reinterpret_cast<int*>(smem + L.tk);
@@ -1752,16 +1818,10 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
             }
         }
     }
-    MdState s = gv;  // env-local view whose hot arrays live in LDS
-    s.shape = l_shape;
-    if (!kLidarOnly) {
-        s.dyn = l_dyn;
-        s.nav = l_nav;
-        s.pid = l_pid;
-        s.action = l_action;
-        s.flags = l_flags;
-        s.param = l_param;
-        s.final_lane = l_final;
+    MdState s = local_view(gv, img);  // env-local view whose hot arrays live in LDS
+    if (kLidarOnly) {   // the lidar-only image holds the shapes alone
+        s = gv;
+        s.shape = l_shape;
     }
     if ((MULTI || PH == PH_ALL) && tid == 0) l_tk[0] = l_tk[1] = l_tk[2] = 0;
     __syncthreads();
@@ -1809,35 +1869,13 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         // poses and the map), so they share ONE stage: work items = [localize of every driving vehicle, then
         // contacts of every driving vehicle], dealt round-robin to the waves.  With the usual 1-3 driving
         // vehicles per env everything fits one round instead of two phases behind two barriers.
-        for (int j0 = 0; j0 < cap; j0 += 64) {
-            const int j = j0 + lane;
-            const unsigned long long mk = __ballot(j < cap && md_drives(s.shape[j < cap ? j : 0].flags));
-            if (j0 == 0) drv_lo = mk;
-            else drv_hi = mk;
-        }
+        const SlotMask drv = drive_mask(s.shape, cap, lane);
+        drv_lo = drv.lo;
+        drv_hi = drv.hi;
         // contacts only for agents (traffic's crash flags are never read): their slots are the first A
-        const int A_ = c.agents_per_env;
-        const unsigned long long a_lo = A_ >= 64 ? ~0ull : ((1ull << A_) - 1ull);
-        const unsigned long long a_hi = A_ <= 64 ? 0ull : (A_ >= 128 ? ~0ull : ((1ull << (A_ - 64)) - 1ull));
-        const unsigned long long adrv_lo = drv_lo & a_lo, adrv_hi = drv_hi & a_hi;
-        const int nd = __popcll(drv_lo) + __popcll(drv_hi);
-        const int na = __popcll(adrv_lo) + __popcll(adrv_hi);
-        const auto kth = [](unsigned long long lo, unsigned long long hi, int k) {  // k-th set bit of (hi:lo), -1 if none
-            int slot = -1;
-            while (k >= 0) {
-                if (lo) {
-                    slot = __ffsll((long long)lo) - 1;
-                    lo &= lo - 1;
-                } else if (hi) {
-                    slot = 64 + __ffsll((long long)hi) - 1;
-                    hi &= hi - 1;
-                } else {
-                    return -1;
-                }
-                --k;
-            }
-            return slot;
-        };
+        const SlotMask adrv = agent_share(drv, c.agents_per_env);
+        const unsigned long long adrv_lo = adrv.lo, adrv_hi = adrv.hi;
+        const int nd = popc(drv), na = popc(adrv);
         if (MULTI) {
             // every workgroup of a multi-agent batch is resident at once: the launch lasts as long as its slowest env, and inside
             // an env as long as the wave with the most expensive items -- the waves take the items by ticket, contacts (the
@@ -1848,24 +1886,24 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
                 if (lane == 0) item = atomicAdd(&l_tk[0], 1);
                 item = __builtin_amdgcn_readfirstlane(item);
                 if (item < 0 || item >= npair + na) break;
-                if (item < na) contacts_vehicle(w, s, c, e, kth(adrv_lo, adrv_hi, item), lane, l_cfl);
-                else localize_pair(w, lanes, roads, s, e, kth(drv_lo, drv_hi, 2 * (item - na)), kth(drv_lo, drv_hi, 2 * (item - na) + 1), lane, l_onlane);
+                if (item < na) contacts_vehicle(w, s, c, e, kth_bit(adrv_lo, adrv_hi, item), lane, l_cfl);
+                else localize_pair(w, lanes, roads, s, e, kth_bit(drv_lo, drv_hi, 2 * (item - na)), kth_bit(drv_lo, drv_hi, 2 * (item - na) + 1), lane, l_onlane);
             }
         } else if (nd + na <= kWaves) {
             // everything fits one round: one wave per job, the vehicle's data in scalar registers
             for (int item = wave; item < nd + na; item += kWaves) {
                 if (item < nd) {
-                    if (!(MD_ENV_SKIP & 4)) localize_vehicle(w, lanes, roads, s, e, kth(drv_lo, drv_hi, item), lane, l_onlane);
-                } else if (!(MD_ENV_SKIP & 8)) contacts_vehicle(w, s, c, e, kth(adrv_lo, adrv_hi, item - nd), lane, l_cfl);
+                    if (!(MD_ENV_SKIP & 4)) localize_vehicle(w, lanes, roads, s, e, kth_bit(drv_lo, drv_hi, item), lane, l_onlane);
+                } else if (!(MD_ENV_SKIP & 8)) contacts_vehicle(w, s, c, e, kth_bit(adrv_lo, adrv_hi, item - nd), lane, l_cfl);
             }
         } else {
             // many vehicles awake: two localisations per wave (32 lanes each), halving the rounds
             const int npair = (nd + 1) >> 1;
             for (int item = wave; item < npair + na; item += kWaves) {
                 if (item < npair) {
-                    if (!(MD_ENV_SKIP & 4)) localize_pair(w, lanes, roads, s, e, kth(drv_lo, drv_hi, 2 * item), kth(drv_lo, drv_hi, 2 * item + 1), lane, l_onlane);
+                    if (!(MD_ENV_SKIP & 4)) localize_pair(w, lanes, roads, s, e, kth_bit(drv_lo, drv_hi, 2 * item), kth_bit(drv_lo, drv_hi, 2 * item + 1), lane, l_onlane);
                 } else if (!(MD_ENV_SKIP & 8))
-                    contacts_vehicle(w, s, c, e, kth(adrv_lo, adrv_hi, item - npair), lane, l_cfl);
+                    contacts_vehicle(w, s, c, e, kth_bit(adrv_lo, adrv_hi, item - npair), lane, l_cfl);
             }
         }
         __syncthreads();
@@ -2058,24 +2096,6 @@ __host__ __device__ inline WaveEnvLds wave_env_lds(int cap, int agents) {
 static_assert((sizeof(MdShape) + sizeof(MdDyn) + sizeof(MdPid) + sizeof(MdParam) + sizeof(MdNav) + 6 * 4) % 8 == 0 && 48 * 4 % 8 == 0,
               "wave_env_lds: the detected sets need 8-B alignment");
 
-// k-th set bit of (hi:lo), -1 if there is none
-__device__ __forceinline__ int kth_bit(unsigned long long lo, unsigned long long hi, int k) {
-    int slot = -1;
-    while (k >= 0) {
-        if (lo) {
-            slot = __ffsll((long long)lo) - 1;
-            lo &= lo - 1;
-        } else if (hi) {
-            slot = 64 + __ffsll((long long)hi) - 1;
-            hi &= hi - 1;
-        } else {
-            return -1;
-        }
-        --k;
-    }
-    return slot;
-}
-
 template <bool RESPAWN>
 __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
                                                                   int lidar_stride, int lidar_offset) {
@@ -2100,6 +2120,7 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
     uint32_t* l_cfl = reinterpret_cast<uint32_t*>(base + L.cfl);
     float* l_scratch = reinterpret_cast<float*>(base + L.scratch);
     unsigned long long* l_det = reinterpret_cast<unsigned long long*>(base + L.det);
+    const EnvImage img = {l_shape, l_dyn, l_pid, l_param, l_nav, l_action, l_flags, l_final};
     const bool track_det = RESPAWN && g.detected != nullptr;
 
     const MdState gv = md_env_view(&g, &c, e);
@@ -2195,15 +2216,7 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
             for (int j = lane; j < cap; j += 64) l_final[j] = gv.final_lane0[j];
         }
     }
-    MdState s = gv;   // env-local view whose hot arrays live in this wave's LDS image
-    s.shape = l_shape;
-    s.dyn = l_dyn;
-    s.nav = l_nav;
-    s.pid = l_pid;
-    s.action = l_action;
-    s.flags = l_flags;
-    s.param = l_param;
-    s.final_lane = l_final;
+    MdState s = local_view(gv, img);   // env-local view whose hot arrays live in this wave's LDS image
     wave_sync();
     MD_STAMP_AT(1);
 
@@ -2223,13 +2236,8 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
     }
     MD_STAMP_AT(3);
     // the slots that drive in this step (the integration does not change any slot's flags)
-    unsigned long long drv_lo = 0ull, drv_hi = 0ull;
-    for (int j0 = 0; j0 < cap; j0 += 64) {
-        const int j = j0 + lane;
-        const unsigned long long mk = __ballot(j < cap && md_drives(s.shape[j < cap ? j : 0].flags));
-        if (j0 == 0) drv_lo = mk;
-        else drv_hi = mk;
-    }
+    const SlotMask drv = drive_mask(s.shape, cap, lane);
+    const unsigned long long drv_lo = drv.lo, drv_hi = drv.hi;
     if (!just_reset) {
         for (int j = lane; j < cap; j += 64) {
             if (RESPAWN) md_advance_mover(&s, &c, j);
@@ -2242,11 +2250,9 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
     MD_STAMP_AT(4);
     // ---- localisation of every driving vehicle, contacts of every driving agent ----
     {
-        const unsigned long long a_lo = A >= 64 ? ~0ull : ((1ull << A) - 1ull);
-        const unsigned long long a_hi = A <= 64 ? 0ull : (A >= 128 ? ~0ull : ((1ull << (A - 64)) - 1ull));
-        const unsigned long long adrv_lo = drv_lo & a_lo, adrv_hi = drv_hi & a_hi;
-        const int nd = __popcll(drv_lo) + __popcll(drv_hi);
-        const int na = __popcll(adrv_lo) + __popcll(adrv_hi);
+        const SlotMask adrv = agent_share(drv, A);
+        const unsigned long long adrv_lo = adrv.lo, adrv_hi = adrv.hi;
+        const int nd = popc(drv), na = popc(adrv);
         // one vehicle: the whole wave, its data in scalar registers; two: 32 lanes each; more: 16 lanes each, four per pass
         if (nd == 1) localize_vehicle(w, lanes, roads, s, e, kth_bit(drv_lo, drv_hi, 0), lane, l_onlane);
         else if (nd == 2) localize_pair(w, lanes, roads, s, e, kth_bit(drv_lo, drv_hi, 0), kth_bit(drv_lo, drv_hi, 1), lane, l_onlane);
@@ -2979,6 +2985,7 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
     float* l_action = reinterpret_cast<float*>(smem + L.action);
     uint32_t* l_flags = reinterpret_cast<uint32_t*>(smem + L.flags);
     uint32_t* l_cfl = reinterpret_cast<uint32_t*>(smem + L.cfl);
+    const EnvImage img = {l_shape, l_dyn, l_pid, l_param, l_nav, l_action, l_flags, nullptr};   // a scene stages no final lanes
     MdTrajLoc* l_loc = reinterpret_cast<MdTrajLoc*>(smem + L.loc);
     int* l_count = reinterpret_cast<int*>(smem + L.count);
     int* l_dbest = reinterpret_cast<int*>(smem + L.dbest);   // [A][n_det] when md_step runs the detectors
@@ -3120,15 +3127,9 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
         for (int it = tid; it < 2 * n_det; it += kBlock)
             l_beams[it] = (it < 2 * ns) ? w.side_beam_cs[it] : w.ll_beam_cs[it - 2 * ns];
     }
-    MdState s = gv;
+    MdState s = local_view(gv, img);
+    s.final_lane = gv.final_lane;   // not staged
     if (gv.route_n) s.route_n = l_rn;
-    s.shape = l_shape;
-    s.dyn = l_dyn;
-    s.nav = l_nav;
-    s.pid = l_pid;
-    s.action = l_action;
-    s.flags = l_flags;
-    s.param = l_param;
     s.next_agent_id = l_count;
     __syncthreads();
     MD_STAMP_AT(1);
