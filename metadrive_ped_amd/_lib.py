@@ -30,32 +30,10 @@ def load():
             "HIP library not found: {}\nBuild it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback.".format(LIB_PATH))
     lib = C.CDLL(LIB_PATH)
-    lib.md_abi.restype = C.c_int
-    lib.md_abi.argtypes = [C.POINTER(C.c_int32), C.c_int]
-    lib.md_last_error.restype = C.c_char_p
-    W, S, K = C.POINTER(abi.MdWorld), C.POINTER(abi.MdState), C.POINTER(abi.MdConfig)
-    for name in ("md_integrate", "md_localize", "md_contacts", "md_observe", "md_idm", "md_traffic_after_step", "md_lifecycle", "md_step"):
+    optional = {n: sig for n, sig in abi.OPTIONAL_ENTRY_POINTS.items() if hasattr(lib, n)}
+    for name, (restype, argtypes) in dict(abi.ENTRY_POINTS, **abi.EXPERT_ENTRY_POINTS, **optional).items():
         fn = getattr(lib, name)
-        fn.restype = C.c_int
-        fn.argtypes = [W, S, K, C.c_void_p]
-    lib.md_lidar.restype = C.c_int
-    lib.md_lidar.argtypes = [W, S, K, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    lib.md_lidar_detect.restype = C.c_int
-    lib.md_lidar_detect.argtypes = [W, S, K, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.md_expert.restype = C.c_int
-    lib.md_expert.argtypes = [W, S, K, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.md_swap_draw.restype = C.c_int
-    lib.md_swap_draw.argtypes = [S, S, K, C.c_int, C.c_void_p, C.c_void_p]
-    lib.md_line_detectors.restype = C.c_int
-    lib.md_line_detectors.argtypes = [W, S, K, C.c_void_p, C.c_int, C.c_float, C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_uint32,
-                                      C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-    lib.md_line_detector.restype = C.c_int
-    lib.md_line_detector.argtypes = [W, S, K, C.c_void_p, C.c_int, C.c_float, C.c_uint32, C.c_void_p, C.c_int, C.c_int,
-                                     C.c_void_p]
-    lib.md_probe_math.restype = C.c_int
-    lib.md_probe_math.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-    lib.md_probe_stream_copy.restype = C.c_int
-    lib.md_probe_stream_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        fn.restype, fn.argtypes = restype, argtypes
     abi.check_abi(lib.md_abi, LIB_PATH)
     _LIB = lib
     return lib

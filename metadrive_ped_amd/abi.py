@@ -155,9 +155,28 @@ STRUCT_NAMES = ["MdShape", "MdDyn", "MdParam", "MdNav", "MdPid", "MdLane", "MdRo
 WORLD_FIELDS = [f for f, t in MdWorld._fields_ if t is P]
 STATE_FIELDS = [f for f, t in MdState._fields_ if t is P]
 
-# symbols include/mdstep.h declares; tests check every one is exported
-ENTRY_POINTS = ["md_abi", "md_last_error", "md_probe_math", "md_probe_stream_copy", "md_lidar", "md_lidar_detect", "md_line_detector", "md_line_detectors", "md_swap_draw", "md_integrate", "md_localize",
-                "md_contacts", "md_observe", "md_idm", "md_traffic_after_step", "md_lifecycle", "md_step"]
+_W, _S, _K = C.POINTER(MdWorld), C.POINTER(MdState), C.POINTER(MdConfig)
+_i, _f, _u = C.c_int, C.c_float, C.c_uint32
+_PHASE = (_i, [_W, _S, _K, P])
+# the C-ABI's functions, name -> (restype, argtypes), one table per header; _lib.load() sets them all
+# include/mdstep.h
+ENTRY_POINTS = {
+    "md_abi": (_i, [C.POINTER(C.c_int32), _i]),
+    "md_last_error": (C.c_char_p, []),
+    "md_probe_math": (_i, [_i, P, P, P, _i, P]),
+    "md_probe_stream_copy": (_i, [P, P, C.c_size_t, P]),
+    "md_lidar": (_i, [_W, _S, _K, P, _i, _i, P]),
+    "md_lidar_detect": (_i, [_W, _S, _K, P, _i, _i, P, P]),
+    "md_line_detector": (_i, [_W, _S, _K, P, _i, _f, _u, P, _i, _i, P]),
+    "md_line_detectors": (_i, [_W, _S, _K, P, _i, _f, _u, _i, P, _i, _f, _u, _i, P, _i, P]),
+    "md_swap_draw": (_i, [_S, _S, _K, _i, P, P]),
+    "md_integrate": _PHASE, "md_localize": _PHASE, "md_contacts": _PHASE, "md_observe": _PHASE, "md_idm": _PHASE,
+    "md_traffic_after_step": _PHASE, "md_lifecycle": _PHASE, "md_step": _PHASE,
+}
+# include/md_expert.h
+EXPERT_ENTRY_POINTS = {"md_expert": (_i, [_W, _S, _K, P, P, P, P, P, P])}
+# exported by diagnostic (-DMD_STAMP) builds only
+OPTIONAL_ENTRY_POINTS = {"md_debug_set_stamp_buffer": (_i, [P]), "md_debug_set_env_order": (_i, [P])}
 
 
 def check_abi(abi_fn, what):

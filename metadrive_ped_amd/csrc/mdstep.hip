@@ -23,6 +23,7 @@
 // MLP, include/md_expert.h), which runs on v_mfma_f32_16x16x4_f32.  The arithmetic formulas are the shared
 // include/md_geom.h / md_entity.h ones (bit-exact vs the CPU oracle, -ffp-contract=off).
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -3563,15 +3564,26 @@ __global__ void probe_kernel(int op, const float* a, const float* b, float* out,
     if (i < n) out[i] = md_probe_eval(op, a[i], b[i]);
 }
 
+// return from the calling entry point unless x is MD_OK
+#define TRY(x)                       \
+    do {                             \
+        const int _r = (x);          \
+        if (_r != MD_OK) return _r;  \
+    } while (0)
+#define NEED(p) TRY(need((const void*)(p), #p))
+
+int check_struct_size(const MdConfig* c) {
+    if (c->struct_size == (int32_t)sizeof(MdConfig)) return MD_OK;
+    snprintf(g_err, sizeof g_err, "MdConfig.struct_size=%d, library expects %d", c->struct_size, (int)sizeof(MdConfig));
+    return MD_EABI;
+}
+
 int check_common(const MdWorld* w, const MdState* s, const MdConfig* c) {
     if (!w || !s || !c) {
         snprintf(g_err, sizeof g_err, "null MdWorld/MdState/MdConfig pointer");
         return MD_EINVAL;
     }
-    if (c->struct_size != (int32_t)sizeof(MdConfig)) {
-        snprintf(g_err, sizeof g_err, "MdConfig.struct_size=%d, library expects %d", c->struct_size, (int)sizeof(MdConfig));
-        return MD_EABI;
-    }
+    TRY(check_struct_size(c));
     if (c->n_envs <= 0 || c->cap <= 0 || c->cap > MD_MAX_CAP || c->agents_per_env <= 0 || c->agents_per_env > c->cap) {
         snprintf(g_err, sizeof g_err, "bad sizes: n_envs=%d cap=%d agents_per_env=%d (cap<=%d)", c->n_envs, c->cap,
                  c->agents_per_env, MD_MAX_CAP);
@@ -3598,6 +3610,108 @@ int need(const void* p, const char* name) {
     return MD_EINVAL;
 }
 
+// ---- the MdWorld / MdState pointers each entry point requires ----
+// A row: the entry points that require its fields (their PH_* bits: PH_RESET is md_step's alone; the k*Entry bits stand for
+// the entry points that run no phase), the condition under which they do, and the fields.  An entry point checks the rows of
+// a few conditions at a time (need_fields), each group where its code has validated what the condition reads; within a
+// group, table order is check order, so the first null field is the one the message names.
+enum When : unsigned {
+    ALWAYS = 1, LIDAR_ON = 2, MULTI = 4, RESPAWN = 8,   // check_phase, before anything but check_common
+    REPLAY = 16, SPAWN_TRAFFIC = 32,                     // check_phase, after traffic_mode is validated
+    SCENARIO = 64, ROUTE = 128, OTHERS = 256,            // md_step, each after the config checks of its branch
+};
+constexpr int kLidarEntry = 1 << 9, kDetectorEntry = 1 << 10, kExpertEntry = 1 << 11;
+constexpr int kMapPhases = PH_LOCALIZE | PH_CONTACTS | PH_OBSERVE | PH_IDM | PH_LIFECYCLE;
+constexpr int kTrafficPhases = PH_INTEGRATE | PH_TRAFFIC;
+
+struct Field { const char* name; bool world; size_t off; };   // "w->x" / "s->x" as the message spells it, MdWorld?, offset
+#define FW(f) Field{"w->" #f, true, offsetof(MdWorld, f)}
+#define FS(f) Field{"s->" #f, false, offsetof(MdState, f)}
+#define MAP_FIELDS FW(env_map), FW(lane_off), FW(lanes), FW(hull_xy), FW(road_off), FW(roads), FW(quad_off), FW(quads), \
+                   FW(quad_kind), FW(grid), FW(cell_start), FW(cell_items)
+struct Need { int entries; When when; Field fields[12]; };   // fields: up to 12, the unused tail has name == nullptr
+const Need kNeeds[] = {
+    {PH_ALL, ALWAYS, {FS(dyn), FS(param), FS(nav), FS(pid), FS(action), FS(flags), FS(route_nodes), FS(route_roads), FS(need_reset)}},
+    {kMapPhases, ALWAYS, {MAP_FIELDS}},
+    {PH_OBSERVE, ALWAYS, {FS(final_lane)}},
+    {PH_IDM, ALWAYS, {FS(idm_rand)}},
+    {PH_OBSERVE, ALWAYS, {FS(obs), FS(reward), FS(cost), FS(step_info)}},
+    {PH_IDM, ALWAYS, {FW(node_adj_off), FW(node_adj), FW(node_off)}},
+    {PH_RESET, LIDAR_ON, {FW(beam_cs)}},
+    {PH_RESET, ALWAYS, {FS(shape0), FS(dyn0), FS(nav0), FS(pid0)}},
+    {PH_LIFECYCLE, MULTI, {FS(rng), FS(env_steps), FS(agent_id), FS(next_agent_id), FS(route_nodes0), FS(route_roads0), FS(final_lane0),
+                           FS(final_lane)}},
+    {PH_LIFECYCLE, RESPAWN, {FW(spawn_off), FW(spawn_place), FW(spawn_lane), FW(spawn_route), FW(spawn_route_meta)}},
+    {kTrafficPhases, REPLAY, {FS(track_shape), FS(track_dyn)}},
+    {kTrafficPhases, SPAWN_TRAFFIC, {MAP_FIELDS}},
+    {kTrafficPhases, SPAWN_TRAFFIC, {FS(rng), FS(route_nodes0), FS(route_roads0), FS(final_lane0), FS(final_lane), FW(spawn_off),
+                                     FW(spawn_lane), FW(spawn_route), FW(spawn_route_meta)}},
+    {PH_RESET, SCENARIO, {FW(poly_off), FW(segs), FW(polyv_off), FW(polyv), FW(ckpt_off), FW(ckpt_xy), FW(track_meta), FS(track_shape),
+                          FS(track_dyn), FS(next_agent_id)}},
+    {PH_RESET, ROUTE, {FS(route_segs), FS(route_verts), FS(route_aux), FW(run_off), FW(runs)}},
+    {PH_RESET, OTHERS, {FS(detected)}},
+    {kLidarEntry, ALWAYS, {FW(beam_cs)}},
+    {kDetectorEntry, ALWAYS, {FW(env_map), FW(quad_off), FW(quads), FW(quad_kind)}},
+    {kExpertEntry, ALWAYS, {FS(obs), FS(detected), FS(dyn), FS(param), FS(nav), FW(env_map), FW(lanes), FW(lane_off), FW(roads),
+                            FW(road_off)}},
+};
+#undef FW
+#undef FS
+#undef MAP_FIELDS
+
+bool holds(When when, const MdState* s, const MdConfig* c) {
+    switch (when) {
+    case ALWAYS: return true;
+    case LIDAR_ON: return c->n_beams > 0;
+    case MULTI: return c->is_multi_agent;
+    case RESPAWN: return c->is_multi_agent && c->allow_respawn;
+    case REPLAY: return c->traffic_mode == 3;
+    case SPAWN_TRAFFIC: return c->traffic_mode == 1 || c->traffic_mode == 2;   // respawn / hybrid
+    case SCENARIO: return c->traffic_mode == 4;
+    case ROUTE: return c->traffic_mode == 4 && s->route_n;
+    case OTHERS: return c->num_others > 0;
+    }
+    return false;
+}
+
+// MD_OK, or MD_EINVAL naming the first null field that `entry` requires under the conditions `whens`
+int need_fields(int entry, unsigned whens, const MdWorld* w, const MdState* s, const MdConfig* c) {
+    for (const Need& n : kNeeds) {
+        if (!(n.entries & entry) || !(n.when & whens) || !holds(n.when, s, c)) continue;
+        for (const Field& f : n.fields) {
+            if (f.name && !*(void* const*)((const char*)(f.world ? (const void*)w : (const void*)s) + f.off)) return need(nullptr, f.name);
+        }
+    }
+    return MD_OK;
+}
+
+// what the eight phase entry points check before they launch (md_step goes on checking)
+int check_phase(int ph, const MdWorld* w, const MdState* s, const MdConfig* c) {
+    TRY(check_common(w, s, c));
+    TRY(need_fields(ph, ALWAYS | LIDAR_ON | MULTI | RESPAWN, w, s, c));
+    if ((ph & PH_LIFECYCLE) && c->is_multi_agent && c->allow_respawn && w->n_dest <= 0) {
+        snprintf(g_err, sizeof g_err, "multi-agent respawn needs MdWorld.n_dest > 0");
+        return MD_EINVAL;
+    }
+    // traffic_mode 4 (scenario) is validated by md_step itself
+    const int tm = c->traffic_mode;
+    if ((ph & kTrafficPhases) && tm != 0 && tm != 4 && (tm < 0 || tm > 3 || c->is_multi_agent)) {
+        snprintf(g_err, sizeof g_err, "traffic_mode=%d is not valid here (0 trigger, 1 respawn, 2 hybrid, 3 replay; "
+                 "single-agent envs)", tm);
+        return MD_EINVAL;
+    }
+    TRY(need_fields(ph, REPLAY | SPAWN_TRAFFIC, w, s, c));
+    if ((ph & kTrafficPhases) && tm == 3 && c->track_len <= 0) {
+        snprintf(g_err, sizeof g_err, "traffic_mode 3 (replay) needs MdConfig.track_len > 0");
+        return MD_EINVAL;
+    }
+    if (ph == PH_OBSERVE && c->obs_dim < md_obs_lidar(c)) {
+        snprintf(g_err, sizeof g_err, "obs_dim=%d < %d", c->obs_dim, md_obs_lidar(c));
+        return MD_EINVAL;
+    }
+    return MD_OK;
+}
+
 // after a hipLaunchKernelGGL: MD_OK, or MD_ELAUNCH with the HIP error in g_err
 int launch_status() {
     const hipError_t err = hipGetLastError();
@@ -3606,116 +3720,71 @@ int launch_status() {
     return MD_ELAUNCH;
 }
 
-// md_step of the single-agent envs has two kernels: env_kernel (one 4-wave workgroup per env) and wave_step_kernel (one
-// wave per env), chosen by MdConfig.step_kernel alone (0 = workgroup, 1 = wave): the host decides -- it knows how many
-// distinct maps the batch shares, which is what tips the balance (metadrive_ped_amd/engine.py) -- and the library reads no
-// environment variable.
-bool use_wave_kernel(const MdConfig* c) { return !c->is_multi_agent && c->step_kernel == 1; }
-
-int launch_wave_step(const MdWorld* w, const MdState* s, const MdConfig* c, float* lidar_out, int stride, int offset,
-                     void* stream) {
-    const size_t per_env = wave_env_lds(c->cap, c->agents_per_env).bytes;
-    int per_wg = kWaveEnvs;   // envs per workgroup: as many as fit 64 KB of LDS (capacity-128 accident scenes: 2)
-    while (per_wg > 1 && per_wg * per_env > 64 * 1024) per_wg >>= 1;
-    const size_t lds = per_wg * per_env;
-    if (lds > 64 * 1024) {
-        snprintf(g_err, sizeof g_err, "LDS image of one env needs %zu B (cap=%d); limit 65536", lds, c->cap);
-        return MD_EINVAL;
-    }
-    const dim3 grid((c->n_envs + per_wg - 1) / per_wg);
-    const hipStream_t st = (hipStream_t)stream;
-    const bool general = c->traffic_mode != 0 || c->agent_idm != 0 || s->detected != nullptr;
-    if (general) hipLaunchKernelGGL((wave_step_kernel<true>), grid, dim3(64 * per_wg), lds, st, *w, *s, *c, lidar_out, stride, offset);
-    else hipLaunchKernelGGL((wave_step_kernel<false>), grid, dim3(64 * per_wg), lds, st, *w, *s, *c, lidar_out, stride, offset);
-    return launch_status();
-}
+// The kernel a phase launches.  md_step of the single-agent envs has two: env_kernel (one 4-wave workgroup per env) and
+// wave_step_kernel (one wave per env), chosen by MdConfig.step_kernel alone (0 = workgroup, 1 = wave): the host decides -- it
+// knows how many distinct maps the batch shares, which is what tips the balance (metadrive_ped_amd/engine.py) -- and the
+// library reads no environment variable.  The wave kernel is wave_step_kernel<respawn>; the workgroup kernel is
+// env_kernel<PH, stage, respawn, multi>, or <PH_ALL, stage, false, true, 512> when wide.
+struct Variant {
+    bool wave, stage, respawn, multi, wide;
+};
 
 template <int PH>
-int launch(const MdWorld* w, const MdState* s, const MdConfig* c, float* lidar_out, int stride, int offset,
-           void* stream) {
-    if (PH == PH_ALL && use_wave_kernel(c)) return launch_wave_step(w, s, c, lidar_out, stride, offset, stream);
-    const bool stage = w->max_lanes <= kStageMaxLanes;
-    constexpr bool kCanRespawn = (PH & (PH_TRAFFIC | PH_RESET | PH_INTEGRATE)) != 0;
-    constexpr bool kCanMulti = (PH & (PH_LIFECYCLE | PH_RESET)) != 0;
+Variant variant(const MdWorld* w, const MdState* s, const MdConfig* c) {
+    Variant v;
+    v.wave = PH == PH_ALL && !c->is_multi_agent && c->step_kernel == 1;
+    v.stage = w->max_lanes <= kStageMaxLanes;
+    v.multi = (PH & (PH_LIFECYCLE | PH_RESET)) && c->is_multi_agent;
+    v.respawn = !v.multi && (PH & (PH_TRAFFIC | PH_RESET | PH_INTEGRATE)) &&
+                (c->traffic_mode != 0 || c->agent_idm != 0 || (PH == PH_ALL && s->detected != nullptr));
     // Multi-agent md_step: eight waves per env while every workgroup of the batch is resident at once at that size (the MULTI
     // kernel's 92 VGPRs allow 5 waves per SIMD = 640 eight-wave workgroups on the 256 CUs); larger batches keep four, which
     // then fill the chip by themselves.  Measured: 512 tollgate envs x 40 agents, 1024 roundabout envs (profiles/r03_*).
-    const bool wide = (PH == PH_ALL) && kCanMulti && c->is_multi_agent && c->n_envs <= kWideMaxEnvs && MD_ENV_BLOCK == 256 &&
-                      c->agents_per_env > 8;
-    const int blk = wide ? 512 : MD_ENV_BLOCK;
-    const size_t lds = env_lds(c->cap, c->agents_per_env, stage ? w->max_lanes : 0, stage ? w->max_roads : 0, blk / 64,
-                               kCanMulti && c->is_multi_agent, PH == PH_LIDAR).bytes;
+    v.wide = PH == PH_ALL && v.multi && c->n_envs <= kWideMaxEnvs && MD_ENV_BLOCK == 256 && c->agents_per_env > 8;
+    return v;
+}
+
+template <int PH, bool RESPAWN, bool MULTI, int BLK = MD_ENV_BLOCK>
+void launch_env(bool stage, size_t lds, hipStream_t st, const MdWorld* w, const MdState* s, const MdConfig* c, float* lidar_out,
+                int stride, int offset) {
+    if (stage) hipLaunchKernelGGL((env_kernel<PH, true, RESPAWN, MULTI, BLK>), dim3(c->n_envs), dim3(BLK), lds, st, *w, *s, *c, lidar_out, stride, offset);
+    else hipLaunchKernelGGL((env_kernel<PH, false, RESPAWN, MULTI, BLK>), dim3(c->n_envs), dim3(BLK), lds, st, *w, *s, *c, lidar_out, stride, offset);
+}
+
+template <int PH>
+int launch(const MdWorld* w, const MdState* s, const MdConfig* c, float* lidar_out, int stride, int offset, void* stream) {
+    const Variant v = variant<PH>(w, s, c);
+    const hipStream_t st = (hipStream_t)stream;
+    if (v.wave) {
+        const size_t per_env = wave_env_lds(c->cap, c->agents_per_env).bytes;
+        int per_wg = kWaveEnvs;   // envs per workgroup: as many as fit 64 KB of LDS (capacity-128 accident scenes: 2)
+        while (per_wg > 1 && per_wg * per_env > 64 * 1024) per_wg >>= 1;
+        const size_t lds = per_wg * per_env;
+        if (lds > 64 * 1024) {
+            snprintf(g_err, sizeof g_err, "LDS image of one env needs %zu B (cap=%d); limit 65536", lds, c->cap);
+            return MD_EINVAL;
+        }
+        const dim3 grid((c->n_envs + per_wg - 1) / per_wg), block(64 * per_wg);
+        if (v.respawn) hipLaunchKernelGGL((wave_step_kernel<true>), grid, block, lds, st, *w, *s, *c, lidar_out, stride, offset);
+        else hipLaunchKernelGGL((wave_step_kernel<false>), grid, block, lds, st, *w, *s, *c, lidar_out, stride, offset);
+        return launch_status();
+    }
+    const size_t lds = env_lds(c->cap, c->agents_per_env, v.stage ? w->max_lanes : 0, v.stage ? w->max_roads : 0,
+                               (v.wide ? 512 : MD_ENV_BLOCK) / 64, v.multi, PH == PH_LIDAR).bytes;
     if (lds > 64 * 1024 || ((PH != PH_LIDAR) && (w->max_lanes <= 0 || w->max_roads <= 0))) {
         snprintf(g_err, sizeof g_err, "LDS image of one env needs %zu B (cap=%d, max_lanes=%d, max_roads=%d); limit 65536",
                  lds, c->cap, w->max_lanes, w->max_roads);
         return MD_EINVAL;
     }
-    const dim3 grid(c->n_envs);
-    const hipStream_t st = (hipStream_t)stream;
-#define MD_LAUNCH(STAGE, RESP, MUL) \
-    hipLaunchKernelGGL((env_kernel<PH, STAGE, RESP, MUL>), grid, dim3(MD_ENV_BLOCK), lds, st, *w, *s, *c, lidar_out, stride, offset)
-#define MD_LAUNCH_WIDE(STAGE) \
-    hipLaunchKernelGGL((env_kernel<PH, STAGE, false, kCanMulti && PH == PH_ALL, (PH == PH_ALL ? 512 : MD_ENV_BLOCK)>), grid, dim3(512), lds, st, *w, *s, *c, lidar_out, stride, offset)
-    if (kCanMulti && c->is_multi_agent && wide) {
-        if (stage) MD_LAUNCH_WIDE(true);
-        else MD_LAUNCH_WIDE(false);
-    } else if (kCanMulti && c->is_multi_agent) {
-        if (stage) MD_LAUNCH(true, false, kCanMulti);
-        else MD_LAUNCH(false, false, kCanMulti);
-    } else if (kCanRespawn && (c->traffic_mode != 0 || c->agent_idm != 0 || (PH == PH_ALL && s->detected != nullptr))) {
-        if (stage) MD_LAUNCH(true, kCanRespawn, false);
-        else MD_LAUNCH(false, kCanRespawn, false);
-    } else if (stage) {
-        MD_LAUNCH(true, false, false);
-    } else {
-        MD_LAUNCH(false, false, false);
-    }
-#undef MD_LAUNCH
-#undef MD_LAUNCH_WIDE
+    // the instantiations: PH_ALL all four; the phases that can be multi-agent or respawn two; the others one (per stage)
+    constexpr bool kAll = PH == PH_ALL, kMulti = (PH & (PH_LIFECYCLE | PH_RESET)) != 0;
+    constexpr bool kRespawn = (PH & (PH_TRAFFIC | PH_RESET | PH_INTEGRATE)) != 0;
+    if (v.wide) launch_env<PH, false, kAll, kAll ? 512 : MD_ENV_BLOCK>(v.stage, lds, st, w, s, c, lidar_out, stride, offset);
+    else if (v.multi) launch_env<PH, false, kMulti>(v.stage, lds, st, w, s, c, lidar_out, stride, offset);
+    else if (v.respawn) launch_env<PH, kRespawn, false>(v.stage, lds, st, w, s, c, lidar_out, stride, offset);
+    else launch_env<PH, false, false>(v.stage, lds, st, w, s, c, lidar_out, stride, offset);
     return launch_status();
 }
-
-#define NEED(p)                                  \
-    do {                                         \
-        int _r = need((const void*)(p), #p);     \
-        if (_r != MD_OK) return _r;              \
-    } while (0)
-
-int check_state(const MdState* s) {
-    NEED(s->shape); NEED(s->dyn); NEED(s->param); NEED(s->nav); NEED(s->pid); NEED(s->action); NEED(s->flags);
-    NEED(s->route_nodes); NEED(s->route_roads); NEED(s->need_reset);
-    return MD_OK;
-}
-
-int check_world(const MdWorld* w) {
-    NEED(w->env_map); NEED(w->lane_off); NEED(w->lanes); NEED(w->hull_xy); NEED(w->road_off); NEED(w->roads);
-    NEED(w->quad_off); NEED(w->quads); NEED(w->quad_kind); NEED(w->grid); NEED(w->cell_start); NEED(w->cell_items);
-    return MD_OK;
-}
-
-// traffic_mode respawn / hybrid: the respawn-lane tables, the env RNG and the route snapshot must be there
-int check_traffic_mode(const MdWorld* w, const MdState* s, const MdConfig* c) {
-    if (c->traffic_mode == 0 || c->traffic_mode == 4) return MD_OK;   // 4 (scenario): validated by md_step itself
-    if (c->traffic_mode < 0 || c->traffic_mode > 3 || c->is_multi_agent) {
-        snprintf(g_err, sizeof g_err, "traffic_mode=%d is not valid here (0 trigger, 1 respawn, 2 hybrid, 3 replay; "
-                 "single-agent envs)", c->traffic_mode);
-        return MD_EINVAL;
-    }
-    if (c->traffic_mode == 3) {
-        NEED(s->track_shape); NEED(s->track_dyn); NEED(s->nav);
-        if (c->track_len <= 0) {
-            snprintf(g_err, sizeof g_err, "traffic_mode 3 (replay) needs MdConfig.track_len > 0");
-            return MD_EINVAL;
-        }
-        return MD_OK;
-    }
-    int r = check_world(w);
-    if (r != MD_OK) return r;
-    NEED(s->rng); NEED(s->route_nodes0); NEED(s->route_roads0); NEED(s->final_lane0); NEED(s->final_lane);
-    NEED(w->spawn_off); NEED(w->spawn_lane); NEED(w->spawn_route); NEED(w->spawn_route_meta);
-    return MD_OK;
-}
-
 
 }  // namespace
 
@@ -3788,9 +3857,9 @@ __attribute__((visibility("default"))) int md_probe_math(int op, const float* a,
 
 __attribute__((visibility("default"))) int md_lidar(const MdWorld* w, const MdState* s, const MdConfig* c, float* out,
                                                    int out_stride, int out_offset, void* stream) {
-    int r = check_common(w, s, c);
-    if (r != MD_OK) return r;
-    NEED(out); NEED(w->beam_cs);
+    TRY(check_common(w, s, c));
+    NEED(out);
+    TRY(need_fields(kLidarEntry, ALWAYS, w, s, c));
     if (c->n_beams <= 0 || out_stride < c->n_beams + out_offset || out_offset < 0) {
         snprintf(g_err, sizeof g_err, "md_lidar: n_beams=%d stride=%d offset=%d", c->n_beams, out_stride, out_offset);
         return MD_EINVAL;
@@ -3800,9 +3869,9 @@ __attribute__((visibility("default"))) int md_lidar(const MdWorld* w, const MdSt
 
 __attribute__((visibility("default"))) int md_lidar_detect(const MdWorld* w, const MdState* s, const MdConfig* c, float* out,
                                                           int out_stride, int out_offset, uint64_t* detected, void* stream) {
-    int r = check_common(w, s, c);
-    if (r != MD_OK) return r;
-    NEED(out); NEED(detected); NEED(w->beam_cs);
+    TRY(check_common(w, s, c));
+    NEED(out); NEED(detected);
+    TRY(need_fields(kLidarEntry, ALWAYS, w, s, c));
     if (c->n_beams <= 0 || out_stride < c->n_beams + out_offset || out_offset < 0) {
         snprintf(g_err, sizeof g_err, "md_lidar_detect: n_beams=%d stride=%d offset=%d", c->n_beams, out_stride, out_offset);
         return MD_EINVAL;
@@ -3815,9 +3884,9 @@ __attribute__((visibility("default"))) int md_lidar_detect(const MdWorld* w, con
 static int line_detector_launch(const MdWorld* w, const MdState* s, const MdConfig* c, const float* beam_cs, int n_beams, float range,
                                 uint32_t kind_mask, int out_offset, const float* beam_cs1, int n_beams1, float range1, uint32_t kind_mask1,
                                 int out_offset1, float* out, int out_stride, void* stream, const char* who) {
-    int r = check_common(w, s, c);
-    if (r != MD_OK) return r;
-    NEED(out); NEED(beam_cs); NEED(w->env_map); NEED(w->quad_off); NEED(w->quads); NEED(w->quad_kind);
+    TRY(check_common(w, s, c));
+    NEED(out); NEED(beam_cs);
+    TRY(need_fields(kDetectorEntry, ALWAYS, w, s, c));
     if (n_beams <= 0 || n_beams > MD_MAX_BEAMS || out_stride < n_beams + out_offset || out_offset < 0 || !(range > 0.0f) ||
         (n_beams1 > 0 && (!beam_cs1 || out_stride < n_beams1 + out_offset1 || out_offset1 < 0 || !(range1 > 0.0f)))) {
         snprintf(g_err, sizeof g_err, "%s: n_beams=%d/%d stride=%d offset=%d/%d range=%f/%f", who, n_beams, n_beams1, out_stride, out_offset,
@@ -3850,10 +3919,7 @@ __attribute__((visibility("default"))) int md_swap_draw(const MdState* s, const 
         snprintf(g_err, sizeof g_err, "md_swap_draw: null MdState / staged MdState / MdConfig / draw_idx");
         return MD_EINVAL;
     }
-    if (c->struct_size != (int32_t)sizeof(MdConfig)) {
-        snprintf(g_err, sizeof g_err, "MdConfig.struct_size=%d, library expects %d", c->struct_size, (int)sizeof(MdConfig));
-        return MD_EABI;
-    }
+    TRY(check_struct_size(c));
     if (n_draws < 1 || c->n_envs <= 0 || c->cap <= 0 || c->cap > MD_MAX_CAP) {
         snprintf(g_err, sizeof g_err, "md_swap_draw: n_draws=%d n_envs=%d cap=%d", n_draws, c->n_envs, c->cap);
         return MD_EINVAL;
@@ -3875,128 +3941,25 @@ __attribute__((visibility("default"))) int md_line_detectors(const MdWorld* w, c
                                 out_offset1, out, out_stride, stream, "md_line_detectors");
 }
 
-__attribute__((visibility("default"))) int md_integrate(const MdWorld* w, const MdState* s, const MdConfig* c,
-                                                       void* stream) {
-    int r = check_common(w, s, c);
-    if (r != MD_OK) return r;
-    r = check_state(s);
-    if (r != MD_OK) return r;
-    NEED(s->dyn); NEED(s->param); NEED(s->action);
-    r = check_traffic_mode(w, s, c);
-    if (r != MD_OK) return r;
-    return launch<PH_INTEGRATE>(w, s, c, nullptr, 0, 0, stream);
-}
-
-__attribute__((visibility("default"))) int md_localize(const MdWorld* w, const MdState* s, const MdConfig* c,
-                                                      void* stream) {
-    int r = check_common(w, s, c);
-    if (r != MD_OK) return r;
-    r = check_state(s);
-    if (r != MD_OK) return r;
-    r = check_world(w);
-    if (r != MD_OK) return r;
-    NEED(s->nav); NEED(s->flags); NEED(s->route_nodes); NEED(s->route_roads);
-    return launch<PH_LOCALIZE>(w, s, c, nullptr, 0, 0, stream);
-}
-
-__attribute__((visibility("default"))) int md_contacts(const MdWorld* w, const MdState* s, const MdConfig* c,
-                                                      void* stream) {
-    int r = check_common(w, s, c);
-    if (r != MD_OK) return r;
-    r = check_state(s);
-    if (r != MD_OK) return r;
-    r = check_world(w);
-    if (r != MD_OK) return r;
-    NEED(s->flags);
-    return launch<PH_CONTACTS>(w, s, c, nullptr, 0, 0, stream);
-}
-
-__attribute__((visibility("default"))) int md_observe(const MdWorld* w, const MdState* s, const MdConfig* c,
-                                                     void* stream) {
-    int r = check_common(w, s, c);
-    if (r != MD_OK) return r;
-    r = check_state(s);
-    if (r != MD_OK) return r;
-    r = check_world(w);
-    if (r != MD_OK) return r;
-    NEED(s->dyn); NEED(s->param); NEED(s->nav); NEED(s->pid); NEED(s->action); NEED(s->route_roads); NEED(s->final_lane);
-    NEED(s->flags); NEED(s->obs); NEED(s->reward); NEED(s->cost); NEED(s->step_info); NEED(s->need_reset);
-    if (c->obs_dim < md_obs_lidar(c)) {
-        snprintf(g_err, sizeof g_err, "obs_dim=%d < %d", c->obs_dim, md_obs_lidar(c));
-        return MD_EINVAL;
+// the eight phase entry points: check_phase, then launch<PH>
+#define MD_PHASE_ENTRY(name, PH)                                                                                          \
+    __attribute__((visibility("default"))) int name(const MdWorld* w, const MdState* s, const MdConfig* c, void* stream) { \
+        TRY(check_phase(PH, w, s, c));                                                                                    \
+        return launch<PH>(w, s, c, nullptr, 0, 0, stream);                                                                \
     }
-    return launch<PH_OBSERVE>(w, s, c, nullptr, 0, 0, stream);
-}
-
-__attribute__((visibility("default"))) int md_idm(const MdWorld* w, const MdState* s, const MdConfig* c, void* stream) {
-    int r = check_common(w, s, c);
-    if (r != MD_OK) return r;
-    r = check_state(s);
-    if (r != MD_OK) return r;
-    r = check_world(w);
-    if (r != MD_OK) return r;
-    NEED(s->dyn); NEED(s->nav); NEED(s->pid); NEED(s->action); NEED(s->route_roads); NEED(s->idm_rand);
-    NEED(w->node_adj_off); NEED(w->node_adj); NEED(w->node_off);
-    return launch<PH_IDM>(w, s, c, nullptr, 0, 0, stream);
-}
-
-__attribute__((visibility("default"))) int md_traffic_after_step(const MdWorld* w, const MdState* s, const MdConfig* c,
-                                                                void* stream) {
-    int r = check_common(w, s, c);
-    if (r != MD_OK) return r;
-    r = check_state(s);
-    if (r != MD_OK) return r;
-    NEED(s->flags);
-    r = check_traffic_mode(w, s, c);
-    if (r != MD_OK) return r;
-    return launch<PH_TRAFFIC>(w, s, c, nullptr, 0, 0, stream);
-}
-
-int check_marl(const MdWorld* w, const MdState* s, const MdConfig* c) {
-    if (!c->is_multi_agent) return MD_OK;
-    NEED(s->rng); NEED(s->env_steps); NEED(s->agent_id); NEED(s->next_agent_id); NEED(s->route_nodes0);
-    NEED(s->route_roads0); NEED(s->final_lane0); NEED(s->final_lane);
-    if (c->allow_respawn) {
-        NEED(w->spawn_off); NEED(w->spawn_place); NEED(w->spawn_lane); NEED(w->spawn_route); NEED(w->spawn_route_meta);
-        if (w->n_dest <= 0) {
-            snprintf(g_err, sizeof g_err, "multi-agent respawn needs MdWorld.n_dest > 0");
-            return MD_EINVAL;
-        }
-    }
-    return MD_OK;
-}
-
-__attribute__((visibility("default"))) int md_lifecycle(const MdWorld* w, const MdState* s, const MdConfig* c, void* stream) {
-    int r = check_common(w, s, c);
-    if (r != MD_OK) return r;
-    r = check_state(s);
-    if (r != MD_OK) return r;
-    r = check_world(w);
-    if (r != MD_OK) return r;
-    r = check_marl(w, s, c);
-    if (r != MD_OK) return r;
-    return launch<PH_LIFECYCLE>(w, s, c, nullptr, 0, 0, stream);
-}
+MD_PHASE_ENTRY(md_integrate, PH_INTEGRATE)
+MD_PHASE_ENTRY(md_localize, PH_LOCALIZE)
+MD_PHASE_ENTRY(md_contacts, PH_CONTACTS)
+MD_PHASE_ENTRY(md_observe, PH_OBSERVE)
+MD_PHASE_ENTRY(md_idm, PH_IDM)
+MD_PHASE_ENTRY(md_traffic_after_step, PH_TRAFFIC)
+MD_PHASE_ENTRY(md_lifecycle, PH_LIFECYCLE)
+#undef MD_PHASE_ENTRY
 
 __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdState* s, const MdConfig* c, void* stream) {
-    int r = check_common(w, s, c);
-    if (r != MD_OK) return r;
-    r = check_state(s);
-    if (r != MD_OK) return r;
-    r = check_world(w);
-    if (r != MD_OK) return r;
-    NEED(s->dyn); NEED(s->param); NEED(s->nav); NEED(s->pid); NEED(s->action); NEED(s->route_nodes); NEED(s->route_roads);
-    NEED(s->final_lane); NEED(s->idm_rand); NEED(s->flags); NEED(s->obs); NEED(s->reward); NEED(s->cost);
-    NEED(s->step_info); NEED(s->need_reset); NEED(w->node_adj_off); NEED(w->node_adj); NEED(w->node_off);
-    if (c->n_beams > 0) NEED(w->beam_cs);
-    NEED(s->shape0); NEED(s->dyn0); NEED(s->nav0); NEED(s->pid0);
-    r = check_marl(w, s, c);
-    if (r != MD_OK) return r;
-    r = check_traffic_mode(w, s, c);
-    if (r != MD_OK) return r;
+    TRY(check_phase(PH_ALL, w, s, c));
     if (c->traffic_mode == 4) {   // scenario mode: its own kernel (ScenarioEnv step)
-        NEED(w->poly_off); NEED(w->segs); NEED(w->polyv_off); NEED(w->polyv); NEED(w->ckpt_off); NEED(w->ckpt_xy);
-        NEED(w->track_meta); NEED(s->track_shape); NEED(s->track_dyn); NEED(s->next_agent_id);
+        TRY(need_fields(PH_ALL, SCENARIO, w, s, c));
         if (c->is_multi_agent || c->agents_per_env != 1 || c->track_len <= 0) {
             snprintf(g_err, sizeof g_err, "scenario mode: single-agent scenes with track_len > 0 (got agents=%d track_len=%d)",
                      c->agents_per_env, c->track_len);
@@ -4009,7 +3972,7 @@ __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdSta
         }
         const size_t lds = scenario_lds(c->cap, c->agents_per_env, c->n_side + c->n_lane_line, s->route_n != nullptr, c->route_seg_cap).bytes;
         if (s->route_n) {
-            NEED(s->route_segs); NEED(s->route_verts); NEED(s->route_aux); NEED(w->run_off); NEED(w->runs);
+            TRY(need_fields(PH_ALL, ROUTE, w, s, c));
             if (c->route_seg_cap < 1 || c->route_vert_cap < 8) {
                 snprintf(g_err, sizeof g_err, "scenario mode: route buffers need route_seg_cap >= 1 and route_vert_cap >= 8 (got %d, %d)",
                          c->route_seg_cap, c->route_vert_cap);
@@ -4037,8 +4000,8 @@ __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdSta
         snprintf(g_err, sizeof g_err, "num_others=%d needs 0..16 and the lidar on", c->num_others);
         return MD_EINVAL;
     }
-    if (c->num_others > 0) NEED(s->detected);
-    r = launch<PH_ALL>(w, s, c, s->obs, c->obs_dim, md_obs_lidar(c), stream);
+    TRY(need_fields(PH_ALL, OTHERS, w, s, c));
+    const int r = launch<PH_ALL>(w, s, c, s->obs, c->obs_dim, md_obs_lidar(c), stream);
     if (r != MD_OK || c->num_others <= 0) return r;
     const int n = c->n_envs * c->agents_per_env;
     hipLaunchKernelGGL(others_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, *w, *s, *c);
@@ -4048,10 +4011,9 @@ __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdSta
 __attribute__((visibility("default"))) int md_expert(const MdWorld* w, const MdState* s, const MdConfig* c, const float* weights,
                                                     const float* noise, float* action_out, float* mlp_out, float* obs_out,
                                                     void* stream) {
-    int r = check_common(w, s, c);
-    if (r != MD_OK) return r;
-    NEED(weights); NEED(action_out); NEED(s->obs); NEED(s->detected); NEED(s->dyn); NEED(s->param); NEED(s->nav);
-    NEED(w->env_map); NEED(w->lanes); NEED(w->lane_off); NEED(w->roads); NEED(w->road_off);
+    TRY(check_common(w, s, c));
+    NEED(weights); NEED(action_out);
+    TRY(need_fields(kExpertEntry, ALWAYS, w, s, c));
     // the configs where the reference's rewrite of the vehicle config (numpy_expert.py:58-62) changes nothing
     if (c->is_multi_agent || c->agents_per_env != 1 || c->traffic_mode == 4 || c->n_beams != 240 || c->lidar_range != 50.0f ||
         c->num_others != 0 || c->n_side != 0 || c->n_lane_line != 0 || c->random_agent_model != 0 ||

@@ -1,5 +1,5 @@
-"""The C-ABI library builds for gfx950, loads without a GPU, exports every symbol include/mdstep.h
-declares, and agrees with the Python binding on every struct size.  No compute calls here."""
+"""The C-ABI library builds for gfx950, loads without a GPU, exports every symbol include/mdstep.h and
+include/md_expert.h declare, and agrees with the Python binding on every struct size.  No compute calls here."""
 import ctypes as C
 import os
 import re
@@ -24,10 +24,16 @@ def declared_symbols():
 
 
 def test_header_symbols_exported(lib):
+    """abi.ENTRY_POINTS names every function include/mdstep.h declares and abi.EXPERT_ENTRY_POINTS those of
+    include/md_expert.h, with the same number of arguments; the library exports each."""
     from metadrive_ped_amd import abi
+    from abi_corpus import declarations
     syms = declared_symbols()
     assert set(syms) == set(abi.ENTRY_POINTS), (syms, abi.ENTRY_POINTS)
-    for s in syms:
+    decl = declarations()
+    tables = dict(abi.ENTRY_POINTS, **abi.EXPERT_ENTRY_POINTS)
+    assert {n: len(a) for n, a in decl.items()} == {n: len(sig[1]) for n, sig in tables.items()}
+    for s in decl:
         assert hasattr(lib, s), "libmdstep.so does not export %s" % s
 
 
