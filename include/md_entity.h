@@ -681,17 +681,19 @@ MD_HD void md_find_front_back(const MdState* s, const MdConfig* c, const MdLane*
     }
 }
 
-/* Stage C */
-MD_HD void md_idm_decide(const MdLane* lanes, const MdRoad* roads, const MdState* s, int slot, const MdIdmPlan* p,
-                         const FrontBack* fbp) {
-    MdShape* sh = &s->shape[slot];
+/* Stage C, first half: lane_change_policy (idm_policy.py:330-402) and the bare-except fallback.  Updates the target
+ * speed and the overtake timer; returns the steering lane (-1: never localised) with the IDM's front object and gap.
+ * The steering lane is always one of the scanned lanes p->ids[0..2] (the left / right changes go to tidx -/+ 1, which
+ * md_idm_plan scanned whenever they are reachable), or -1: the HIP kernel's one-vehicle form (idm_vehicle_wave) relies on
+ * it, steering by the scan's projections on those lanes. */
+MD_HD int md_idm_policy(const MdLane* lanes, const MdRoad* roads, const MdState* s, int slot, const MdIdmPlan* p,
+                        const FrontBack* fbp, int* front_obj_out, float* front_dist_out) {
     MdNav* nav = &s->nav[slot];
     MdPid* pid = &s->pid[slot];
-    MdDyn* d = &s->dyn[slot];
+    const MdDyn* d = &s->dyn[slot];
     const MdRoad* cur_road = &roads[nav->road0];
     int has_next = nav->ck1 != nav->ck0;
     const MdRoad* next_road = has_next ? &roads[nav->road1] : 0;
-    float px = sh->cx, py = sh->cy;
     float speed_kmh = md_fabs(d->speed) * 3.6f;
     FrontBack fb = *fbp;
 
@@ -790,16 +792,19 @@ MD_HD void md_idm_decide(const MdLane* lanes, const MdRoad* roads, const MdState
         front_dist = 5.0f;
         steer_lane = nav->target_lane;
     }
-    if (steer_lane < 0) { /* never localised: coast straight */
-        s->action[2 * slot] = 0.0f;
-        s->action[2 * slot + 1] = 0.0f;
-        return;
-    }
-    /* ---- steering_control (idm_policy.py:293-301) ---- */
-    const MdLane* TL = &lanes[steer_lane];
-    float tl_s, tl_lat;
-    md_lane_local(TL, px, py, &tl_s, &tl_lat);
-    float lane_heading = md_lane_heading_at(TL, tl_s + 1.0f);
+    *front_obj_out = front_obj;
+    *front_dist_out = front_dist;
+    return steer_lane;
+}
+
+/* Stage C, second half: steering_control (idm_policy.py:293-301) and acceleration (:303-320), given the vehicle's
+ * lateral offset on the steering lane and that lane's heading 1 m ahead of the vehicle's longitudinal, and its speed in
+ * km/h as read before the policy ran. */
+MD_HD void md_idm_act(const MdState* s, int slot, float speed_kmh, int front_obj, float front_dist, float tl_lat,
+                      float lane_heading) {
+    const MdShape* sh = &s->shape[slot];
+    MdPid* pid = &s->pid[slot];
+    const MdDyn* d = &s->dyn[slot];
     float steering = md_pid(&pid->hp, &pid->hi, &pid->hd, 1.7f, 0.01f, 3.5f, -md_wrap_to_pi(lane_heading - d->heading));
     steering += md_pid(&pid->lp, &pid->li, &pid->ld, 0.3f, 0.002f, 0.05f, -tl_lat);
     /* ---- acceleration (idm_policy.py:303-320) ---- */
@@ -814,6 +819,25 @@ MD_HD void md_idm_decide(const MdLane* lanes, const MdRoad* roads, const MdState
     float acc = md_idm_acceleration(speed_kmh, pid->target_speed, front_obj >= 0, front_dist, dv);
     s->action[2 * slot] = steering;
     s->action[2 * slot + 1] = acc;
+}
+
+/* Stage C */
+MD_HD void md_idm_decide(const MdLane* lanes, const MdRoad* roads, const MdState* s, int slot, const MdIdmPlan* p,
+                         const FrontBack* fbp) {
+    int front_obj;
+    float front_dist;
+    float px = s->shape[slot].cx, py = s->shape[slot].cy;
+    float speed_kmh = md_fabs(s->dyn[slot].speed) * 3.6f;
+    int steer_lane = md_idm_policy(lanes, roads, s, slot, p, fbp, &front_obj, &front_dist);
+    if (steer_lane < 0) { /* never localised: coast straight */
+        s->action[2 * slot] = 0.0f;
+        s->action[2 * slot + 1] = 0.0f;
+        return;
+    }
+    const MdLane* TL = &lanes[steer_lane];
+    float tl_s, tl_lat;
+    md_lane_local(TL, px, py, &tl_s, &tl_lat);
+    md_idm_act(s, slot, speed_kmh, front_obj, front_dist, tl_lat, md_lane_heading_at(TL, tl_s + 1.0f));
 }
 
 /* All three stages for one vehicle, serial. */
