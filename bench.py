@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """bench.py -- agent-steps/s of the batched MetaDrive step() on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline line needs and no more: it builds the scenes, pre-rolls, warms up, times the K steps,
+writes --dump-outputs if asked, and prints the line (`value`, `ms_per_step`, `roofline` of the timed region).  --full adds
+every other leg listed under "Extra objects" below (each still has its --no-* switch); without it those objects are null.
 
 A "step" is one env.step() of the whole batch: ONE md_step launch that advances every env by 0.1 s
 of simulated time (IDM traffic -> kinematic integration -> lane localisation -> contacts -> obs /
@@ -28,9 +32,11 @@ most 64 MB in all (above that, a fixed seeded sample of the envs, listed in env_
 actions and seeds depend on the arguments only, so two builds run with the same arguments can be
 compared array for array.
 
-Extra objects in the JSON line:
+Objects in the JSON line:
   roofline     the fused step kernel: algorithmic bytes per launch / average launch duration
-               (HIP events on the launch stream over the timed region) against the HBM peak
+               (HIP events on the launch stream over the timed region) against the HBM peak; with --full also
+               peak_attainable, a stream-copy kernel's GB/s on this GPU
+Extra objects (--full only):
   lidar        the stand-alone md_lidar kernel measured the same way (bytes = 16 + 24*M + 4*B per agent)
   cpu_baseline the CPU oracle (oracle/md_oracle.c, "port", rebuilt -O3 -march=native on this host) on the
                host cores, bounded sample
@@ -50,6 +56,7 @@ import subprocess
 import sys
 import time
 from collections import OrderedDict
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -70,6 +77,9 @@ def parse():
                    help="untimed steps after reset() before --warmup: the batch reaches its stationary episode mix")
     p.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     p.add_argument("--cap", type=int, default=0, help="mover slots per env (0 = smallest that fits)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline steps, also run the extra legs: stand-alone lidar, stream copy, env API, lane "
+                        "follow, sub-batches, shared maps, gather (N>1), CPU baseline; the --no-* switches below skip one each")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-lane-follow", action="store_true", help="skip the scripted-driver operating point")
     p.add_argument("--no-env-api", action="store_true", help="skip the BatchedMetaDriveEnv.step leg")
@@ -175,24 +185,27 @@ def host_cache_key(args, rank, world):
             h.update(fh.read())
     return dict(abi=abi.MD_ABI_VERSION, workload=args.workload, envs=args.envs, cap=args.cap, sub=args.sub_batches, rank=rank,
                 world=world, cpu=(args.cpu_envs, bool(args.no_cpu_baseline)), src=h.hexdigest()[:16],
-                step_kernel=os.environ.get("MD_STEP_KERNEL", ""), shared=bool(args.no_shared_maps))
+                step_kernel=os.environ.get("MD_STEP_KERNEL", ""), shared=bool(args.no_shared_maps), full=bool(args.full))
 
 
-def load_or_build_hosts(path, build, key):
-    """--host-cache: our own pickle of the host scenes, valid only for the key it was written with (a stale one is rebuilt)."""
-    if path and os.path.exists(path):
-        with open(path, "rb") as fh:   # our own file, written by the branch below
-            blob = pickle.load(fh)
-        if isinstance(blob, dict) and blob.get("key") == key:
-            return blob["hosts"]
-        print("bench.py: host cache %s was built for %r, not %r: rebuilding" % (path, blob.get("key") if isinstance(blob, dict) else None, key),
-              file=sys.stderr)
-    hosts = build()
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "wb") as fh:
-            pickle.dump(dict(key=key, hosts=hosts), fh, protocol=4)
-    return hosts
+def read_host_cache(path, key):
+    """--host-cache: our own pickle of the host scenes, valid only for the key it was written with (None: absent or stale,
+    to be rebuilt)."""
+    if not (path and os.path.exists(path)):
+        return None
+    with open(path, "rb") as fh:   # our own file, written by write_host_cache
+        blob = pickle.load(fh)
+    if isinstance(blob, dict) and blob.get("key") == key:
+        return blob["hosts"]
+    print("bench.py: host cache %s was built for %r, not %r: rebuilding" % (path, blob.get("key") if isinstance(blob, dict) else None, key),
+          file=sys.stderr)
+    return None
+
+
+def write_host_cache(path, key, hosts):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:
+        pickle.dump(dict(key=key, hosts=hosts), fh, protocol=4)
 
 
 def dump_outputs(eng, out_dir, rank, world):
@@ -244,17 +257,17 @@ def main():
         os.environ.setdefault("MD_BUILD_WORKERS", str(max(1, min(32, (os.cpu_count() or 8) // world))))
     # the host build workers first: plain child interpreters, started while this process has no GPU context, kept to the end
     from metadrive_ped_amd import hostpool
-    if not (args.host_cache and os.path.exists(args.host_cache)):
+    cache_key = host_cache_key(args, rank, world)
+    hosts = read_host_cache(args.host_cache, cache_key)
+    if hosts is None:
         hostpool.start()
-    import torch
-    import torch.distributed as dist
     from metadrive_ped_amd.config import make_config
     from metadrive_ped_amd.engine import BatchedEngine, HostScene
 
     E = args.envs
     common = dict(num_envs=E, num_scenarios=E * max(world, 1), env_seed_offset=rank * E, start_seed=0,
                   mover_capacity=args.cap, auto_reset=True, device="cuda:%d" % local_rank,
-                  build_cache=True)   # the sub-batch leg and the CPU baseline step the same scenario seeds: built once
+                  build_cache=args.full)   # --full: the sub-batch leg and the CPU baseline step the same scenario seeds: built once
     env_cls = None
     if args.workload == "metadrive":
         user = dict(common, map=3, traffic_density=0.1, horizon=1000)
@@ -293,13 +306,13 @@ def main():
         cfg = BatchedMultiAgentRoundaboutEnv(dict(common, vehicle_config=dict(lidar=dict(num_lasers=240, distance=50)))).config
         label = "BASELINE configs[2]: %d MultiAgentRoundaboutEnv x 40 agents per GPU, 240-beam lidar, respawn on" % E
 
-    # ---- host-side scene generation: ALL of it happens BEFORE the GPU / process group are touched (fork pools
-    #      inside HostScene), including the scenes of the CPU baseline and of the extra legs ----
+    # ---- host-side scene generation: ALL of it (the scenes of the CPU baseline and of the extra legs included) is done by the
+    #      build workers started above, before the process group comes up; a plain run builds the main scenes only ----
     t0 = time.time()
-    want_sub = (world == 1 and args.sub_batches > 1 and args.workload in ("metadrive", "safe", "marl")
+    want_sub = (args.full and world == 1 and args.sub_batches > 1 and args.workload in ("metadrive", "safe", "marl")
                 and E % args.sub_batches == 0)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "metadrive"
-    want_shared = world == 1 and args.workload == "metadrive" and not args.no_shared_maps
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "metadrive"
+    want_shared = args.full and world == 1 and args.workload == "metadrive" and not args.no_shared_maps
     n_cpu = min(args.cpu_envs, E)
     n_cpu1 = max(1, n_cpu // 16)
 
@@ -335,13 +348,24 @@ def main():
                 h[key] = HostScene(c)
         return h
 
-    hosts = load_or_build_hosts(args.host_cache, build_hosts, host_cache_key(args, rank, world))
+    cpu_lib = build_fast_oracle() if want_cpu else None     # its `make` runs before this process has a GPU context
+    with ThreadPoolExecutor(1) as builder:
+        # the build workers (started above) make the scenes while this thread imports torch and brings up the GPU: nothing
+        # forks from here on
+        hosts_f = builder.submit(build_hosts) if hosts is None else None
+        import torch
+        import torch.distributed as dist
+        from metadrive_ped_amd import _lib
+        torch.cuda.set_device(local_rank)
+        _lib.load()
+        if hosts_f is not None:
+            hosts = hosts_f.result()
+            if args.host_cache:
+                write_host_cache(args.host_cache, cache_key, hosts)
     hostpool.clear_memo()
     host = hosts["main"]
-    cpu_lib = build_fast_oracle() if want_cpu else None
     build_s = time.time() - t0
 
-    torch.cuda.set_device(local_rank)
     sub = None
     if want_sub and "sub_hosts" in hosts:
         from metadrive_ped_amd.envs.metadrive_env import BatchedMetaDriveEnv
@@ -474,50 +498,54 @@ def main():
                     limiter="instruction issue / dependent-chain latency, not HBM: the path moves ~15 MB per launch "
                             "(SURVEY 8d); frac is the BASELINE metric, not a claim that HBM bounds the kernel")
 
-    # ---- stand-alone lidar kernel ----
-    n_ev = 50
-    out = torch.empty(E * A, B, device=dev)
-    ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    eng.lidar(out, B, 0)
-    torch.cuda.synchronize()
-    ev_a.record()
-    for i in range(n_ev):
+    # ---- --full: the stand-alone lidar kernel and the stream copy take launches of their own ----
+    lidar = None
+    roofline.update(peak_attainable=None, frac_attainable=None)
+    if args.full:
+        # ---- stand-alone lidar kernel ----
+        n_ev = 50
+        out = torch.empty(E * A, B, device=dev)
+        ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         eng.lidar(out, B, 0)
-    ev_b.record()
-    torch.cuda.synchronize()
-    lid_ms = ev_a.elapsed_time(ev_b) / n_ev
-    bytes_lidar = (16.0 + 24.0 * (M - 1) + 4.0 * B) * E * A
-    lidar = dict(kernel="lidar_kernel (md_lidar)", avg_launch_us=round(lid_ms * 1e3, 2),
-                 achieved=round(bytes_lidar / (lid_ms * 1e-3) / 1e9, 2), peak=HBM_PEAK_GBS, unit="GB/s",
-                 frac=round(bytes_lidar / (lid_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5), bytes_per_launch=int(bytes_lidar),
-                 flops_per_launch=int(30.0 * B * (M - 1) * E * A))
+        torch.cuda.synchronize()
+        ev_a.record()
+        for i in range(n_ev):
+            eng.lidar(out, B, 0)
+        ev_b.record()
+        torch.cuda.synchronize()
+        lid_ms = ev_a.elapsed_time(ev_b) / n_ev
+        bytes_lidar = (16.0 + 24.0 * (M - 1) + 4.0 * B) * E * A
+        lidar = dict(kernel="lidar_kernel (md_lidar)", avg_launch_us=round(lid_ms * 1e3, 2),
+                     achieved=round(bytes_lidar / (lid_ms * 1e-3) / 1e9, 2), peak=HBM_PEAK_GBS, unit="GB/s",
+                     frac=round(bytes_lidar / (lid_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5), bytes_per_launch=int(bytes_lidar),
+                     flops_per_launch=int(30.0 * B * (M - 1) * E * A))
 
-    # ---- attainable HBM bandwidth on this box: HIP stream-copy kernel through the same library ----
-    import ctypes as C
-    nbytes = 1 << 30
-    src = torch.empty(nbytes, dtype=torch.uint8, device=dev).fill_(1)
-    dst = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    for _ in range(3):
-        eng._check(eng.lib.md_probe_stream_copy(C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), nbytes, st), "copy")
-    ca, cb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ca.record()
-    for _ in range(10):
-        eng._check(eng.lib.md_probe_stream_copy(C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), nbytes, st), "copy")
-    cb.record()
-    torch.cuda.synchronize()
-    copy_gbs = 2.0 * nbytes * 10 / (ca.elapsed_time(cb) * 1e-3) / 1e9
-    del src, dst
-    roofline["peak_attainable"] = round(copy_gbs, 1)            # measured stream copy (read + write), GB/s
-    roofline["frac_attainable"] = round(achieved / copy_gbs, 5)
-    lidar["fp32_tflops"] = round(lidar["flops_per_launch"] / (lid_ms * 1e-3) / 1e12, 2)
-    lidar["fp32_peak_tflops"] = FP32_PEAK_TFLOPS
-    lidar["fp32_frac"] = round(lidar["fp32_tflops"] / FP32_PEAK_TFLOPS, 4)
+        # ---- attainable HBM bandwidth on this GPU: HIP stream-copy kernel through the same library ----
+        import ctypes as C
+        nbytes = 1 << 30
+        src = torch.empty(nbytes, dtype=torch.uint8, device=dev).fill_(1)
+        dst = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for _ in range(3):
+            eng._check(eng.lib.md_probe_stream_copy(C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), nbytes, st), "copy")
+        ca, cb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ca.record()
+        for _ in range(10):
+            eng._check(eng.lib.md_probe_stream_copy(C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), nbytes, st), "copy")
+        cb.record()
+        torch.cuda.synchronize()
+        copy_gbs = 2.0 * nbytes * 10 / (ca.elapsed_time(cb) * 1e-3) / 1e9
+        del src, dst
+        roofline["peak_attainable"] = round(copy_gbs, 1)            # measured stream copy (read + write), GB/s
+        roofline["frac_attainable"] = round(achieved / copy_gbs, 5)
+        lidar["fp32_tflops"] = round(lidar["flops_per_launch"] / (lid_ms * 1e-3) / 1e12, 2)
+        lidar["fp32_peak_tflops"] = FP32_PEAK_TFLOPS
+        lidar["fp32_frac"] = round(lidar["fp32_tflops"] / FP32_PEAK_TFLOPS, 4)
 
     # ---- the Gymnasium-shaped boundary (N=1, single-agent): BatchedMetaDriveEnv.step on the same scenes and the
     #      same actions: engine.step + the (terminated, truncated) flags + the lazy info dict, per step ----
     env_api = None
-    if rank == 0 and world == 1 and A == 1 and args.workload in ("metadrive", "safe") and not args.no_env_api:
+    if args.full and rank == 0 and world == 1 and A == 1 and args.workload in ("metadrive", "safe") and not args.no_env_api:
         from metadrive_ped_amd.envs.metadrive_env import BatchedMetaDriveEnv
         env = BatchedMetaDriveEnv(dict(user, mover_capacity=host.cap) if args.workload == "metadrive" else
                                   dict(user, mover_capacity=host.cap))
@@ -542,7 +570,7 @@ def main():
     #      actions.  Episodes last several hundred steps, more traffic blocks get triggered (about twice the driving
     #      vehicles per env), so the step is heavier: reported next to `value`, never instead of it. ----
     lane_follow = None
-    if rank == 0 and world == 1 and A == 1 and args.workload in ("metadrive", "safe") and not args.no_lane_follow:
+    if args.full and rank == 0 and world == 1 and A == 1 and args.workload in ("metadrive", "safe") and not args.no_lane_follow:
         o_hd, o_v, o_lat = eng.host.obs_base + (eng.host.n_side or 2), eng.host.obs_base + (eng.host.n_side or 2) + 1, \
             eng.host.obs_base + (eng.host.n_side or 2) + 6
         act_buf = torch.zeros(E, 1, 2, device=dev)
@@ -625,7 +653,7 @@ def main():
     #      (BatchedEngine.out_slab) -- to every rank with ONE RCCL collective per step, timed over the same number of steps
     #      as the main leg (>= MIN_TIMED_S) ----
     with_gather = None
-    if world > 1:
+    if args.full and world > 1:
         from metadrive_ped_amd.sharding import gather_step_slab
         slab = eng.out_slab
         gathered = torch.empty((world, slab.numel()), dtype=torch.uint8, device="cpu" if rehearse else dev)
@@ -703,7 +731,7 @@ def main():
             higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
             config=dict(workload=label,
                         envs_per_gpu=E, active_agent_fraction=round(active_frac, 3), agents_per_env=A, mover_capacity=cap, n_beams=B, sharding="env-range per rank"),
-            preroll=args.preroll, timed_steps=timed_steps,
+            preroll=args.preroll, timed_steps=timed_steps, full=args.full,
             roofline=roofline, lidar=lidar, cpu_baseline=cpu_baseline, env_api=env_api, lane_follow_policy=lane_follow,
             double_buffered=double_buffered, shared_maps=shared_maps, with_gather=with_gather, host_build_s=round(build_s, 1))
         print(json.dumps(line))

@@ -3,7 +3,7 @@
 OUT=$1; shift
 mkdir -p $OUT
 CACHE_DIR=$(mktemp -d); CACHE=$CACHE_DIR/host_cache.pkl   # a private scratch dir (the pickle is keyed; gpurun_out/ only carries results back)
-LEAN="--no-cpu-baseline --no-lane-follow --no-env-api --no-shared-maps --host-cache $CACHE"
+LEAN="--full --no-cpu-baseline --no-lane-follow --no-env-api --no-shared-maps --host-cache $CACHE"   # --full: the double_buffered leg
 python bench.py --steps 100 --warmup 10 $LEAN > $OUT/base.json 2> $OUT/base.err || { tail -5 $OUT/base.err; exit 1; }
 python - <<PY
 import json; d=json.loads(open("$OUT/base.json").read().strip().splitlines()[-1]); print("base", d["ms_per_step"], d["value"], (d.get("double_buffered") or {}).get("ms_per_step"))
