@@ -21,10 +21,19 @@
 
 #include "md_geom.h"
 
+/* scenario mode: the scene env e plays (MdState.scene_of; `s` global, not a view), and the slots per recorded frame */
+MD_HD int md_scene_of_env(const MdState* g, int e) { return g->scene_of ? g->scene_of[e] : e; }
+MD_HD size_t md_track_stride(const MdState* s, const MdConfig* c) {
+    return (size_t)(s->walk.n_scenes > 0 ? s->walk.n_scenes : c->n_envs) * (size_t)c->cap;
+}
+/* the same on an env view: its scene_of points at the env's own entry */
+MD_HD int md_scene(const MdState* s, int e) { return s->scene_of ? s->scene_of[0] : e; }
+
 /* env-local view of the global state arrays (see header comment) */
 MD_HD MdState md_env_view(const MdState* g, const MdConfig* c, int e) {
     MdState v = *g;
     const size_t b = (size_t)e * (size_t)c->cap;
+    const size_t bs = (size_t)md_scene_of_env(g, e) * (size_t)c->cap;   /* the scene's slots in the per-scene frames */
     const size_t a = (size_t)e * (size_t)c->agents_per_env;
     v.shape = g->shape + b;
     v.dyn = g->dyn ? g->dyn + b : 0;
@@ -58,8 +67,10 @@ MD_HD MdState md_env_view(const MdState* g, const MdConfig* c, int e) {
     v.next_agent_id = g->next_agent_id ? g->next_agent_id + e : 0;
     v.detected = g->detected ? g->detected + (size_t)e * c->agents_per_env * 2 : 0;
     v.agent_action = g->agent_action ? g->agent_action + (size_t)e * c->agents_per_env * 2 : 0;
-    v.track_shape = g->track_shape ? g->track_shape + b : 0;   /* + t * n_envs * cap per frame */
-    v.track_dyn = g->track_dyn ? g->track_dyn + 2 * b : 0;
+    v.track_shape = g->track_shape ? g->track_shape + bs : 0;   /* + t * md_track_stride(s, c) per frame */
+    v.track_dyn = g->track_dyn ? g->track_dyn + 2 * bs : 0;
+    v.scene_of = g->scene_of ? g->scene_of + e : 0;
+    v.walk_ep = g->walk_ep ? g->walk_ep + e : 0;
     v.route_n = g->route_n ? g->route_n + 4 * b : 0;
     v.route_segs = g->route_segs ? g->route_segs + b * (size_t)c->route_seg_cap : 0;
     v.route_verts = g->route_verts ? g->route_verts + 2 * b * (size_t)c->route_vert_cap : 0;
@@ -121,7 +132,7 @@ MD_HD void md_replay_mover(const MdState* s, const MdConfig* c, int n) {
     int t = s->nav[0].steps + 1;
     if (t >= c->track_len) t = c->track_len - 1;
     if (t < 0) return;
-    const size_t at = (size_t)t * (size_t)c->n_envs * (size_t)c->cap + (size_t)n;
+    const size_t at = (size_t)t * md_track_stride(s, c) + (size_t)n;
     const MdShape r = s->track_shape[at];
     MdShape* sh = &s->shape[n];
     MdDyn* d = &s->dyn[n];

@@ -235,7 +235,7 @@ MD_HD void md_scenario_observe_at(const MdWorld* w, const MdState* s, const MdCo
     else
         for (int i = 0; i < c->n_lane_line; ++i) obs[o_ll + i] = 1.0f;
     {
-        const int k0 = w->ckpt_off[e], k1 = w->ckpt_off[e + 1];
+        const int sc = md_scene(s, e), k0 = w->ckpt_off[sc], k1 = w->ckpt_off[sc + 1];
         md_traj_navi(w->ckpt_xy + 2 * (size_t)k0, k1 - k0, &L, sh->cx, sh->cy, sh->c, sh->s, d->heading, c->max_lateral_dist,
                      obs + o_navi, with_points);
     }
@@ -299,7 +299,7 @@ MD_HD void md_scenario_observe_at(const MdWorld* w, const MdState* s, const MdCo
     else if (max_step) {
         if (c->truncate_as_terminate) done = 1;
     } else if (c->allowed_more_steps > 0 &&   /* this scene's own length: track_meta[slot 0][1] (<= c->scenario_length, the batch's) */
-               nav->steps >= w->track_meta[4 * ((size_t)e * c->cap) + 1] + c->allowed_more_steps) {
+               nav->steps >= w->track_meta[4 * ((size_t)md_scene(s, e) * c->cap) + 1] + c->allowed_more_steps) {
         if (c->truncate_as_terminate) done = 1;
         max_step = 1;
     }
@@ -333,7 +333,7 @@ MD_HD void md_scenario_observe_at(const MdWorld* w, const MdState* s, const MdCo
 
 /* serial form (oracle): project the agent on its reference trajectory, then observe */
 MD_HD void md_scenario_observe(const MdWorld* w, const MdState* s, const MdConfig* c, int e, int a, int env_just_reset) {
-    const MdPoly ref = md_poly_of(w, (size_t)e * c->cap + a);
+    const MdPoly ref = md_poly_of(w, (size_t)md_scene(s, e) * c->cap + a);
     MdTrajLoc L;
     md_traj_locate(&ref, s->shape[a].cx, s->shape[a].cy, &L);
     md_scenario_observe_at(w, s, c, e, a, env_just_reset, &L, ref.length, 1);
@@ -361,7 +361,7 @@ MD_HD MdRoute md_route_of(const MdWorld* w, const MdState* s, const MdConfig* c,
         r.n_verts = s->route_n[4 * slot + 1];
         r.aux = s->route_aux + 8 * (size_t)slot;
     } else {
-        const size_t ng = (size_t)e * c->cap + slot;
+        const size_t ng = (size_t)md_scene(s, e) * c->cap + slot;
         const int a = w->poly_off[ng], b = w->poly_off[ng + 1];
         r.poly.segs = w->segs + a;
         r.poly.n = b - a;
@@ -659,7 +659,7 @@ MD_HD void md_scenario_replay_ego(const MdState* s, const MdConfig* c, int a, in
     d->steering = 0.0f;
     d->throttle = 0.0f;
     if (k >= c->track_len) return;
-    const size_t at = (size_t)k * (size_t)c->n_envs * (size_t)c->cap + (size_t)a;
+    const size_t at = (size_t)k * md_track_stride(s, c) + (size_t)a;
     const MdShape fr = s->track_shape[at];
     if (!(fr.flags & MD_F_ALIVE)) return;
     sh->cx = fr.cx;
@@ -688,10 +688,10 @@ MD_HD int md_scenario_slot_after_step(const MdWorld* w, const MdState* s, const 
     MdShape* sh = &s->shape[j];
     MdDyn* d = &s->dyn[j];
     MdNav* nav = &s->nav[j];
-    const size_t ng = (size_t)e * c->cap + j;
+    const size_t ng = (size_t)md_scene(s, e) * c->cap + j;
     const int32_t* tm = w->track_meta + 4 * ng;
     const int in_data = k < c->track_len;
-    const size_t at = (size_t)(in_data ? k : 0) * (size_t)c->n_envs * (size_t)c->cap + (size_t)j;
+    const size_t at = (size_t)(in_data ? k : 0) * md_track_stride(s, c) + (size_t)j;
     const MdShape fr = s->track_shape[at];
     const int valid = in_data && (fr.flags & MD_F_ALIVE);
     const int kind = md_kind_of(fr.flags);
@@ -744,7 +744,7 @@ MD_HD int md_scenario_slot_after_step(const MdWorld* w, const MdState* s, const 
                 if (s->route_n && c->route_seg_cap > 0) {
                     const int t1 = md_track_run_end(w, ng, k);
                     if (t1 > k) {
-                        const MdShape last = s->track_shape[(size_t)(t1 - 1) * (size_t)c->n_envs * (size_t)c->cap + (size_t)j];
+                        const MdShape last = s->track_shape[(size_t)(t1 - 1) * md_track_stride(s, c) + (size_t)j];
                         idm = md_norm(fr.cx - last.cx, fr.cy - last.cy) > 5.0f;
                         late_pts = t1 - k;
                     }
@@ -796,8 +796,8 @@ MD_HD void md_scenario_build_pending(const MdState* s, const MdConfig* c, int j,
     const int n_pts = s->route_n[4 * j + 3] < c->route_seg_cap ? s->route_n[4 * j + 3] : c->route_seg_cap;   /* (the host sizes the cap
                                                                                         by the longest run: never cut) */
     if (!xy) {
-        xy = &s->track_shape[(size_t)k * (size_t)c->n_envs * (size_t)c->cap + (size_t)j].cx;
-        stride = (size_t)c->n_envs * (size_t)c->cap * (sizeof(MdShape) / sizeof(float));
+        xy = &s->track_shape[(size_t)k * md_track_stride(s, c) + (size_t)j].cx;
+        stride = md_track_stride(s, c) * (sizeof(MdShape) / sizeof(float));
     }
     int32_t counts[2];
     md_build_route(xy, stride, n_pts, s->route_segs + (size_t)j * c->route_seg_cap, c->route_seg_cap,
@@ -813,6 +813,34 @@ MD_HD void md_scenario_after_step_env(const MdWorld* w, const MdState* s, const 
         s->next_agent_id[0] += md_scenario_slot_after_step(w, s, c, e, j, k, s->next_agent_id[0], 0);
         md_scenario_build_pending(s, c, j, 0, 0);
     }
+}
+
+/* ------------------------------------------------------------------------------------------
+ * The scenario walk (MdState.walk): the scene (index into the dataset slice [start_scenario_index, + n_scenes)) env e of the
+ * batch plays in its episode `ep` (0 = the first after a reset).  A pure function of (e, ep), so that the walk's whole state is
+ * MdState.walk_ep.  md_swap_draw runs it on the device; the host (metadrive_ped_amd/scenario.py walk_scene) restates it.
+ *   mode 1, sequential: ScenarioEnv._reset_global_seed with sequential_seed (envs/scenario_env.py:359-380) as worker
+ *     w = (offset + e) mod n_scenes of W = stride workers: the first seed is w, every episode end adds W, a seed past the
+ *     slice goes back to w -- the env plays w, w + W, w + 2W, ... (never the seeds in between), m = ceil((n_scenes - w) / W) of them.
+ *   mode 2, uniform: a draw over the slice keyed by (seed, global env index offset + e, ep) -- a counter-based stream,
+ *     reproducible (the reference draws from an unseeded generator).
+ * -----------------------------------------------------------------------------------------*/
+MD_HD uint64_t md_walk_mix(uint64_t z) {   /* splitmix64's finaliser */
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+MD_HD int md_walk_scene(const MdWalk* c, int e, int ep) {
+    const int n = c->n_scenes;
+    if (c->mode == 2) {
+        const uint64_t key = ((uint64_t)c->seed << 32) | (uint32_t)(c->offset + e);
+        const uint64_t z = md_walk_mix(md_walk_mix(key) ^ ((uint64_t)(uint32_t)ep * 0x9E3779B97F4A7C15ull));
+        return (int)(((z >> 32) * (uint64_t)(uint32_t)n) >> 32);   /* multiply-shift onto [0, n) */
+    }
+    const int w = (c->offset + e) % n, W = c->stride;
+    const int m = (n - w + W - 1) / W;
+    return w + (ep % m) * W;
 }
 
 #endif /* MD_SCENARIO_H */

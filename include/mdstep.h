@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MD_ABI_VERSION 11
+#define MD_ABI_VERSION 12
 
 /* ---- error codes ------------------------------------------------------------------------- */
 #define MD_OK 0
@@ -305,6 +305,16 @@ typedef struct MdWorld {
 } MdWorld;
 
 /* Dynamic state: one entry per mover unless noted. */
+/* MdState.walk -- the scenario walk of scenario mode (ABI v12; all 0 = off: scene e of the batch is scenario e for good) */
+typedef struct MdWalk {
+    int32_t n_scenes;          /* scenes in the per-scene tables and frames (0 = n_envs: one per env)                           */
+    int32_t mode;              /* 0 off, 1 sequential (ScenarioEnv sequential_seed, env e one worker of `stride`), 2 uniform draws */
+    int32_t stride;            /* W: the envs over all shards (the workers of the sequential walk)                             */
+    int32_t offset;            /* global index of env 0 of this batch (config env_seed_offset)                                 */
+    uint32_t seed;             /* seed of the uniform draws                                                                    */
+    int32_t reserved;          /* 0                                                                                            */
+} MdWalk;
+
 typedef struct MdState {
     MdShape* shape;
     MdDyn* dyn;
@@ -343,7 +353,8 @@ typedef struct MdState {
      * Saves the scatter into the per-slot array; md_step still writes the sanitised values to `action`. */
     const float* agent_action;
     /* traffic_mode 3 (replay): recorded poses of every non-agent slot, frame-major:
-     * track_shape[t * n_envs * cap + n], track_dyn[2 * (t * n_envs * cap + n)] = (heading, speed);
+     * track_shape[t * n_envs * cap + n], track_dyn[2 * (t * n_envs * cap + n)] = (heading, speed) (n_envs: MdState.walk.n_scenes
+     * when that is set, see scene_of);
      * frame t is the state at the END of the t-th step of the episode (frame 0 = reset state).  The role of
      * ReplayTrafficParticipantPolicy.act (policy/replay_policy.py:43-67): position / heading / velocity set
      * from the track at the current episode step, no reaction to the agents. */
@@ -380,6 +391,15 @@ typedef struct MdState {
      * agent's last steps, a ring written at index (MdNav.toll_state mod MD_IDLE_WINDOW); MdNav.toll_state counts the entries
      * (movement_between_steps, marl_racing_env.py:342,415) */
     float* idle_ring;
+    /* scenario mode with the scenario walk (MdState.walk; ABI v12), optional (both or none; NULL = env e plays scene e):
+     *   scene_of [n_envs]  the scene env e plays: the index its per-scene tables are read at (MdWorld.poly_off / polyv_off /
+     *                      poly_aux / poly_ball_off / run_off / track_meta at scene * cap + slot, ckpt_off[scene], the frames
+     *                      track_*[t * n_scenes * cap + scene * cap + slot]); MdWorld.env_map[e] names the same scene's line map
+     *   walk_ep  [n_envs]  the env's episode number along its walk (md_walk_scene(&walk, e, walk_ep[e]) == scene_of[e])
+     * md_swap_draw moves an env whose episode has ended on to its next scene (rows, scene_of, walk_ep, env_map). */
+    int32_t* scene_of;
+    int32_t* walk_ep;
+    MdWalk walk;               /* all 0 = no walk, one scene per env */
 } MdState;
 
 typedef struct MdConfig {

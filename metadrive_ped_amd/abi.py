@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-MD_ABI_VERSION = 11
+MD_ABI_VERSION = 12
 MD_POLY_GROUP = 8     # pieces per MdWorld.poly_ball group
 MD_OK, MD_EINVAL, MD_ELAUNCH, MD_ENODEV, MD_EABI = 0, -1, -2, -3, -4
 MD_MAX_CAP = 128
@@ -92,6 +92,11 @@ class MdWorld(C.Structure):
     ]
 
 
+class MdWalk(C.Structure):
+    _fields_ = [("n_scenes", C.c_int32), ("mode", C.c_int32), ("stride", C.c_int32), ("offset", C.c_int32), ("seed", C.c_uint32),
+                ("reserved", C.c_int32)]
+
+
 class MdState(C.Structure):
     _fields_ = [
         ("shape", P), ("dyn", P), ("param", P), ("nav", P), ("pid", P), ("action", P), ("route_nodes", P),
@@ -107,6 +112,8 @@ class MdState(C.Structure):
         ("param0", P),
         ("done_out", P),
         ("route_n", P), ("route_segs", P), ("route_verts", P), ("route_aux", P), ("idle_ring", P),
+        ("scene_of", P), ("walk_ep", P),
+        ("walk", MdWalk),
     ]
 
 

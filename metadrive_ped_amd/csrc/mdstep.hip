@@ -3209,6 +3209,9 @@ __host__ __device__ inline ScenarioLds scenario_lds(int cap, int agents, int n_d
     L.bytes = L.desc + (uint32_t)cap * sizeof(RouteDesc);
     return L;
 }
+// kPool: the batch plays scenes of a pool (MdState.scene_of, the scenario walk).  Without it the walk fields are constants here, so
+// that the per-scene lookups of the shared headers fold to scene = env and the kernel is the one of a batch without a walk.
+template <bool kPool>
 __global__ __launch_bounds__(256)
 #if MD_SC_WAVES_EU
 __attribute__((amdgpu_waves_per_eu(MD_SC_WAVES_EU, MD_SC_WAVES_EU)))
@@ -3216,6 +3219,11 @@ __attribute__((amdgpu_waves_per_eu(MD_SC_WAVES_EU, MD_SC_WAVES_EU)))
 void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, int lidar_stride,
                                                            int lidar_offset) {
     constexpr int kBlock = 256, kWaves = 4;
+    if (!kPool) {
+        g.scene_of = nullptr;
+        g.walk_ep = nullptr;
+        g.walk = MdWalk{};
+    }
     const int e = blockIdx.x;
     if (e >= c.n_envs) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -3287,7 +3295,7 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
             r_act = (fused_act && tid < A) ? reinterpret_cast<const float2*>(gv.agent_action)[tid] : reinterpret_cast<const float2*>(gv.action)[tid];
             r_fl = gv.flags[tid];
             // the slot's route record (md_route_of + MdWorld.poly_aux): every address is known here
-            const size_t ng = (size_t)e * cap + tid;
+            const size_t ng = (size_t)md_scene_of_env(&g, e) * cap + tid;   // the scene this env plays (MdState.scene_of)
             po0 = w.poly_off[ng];
             po1 = w.poly_off[ng + 1];
             pv0 = w.polyv_off[ng];
@@ -3500,7 +3508,7 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
                 const int kb = s.route_n[4 * jb + 2];
                 const int nb = min(s.route_n[4 * jb + 3], c.route_seg_cap);
                 for (int i = lane; i < nb; i += 64) {
-                    const MdShape fr = s.track_shape[(size_t)(kb + i) * (size_t)c.n_envs * (size_t)cap + (size_t)jb];
+                    const MdShape fr = s.track_shape[(size_t)(kb + i) * md_track_stride(&s, &c) + (size_t)jb];
                     l_pts[2 * i] = fr.cx;
                     l_pts[2 * i + 1] = fr.cy;
                 }
@@ -3557,7 +3565,8 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
     MD_STAMP_AT(5);
     // the nine way points of the navigation vector: one lane each (wave 0), both slots of a way point get the value
     if (wave == 0 && lane < MD_TRAJ_NUM_WAY_POINT - 1) {
-        const int k0 = w.ckpt_off[e], n_ck = w.ckpt_off[e + 1] - k0;
+        const int sc = md_scene_of_env(&g, e);
+        const int k0 = w.ckpt_off[sc], n_ck = w.ckpt_off[sc + 1] - k0;
         const float* ck = w.ckpt_xy + 2 * (size_t)k0;
         for (int a = 0; a < A; ++a) {
             const MdTrajLoc L = l_loc[a];
@@ -3638,14 +3647,25 @@ __global__ __launch_bounds__(256) void lidar_detect_kernel(MdWorld w, MdState g,
 // that has just finished its episode (need_reset != 0: md_step restores it from the snapshot at the NEXT step) takes the next draw --
 // the snapshot rows and the per-slot constants of the traffic (parameters, routes, pre-drawn lane-change timers) of that env are
 // replaced.  One workgroup per env, a no-op for the envs that go on.
+// The scenario walk (traffic_mode 4, MdState.walk.mode > 0) is the same move with the scenes for draws: `staged` holds the snapshot rows
+// of the n_draws = n_scenes scenes of the pool (scene p at p * cap), `draw_idx` is MdWorld.env_map (the scene's line map); the env
+// takes scene md_walk_scene(c, e, walk_ep[e] + 1) and scene_of / walk_ep / env_map follow.  The per-scene tables are only redirected.
 __global__ __launch_bounds__(256) void swap_draw_kernel(MdState live, MdState staged, MdConfig c, int n_draws, int32_t* draw_idx) {
     const int e = blockIdx.x;
     if (e >= c.n_envs || live.need_reset[e] == 0) return;   // block-uniform
     const int tid = threadIdx.x;
-    const int k = (draw_idx[e] + 1) % n_draws;
+    const bool walk = live.walk.mode != 0;
+    const int ep = walk ? live.walk_ep[e] + 1 : 0;
+    const int k = walk ? md_walk_scene(&live.walk, e, ep) : (draw_idx[e] + 1) % n_draws;
     __syncthreads();   // every thread has read the index
-    if (tid == 0) draw_idx[e] = k;
-    const size_t row = (size_t)e * c.cap, from = ((size_t)k * c.n_envs + e) * c.cap;
+    if (tid == 0) {
+        draw_idx[e] = k;
+        if (walk) {
+            live.scene_of[e] = k;
+            live.walk_ep[e] = ep;
+        }
+    }
+    const size_t row = (size_t)e * c.cap, from = walk ? (size_t)k * c.cap : ((size_t)k * c.n_envs + e) * c.cap;
     auto words = [&](void* dst, const void* src, size_t elem_words) {   // cap slots of elem_words 4-byte words each
         if (dst == nullptr || src == nullptr) return;
         uint32_t* d = reinterpret_cast<uint32_t*>(dst) + row * elem_words;
@@ -4174,6 +4194,16 @@ __attribute__((visibility("default"))) int md_swap_draw(const MdState* s, const 
         snprintf(g_err, sizeof g_err, "md_swap_draw: need_reset and the snapshot arrays shape0 / dyn0 / nav0 / pid0 (live and staged) are required");
         return MD_EINVAL;
     }
+    const MdWalk& wk = s->walk;
+    if (wk.mode != 0) {   // the scenario walk: n_draws scenes, draw_idx = MdWorld.env_map
+        if (wk.mode < 0 || wk.mode > 2 || c->traffic_mode != 4 || wk.n_scenes != n_draws || wk.stride < 1 || wk.offset < 0 ||
+            !s->scene_of || !s->walk_ep) {
+            snprintf(g_err, sizeof g_err, "md_swap_draw: the scenario walk needs mode 1 or 2 (got %d), traffic_mode 4, n_scenes == "
+                     "n_draws (%d, %d), stride >= 1 (%d), offset >= 0 (%d) and MdState.scene_of / walk_ep", wk.mode, wk.n_scenes,
+                     n_draws, wk.stride, wk.offset);
+            return MD_EINVAL;
+        }
+    }
     hipLaunchKernelGGL(swap_draw_kernel, dim3(c->n_envs), dim3(256), 0, (hipStream_t)stream, *s, *staged, *c, n_draws, draw_idx);
     return launch_status();
 }
@@ -4216,6 +4246,10 @@ __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdSta
                      md_sc_obs_lidar(c), c->n_beams);
             return MD_EINVAL;
         }
+        if (s->walk.n_scenes < 0 || (s->walk.n_scenes > 0 && !s->scene_of)) {   // a scene pool: scene_of says which scene
+            snprintf(g_err, sizeof g_err, "scenario mode: MdState.walk.n_scenes=%d needs MdState.scene_of", s->walk.n_scenes);
+            return MD_EINVAL;
+        }
         const size_t lds = scenario_lds(c->cap, c->agents_per_env, c->n_side + c->n_lane_line, s->route_n != nullptr, c->route_seg_cap).bytes;
         if (s->route_n) {
             TRY(need_fields(PH_ALL, ROUTE, w, s, c));
@@ -4229,8 +4263,12 @@ __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdSta
             snprintf(g_err, sizeof g_err, "scenario mode: LDS image needs %zu B (cap=%d)", lds, c->cap);
             return MD_EINVAL;
         }
-        hipLaunchKernelGGL(scenario_step_kernel, dim3(c->n_envs), dim3(256), lds, (hipStream_t)stream, *w, *s, *c, s->obs, c->obs_dim,
-                           md_sc_obs_lidar(c));
+        if (s->scene_of)
+            hipLaunchKernelGGL(scenario_step_kernel<true>, dim3(c->n_envs), dim3(256), lds, (hipStream_t)stream, *w, *s, *c, s->obs,
+                               c->obs_dim, md_sc_obs_lidar(c));
+        else
+            hipLaunchKernelGGL(scenario_step_kernel<false>, dim3(c->n_envs), dim3(256), lds, (hipStream_t)stream, *w, *s, *c, s->obs,
+                               c->obs_dim, md_sc_obs_lidar(c));
         return launch_status();
     }
     if (c->obs_dim != md_obs_lidar(c) + c->n_beams + md_obs_tail(c)) {

@@ -503,6 +503,18 @@ class BatchedEngine:
             self._staged = abi.MdState()
             abi.fill_struct(self._staged, abi.STATE_FIELDS, self._staged_dev, ptr)
             self.draw_idx = torch.zeros(self.E, dtype=torch.int32, device=self.device)
+        # the scenario walk: the staged "draws" are the scene pool's snapshot rows; the env's scene index is its line map
+        # (MdWorld.env_map), which md_swap_draw rewrites together with MdState.scene_of / walk_ep
+        self._walk = getattr(h, "pool", None) is not None
+        if self._walk:
+            self.s.walk = abi.MdWalk(*h.walk_params)
+            self._staged_dev = {k: self._to_dev(v) for k, v in h.pool.items()}
+            self._staged = abi.MdState()
+            abi.fill_struct(self._staged, abi.STATE_FIELDS, self._staged_dev, ptr)
+            self.draw_idx = self.world_dev["env_map"]
+            self._n_draws = int(h.walk_params[0])
+        elif self._staged is not None:
+            self._n_draws = len(self.draw_hosts_)
         sd = self.state_dev
         # typed views for the env API
         self.obs = sd["obs"].view(torch.float32).view(self.E, self.A, self.obs_dim)
@@ -558,7 +570,15 @@ class BatchedEngine:
         """All envs back to their reset snapshot; returns after the reset observation is computed.
         (BaseEnv.reset -> engine.reset -> _get_reset_return, envs/base_env.py:502-584)"""
         self.need_reset.fill_(1)
+        if self._walk:     # every env back to the first scene of its walk (episode 0), then the reset step
+            self.state_dev["walk_ep"].view(self.torch.int32).fill_(-1)
+            with self._on_device():
+                self._swap()
         self.step_raw()
+
+    def _swap(self):
+        self._check(self.lib.md_swap_draw(C.byref(self.s), C.byref(self._staged), C.byref(self.k), self._n_draws,
+                                          C.c_void_p(self.draw_idx.data_ptr()), self._stream()), "md_swap_draw")
 
     SIDE_MASK = (1 << abi.Q_LINE_WHITE_CONT) | (1 << abi.Q_LINE_YELLOW_CONT)      # CollisionGroup.ContinuousLaneLine
     LANE_LINE_MASK = SIDE_MASK | (1 << abi.Q_LINE_BROKEN)                         # ... | BrokenLaneLine
@@ -569,9 +589,8 @@ class BatchedEngine:
 
     def _step_raw(self):
         self._check(self.lib.md_step(C.byref(self.w), C.byref(self.s), C.byref(self.k), self._stream()), "md_step")
-        if self._staged is not None:     # random_traffic: the envs whose episode just ended get other traffic for the next one
-            self._check(self.lib.md_swap_draw(C.byref(self.s), C.byref(self._staged), C.byref(self.k), len(self.draw_hosts_),
-                                              C.c_void_p(self.draw_idx.data_ptr()), self._stream()), "md_swap_draw")
+        if self._staged is not None:     # random_traffic / the scenario walk: the envs whose episode just ended get the next draw
+            self._swap()
         h = self.host
         vc = self.cfg["vehicle_config"]
         if self._fused_detectors:

@@ -5,7 +5,21 @@ of the same format (e.g. from BatchedMetaDriveEnv.export_scenarios()), or metadr
 
 Returns like the single-agent env: obs [E, obs_dim] (side cloud | state | 22 navigation dims | lidar), reward [E],
 terminated [E], truncated [E], info = dict of [E] tensors with ScenarioEnv's keys (route_completion, cost, crash_*,
-out_of_road, arrive_dest, max_step, ...)."""
+out_of_road, arrive_dest, max_step, ..., and scenario_index: the dataset index each env plays).
+
+walk_scenarios=True: the envs walk through the dataset slice [start_scenario_index, start_scenario_index + num_scenarios), a new
+scenario whenever an episode ends (the reference's ScenarioEnv picks one at every reset, envs/scenario_env.py:359-380).  Every
+scenario of the slice is built once into a scene pool; the device moves an env that has finished its episode on to its next
+scene (md_swap_draw), so a walk step costs what a fixed-scene step does.  The order:
+  sequential_seed=True: env e is worker w = (env_seed_offset + e) % num_scenarios of W = walk_stride workers (default num_envs;
+    sharding.shard_config sets it to the env count over all shards, so the shards split the slice as RLlib workers do).  It plays
+    start + w, then adds W after every episode, and goes back to start + w once the seed reaches start + num_scenarios: env e
+    plays only start + w + k * W, never the seeds in between.  (One worker of the reference's multi-worker rule, not one
+    single-env walk spread over the batch.)
+  sequential_seed=False: a uniform draw over the slice per (env, episode), from a stream keyed by start_seed and the global env
+    index -- reproducible, where the reference's draw is unseeded.
+reset() starts every env again at the first scenario of its walk; get_state() / set_state() carry each env's scene and walk
+position (MdState.scene_of / walk_ep) with the rest of the state."""
 import numpy as np
 
 from metadrive_ped_amd import abi
@@ -30,9 +44,13 @@ class BatchedScenarioEnv:
     def __init__(self, config=None, scenarios=None):
         self.config = make_scenario_config(config)
         self.num_envs = self.config["num_envs"]
+        walk = bool(self.config["walk_scenarios"])
         if scenarios is None and self.config["data_directory"] is not None:
             from metadrive_ped_amd.scenario_data import load_scenarios
-            scenarios = load_scenarios(self.config)   # scene e = scenario start_scenario_index + (offset + e) % num_scenarios
+            # scene e = scenario start_scenario_index + (offset + e) % num_scenarios; a walk: the whole slice, in order
+            scenarios = load_scenarios(self.config, pool=walk)
+        if scenarios is None and walk:
+            scenarios = synthetic_scenarios(self.config["num_scenarios"], self.config["start_scenario_index"])
         if scenarios is None:
             scenarios = synthetic_scenarios(self.num_envs, self.config["start_scenario_index"] + self.config["env_seed_offset"])
         self.scenarios = scenarios
@@ -104,6 +122,8 @@ class BatchedScenarioEnv:
             if k not in ref or np.asarray(v).nbytes != ref[k].nbytes:
                 raise ValueError("checkpoint array {!r} does not fit this batch".format(k))
         self.engine.upload_state(arrays)
+        if "scene_of" in arrays:     # the walk: each env's line map is its scene
+            self.engine.world_dev["env_map"].copy_(self.engine.state_dev["scene_of"])
 
     def _info(self):
         e = self.engine
@@ -118,8 +138,22 @@ class BatchedScenarioEnv:
                 "crash_sidewalk": bit(abi.FL_CRASH_SIDEWALK), "out_of_road": bit(abi.FL_OUT_OF_ROAD),
                 "arrive_dest": bit(abi.FL_ARRIVE_DEST), "max_step": bit(abi.FL_MAX_STEP),
                 "crash": bit(abi.FL_CRASH_VEHICLE | abi.FL_CRASH_OBJECT | abi.FL_CRASH_BUILDING | abi.FL_CRASH_SIDEWALK |
-                             abi.FL_CRASH_HUMAN)}
+                             abi.FL_CRASH_HUMAN),
+                "scenario_index": self._scenario_index}
         return LazyInfo(eager, lazy)
+
+    def _scenario_index(self):
+        """[E] int64: the dataset index each env plays in this step (step_info["scenario_index"], envs/scenario_env.py:281).  In
+        a walk the scene of the episode that this step belongs to: an env whose episode ended here has already been moved on
+        (need_reset set, walk_ep advanced), so it reports episode walk_ep - need_reset."""
+        e = self.engine
+        torch = e.torch
+        if not e.host.walk:
+            return torch.as_tensor(np.asarray(e.host.seeds, np.int64), device=e.device)
+        from metadrive_ped_amd.scenario import walk_scene
+        ep = e.state_dev["walk_ep"].view(torch.int32).cpu().numpy().astype(np.int64) - e.need_reset.cpu().numpy()
+        p = walk_scene(self.config, np.arange(self.num_envs), np.maximum(ep, 0))
+        return torch.as_tensor(int(self.config["start_scenario_index"]) + p, device=e.device)
 
     def close(self):
         self.engine = None

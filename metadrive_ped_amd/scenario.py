@@ -38,6 +38,11 @@ SCENARIO_DEFAULT_CONFIG = dict(
     out_of_route_done=False, crash_vehicle_done=False, crash_object_done=False, crash_human_done=False,
     relax_out_of_road_done=True, allowed_more_steps=None,
     map_region_size=512,          # envs/scenario_env.py:40: line bodies exist within +-256 m of the origin
+    # the scenario walk (no key of the reference's: its ScenarioEnv picks a new scenario at every reset by itself): True = every
+    # env moves on to another scenario of [start_scenario_index, + num_scenarios) whenever its episode ends (walk_scene)
+    walk_scenarios=False,
+    walk_stride=None,             # W, the envs over all shards (sharding.shard_config sets it); None: num_envs
+    scenario_pool_max_bytes=64 << 30,   # a walk's scene pool larger than this (device bytes) is refused
 )
 SCENARIO_VEHICLE_CONFIG = dict(lidar=dict(num_lasers=120, distance=50), lane_line_detector=dict(num_lasers=0, distance=50),
                                side_detector=dict(num_lasers=12, distance=50))
@@ -45,7 +50,8 @@ _ONLY_SCENARIO_KEYS = ("data_directory", "start_scenario_index", "sequential_see
                        "reactive_traffic", "filter_overlapping_car", "even_sample_vehicle_class",
                        "default_vehicle_in_traffic", "on_lane_line_penalty", "crash_human_penalty",
                        "steering_range_penalty", "heading_penalty", "lateral_penalty", "max_lateral_dist",
-                       "no_negative_reward", "crash_human_cost", "relax_out_of_road_done", "allowed_more_steps")
+                       "no_negative_reward", "crash_human_cost", "relax_out_of_road_done", "allowed_more_steps",
+                       "walk_scenarios", "walk_stride", "scenario_pool_max_bytes")
 
 STATIC_THRESHOLD = 3.0        # ScenarioTrafficManager.STATIC_THRESHOLD
 IDM_CREATE_MIN_LENGTH = 5.0   # ScenarioTrafficManager.IDM_CREATE_MIN_LENGTH
@@ -448,6 +454,40 @@ def _build_scene(job):
 
 
 
+def walk_params(cfg):
+    """(n_scenes, mode, W, offset, seed) of MdState.walk for a scenario config: mode 0 off, 1 sequential, 2 uniform"""
+    if not cfg.get("walk_scenarios"):
+        return 0, 0, 0, 0, 0
+    W = int(cfg.get("walk_stride") or cfg["num_envs"])
+    return (int(cfg["num_scenarios"]), 1 if cfg["sequential_seed"] else 2, W, int(cfg.get("env_seed_offset", 0)),
+            int(cfg.get("start_seed", 0)) & 0xFFFFFFFF)
+
+
+def _mix(z):
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def walk_scene(cfg, e, ep):
+    """The scene (index into the slice [start_scenario_index, + num_scenarios)) env e plays in episode ep of its walk
+    (0 = the first after a reset): md_walk_scene of include/md_scenario.h, restated for arrays of e / ep.
+    sequential_seed: ScenarioEnv._reset_global_seed (envs/scenario_env.py:359-380) with env e as worker
+    w = (env_seed_offset + e) % num_scenarios of W = walk_stride workers -- w, w + W, w + 2W, ... while inside the slice, then w
+    again; otherwise a draw over the slice keyed by (start_seed, env_seed_offset + e, ep)."""
+    n, walk, W, off, seed = walk_params(cfg)
+    e = np.asarray(e, np.int64)
+    ep = np.asarray(ep, np.int64)
+    if walk == 2:
+        with np.errstate(over="ignore"):
+            key = (np.uint64(seed) << np.uint64(32)) | ((off + e) & 0xFFFFFFFF).astype(np.uint64)
+            z = _mix(_mix(key) ^ ((ep & 0xFFFFFFFF).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)))
+            return (((z >> np.uint64(32)) * np.uint64(n)) >> np.uint64(32)).astype(np.int64)
+    w = (off + e) % n
+    m = (n - w + W - 1) // W
+    return w + (ep % m) * W
+
+
 class _World:
     def __init__(self, arrays, n_envs):
         self.arrays = arrays
@@ -516,20 +556,36 @@ def _poly_balls(poly_off, segs):
 
 
 class ScenarioHostScene:
-    """The HostScene of scenario mode: one scenario description per env (`scenarios[e]` -> env e)."""
+    """The HostScene of scenario mode: one scenario description per env (`scenarios[e]` -> env e), or -- with walk_scenarios --
+    the scene pool of the dataset slice (`scenarios[p]` = scenario start_scenario_index + p), every scene built once, that the
+    envs walk through (walk_scene; the device moves an env on in md_swap_draw)."""
     def __init__(self, cfg, scenarios):
         from metadrive_ped_amd.engine import make_md_config
-        from metadrive_ped_amd.scene import vehicle_param_record
-        from metadrive_ped_amd.rng import get_np_random
         self.cfg = cfg
         E = cfg["num_envs"]
-        if len(scenarios) != E:
-            raise ValueError("need one scenario per env: got {} for {} envs".format(len(scenarios), E))
+        walk = bool(cfg.get("walk_scenarios"))
+        if walk:
+            P = int(cfg["num_scenarios"])
+            if len(scenarios) != P:
+                raise ValueError("walk_scenarios: need the num_scenarios={} scenarios of the slice, got {}".format(P, len(scenarios)))
+            env_scene = [int(p) for p in walk_scene(cfg, np.arange(E), 0)]     # every env at the first scene of its walk
+        else:
+            if len(scenarios) != E:
+                raise ValueError("need one scenario per env: got {} for {} envs".format(len(scenarios), E))
+            env_scene = list(range(E))
+        S = len(scenarios)
         T = max(int(sc["length"]) for sc in scenarios)   # frames of the batch; a shorter scene is over (all invalid) after its own
         n_tracks = max(len(sc["tracks"]) for sc in scenarios)
         cap = cfg["mover_capacity"] or min(abi.MD_MAX_CAP, max(8, (n_tracks + 7) // 8 * 8))
         if n_tracks > cap:
             raise ValueError("a scenario holds {} objects, the mover capacity is {}".format(n_tracks, cap))
+        if walk:
+            # the recorded frames dominate the pool: T x scenes x cap x (MdShape + heading, speed)
+            frames = T * S * cap * (abi.SHAPE_DT.itemsize + 8)
+            if frames > int(cfg["scenario_pool_max_bytes"]):
+                raise ValueError("walk_scenarios: the pool of num_scenarios={} scenes needs {:.2f} GiB of recorded frames alone "
+                                 "(T={}, mover capacity {}), more than scenario_pool_max_bytes={:.2f} GiB: walk a smaller slice".format(
+                                     S, frames / 2 ** 30, T, cap, int(cfg["scenario_pool_max_bytes"]) / 2 ** 30))
         A = 1
         self.E, self.cap, self.A, self.T = E, cap, A, T
         vc = cfg["vehicle_config"]
@@ -542,10 +598,12 @@ class ScenarioHostScene:
         self.obs_dim = self.state_dim + self.n_beams
         # scene e <-> dataset index start_scenario_index + (env_seed_offset + e) % num_scenarios (scenario_data.scenario_indices):
         # the identity checkpoints and track sets are checked against, and the fallback parameter seed of a description that
-        # carries none -- tied to WHICH scenario it is, not to where it sits in the batch
+        # carries none -- tied to WHICH scenario it is, not to where it sits in the batch.  A walk's pool: the slice itself.
         from metadrive_ped_amd.scenario_data import scenario_indices
-        self.seeds = scenario_indices(cfg, E)
+        self.seeds = [int(cfg["start_scenario_index"]) + p for p in range(S)] if walk else scenario_indices(cfg, E)
         self.scenario_ids = [str(sc.get("id", sc.get("metadata", {}).get("scenario_id", i))) for sc, i in zip(scenarios, self.seeds)]
+        self.walk = walk
+        self.env_scene = env_scene
         self.spawn = None
         self.traffic_respawns = False
         self.scenes, self.map_tables = {}, []
@@ -554,17 +612,22 @@ class ScenarioHostScene:
 
         # vehicle parameters are sampled from a stream seeded by the scenario's OWN seed where it carries one, so that a
         # scene behaves the same in whatever batch (slot, shard) it is loaded
-        jobs = [(e, scenarios[e], cap, T, int(scenarios[e]["metadata"].get("seed", self.seeds[e])), dt, bool(cfg["no_traffic"]),
-                 float(cfg["map_region_size"])) for e in range(E)]
+        jobs = [(p, scenarios[p], cap, T, int(scenarios[p]["metadata"].get("seed", self.seeds[p])), dt, bool(cfg["no_traffic"]),
+                 float(cfg["map_region_size"])) for p in range(S)]
         from metadrive_ped_amd import hostpool
         built = hostpool.build_all(_build_scene, jobs, workers=int(cfg.get("build_workers", 0)))
-        shape0 = np.concatenate([b_["shape0"] for b_ in built])
-        dyn0 = np.concatenate([b_["dyn0"] for b_ in built])
-        param = np.concatenate([b_["param"] for b_ in built])
+        shape0 = np.concatenate([built[p]["shape0"] for p in env_scene])
+        dyn0 = np.concatenate([built[p]["dyn0"] for p in env_scene])
+        param = np.concatenate([built[p]["param"] for p in env_scene])
         nav0 = np.zeros(N, dtype=abi.NAV_DT)
         nav0["lane"], nav0["target_lane"], nav0["road0"], nav0["road1"] = -1, -1, -1, -1
         pid0 = np.zeros(N, dtype=abi.PID_DT)
         pid0["target_speed"] = 40.0
+        self.pool = None
+        if walk:   # the snapshot rows of every scene, at p * cap: what md_swap_draw copies into an env that moves on to scene p
+            self.pool = dict(shape0=np.concatenate([b_["shape0"] for b_ in built]), dyn0=np.concatenate([b_["dyn0"] for b_ in built]),
+                             nav0=np.resize(nav0[:cap], S * cap), pid0=np.resize(pid0[:cap], S * cap),
+                             param=np.concatenate([b_["param"] for b_ in built]))
         fshape = np.concatenate([b_["fshape"] for b_ in built], axis=1)
         fdyn = np.concatenate([b_["fdyn"] for b_ in built], axis=1)
         meta = np.concatenate([b_["meta"] for b_ in built])
@@ -582,7 +645,7 @@ class ScenarioHostScene:
         # static bodies: one map per scene (its road lines + their grid); the lane / road / node tables are placeholders
         from metadrive_ped_amd.mapgen.tables import WorldTables
         self.map_tables = [b_["static"] for b_ in built]
-        self.world = WorldTables(self.map_tables, list(range(E)), beam_table(self.n_beams))
+        self.world = WorldTables(self.map_tables, list(env_scene), beam_table(self.n_beams))
         a = self.world.arrays
         a["poly_off"] = np.asarray(poly_off, np.int32)
         a["segs"] = np.concatenate(segs) if sum(len(x) for x in segs) else np.zeros(1, dtype=abi.SEG_DT)
@@ -622,6 +685,9 @@ class ScenarioHostScene:
         st["done_out"] = np.zeros((E * A, 4), np.uint8)
         st["need_reset"] = np.ones(E, np.int32)
         st["next_agent_id"] = np.zeros(E, np.int32)     # ScenarioTrafficManager.idm_policy_count
+        if walk:
+            st["scene_of"] = np.asarray(env_scene, np.int32)
+            st["walk_ep"] = np.zeros(E, np.int32)
         if cfg["reactive_traffic"]:
             st["route_n"] = np.zeros((N, 4), np.int32)
             st["route_segs"] = np.zeros((N, self.route_seg_cap), dtype=abi.SEG_DT)
@@ -644,7 +710,12 @@ class ScenarioHostScene:
         k.allowed_more_steps = int(cfg["allowed_more_steps"] or 0)
         k.route_seg_cap, k.route_vert_cap = self.route_seg_cap, self.route_vert_cap
         k.ego_replay = int(cfg["agent_policy"] == "ReplayEgoCarPolicy")
+        self.walk_params = walk_params(cfg)      # MdState.walk (all 0 without the walk)
         self.md_config = k
+        if walk:
+            dev_bytes = sum(v.nbytes for v in a.values()) + fshape.nbytes + fdyn.nbytes + sum(v.nbytes for v in self.pool.values())
+            print("walk_scenarios: scene pool of num_scenarios={} scenes (T={}, mover capacity {}): {:.1f} MiB on the device".format(
+                S, T, cap, dev_bytes / 2 ** 20))
         self.side_beams = beam_table(self.n_side, np.pi / 2) if self.n_side else None
         self.ll_beams = beam_table(self.n_ll, np.pi / 2) if self.n_ll else None
 

@@ -103,8 +103,9 @@ def scenario_indices(cfg, num_envs=None):
     return [int(cfg["start_scenario_index"]) + ((off + e) % max(1, n)) for e in range(E)]
 
 
-def load_scenarios(cfg, num_envs=None):
-    """The description dicts of this batch from cfg['data_directory'] (each distinct scenario is read once)."""
+def load_scenarios(cfg, num_envs=None, pool=False):
+    """The description dicts of this batch from cfg['data_directory'] (each distinct scenario is read once); pool=True: those of
+    the whole slice [start_scenario_index, + num_scenarios) in order (the scene pool of walk_scenarios)."""
     folder = cfg["data_directory"]
     summary, names, mapping = read_dataset_summary(folder, check_file_existence=False)
     start, n = int(cfg["start_scenario_index"]), int(cfg["num_scenarios"])
@@ -114,7 +115,7 @@ def load_scenarios(cfg, num_envs=None):
         raise ValueError("Insufficient scenarios! Need: {} Has: {}".format(n, len(names) - start))
     cache = {}
     out = []
-    for i in scenario_indices(cfg, num_envs):
+    for i in (range(start, start + n) if pool else scenario_indices(cfg, num_envs)):
         if i not in cache:
             name = names[i]
             p = os.path.join(folder, mapping[name], name)

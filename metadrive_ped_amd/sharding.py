@@ -14,6 +14,8 @@ def shard_config(cfg, rank, world_size):
     """Config of rank `rank`'s shard: same scenario table, env range [rank*E, (rank+1)*E)."""
     c = copy.copy(cfg)
     c["env_seed_offset"] = cfg.get("env_seed_offset", 0) + rank * cfg["num_envs"]
+    if cfg.get("walk_scenarios") and not cfg.get("walk_stride"):    # the scenario walk: every shard's envs are workers of ONE walk
+        c["walk_stride"] = world_size * cfg["num_envs"]
     return c
 
 
