@@ -97,6 +97,18 @@ class MdWalk(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class MdCurriculum(C.Structure):
+    """include/md_curriculum.h: ScenarioEnv's curriculum manager, per env"""
+    _fields_ = [("level", P), ("seed", P), ("q_len", P), ("q_key", P), ("q_success", P), ("q_route", P), ("cover", P),
+                ("cover_n", P), ("rep_i", P), ("rep_f", P),
+                ("n_levels", C.c_int32), ("per_level", C.c_int32), ("eval", C.c_int32), ("n_scenes", C.c_int32),
+                ("stride", C.c_int32), ("offset", C.c_int32), ("cover_words", C.c_int32), ("reserved", C.c_int32),
+                ("target", C.c_double)]
+
+
+CURRICULUM_FIELDS = [f for f, t in MdCurriculum._fields_ if t is P]
+
+
 class MdState(C.Structure):
     _fields_ = [
         ("shape", P), ("dyn", P), ("param", P), ("nav", P), ("pid", P), ("action", P), ("route_nodes", P),
@@ -182,6 +194,8 @@ ENTRY_POINTS = {
 }
 # include/md_expert.h
 EXPERT_ENTRY_POINTS = {"md_expert": (_i, [_W, _S, _K, P, P, P, P, P, P])}
+# include/md_curriculum.h
+CURRICULUM_ENTRY_POINTS = {"md_curriculum": (_i, [_S, _S, _K, C.POINTER(MdCurriculum), P, _i, P])}
 # exported by diagnostic (-DMD_STAMP) builds only
 OPTIONAL_ENTRY_POINTS = {"md_debug_set_stamp_buffer": (_i, [P]), "md_debug_set_env_order": (_i, [P])}
 

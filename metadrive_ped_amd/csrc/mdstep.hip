@@ -28,6 +28,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include "md_curriculum.h"
 #include "md_expert.h"
 #include "md_scenario.h"
 
@@ -3642,6 +3643,30 @@ __global__ __launch_bounds__(256) void lidar_detect_kernel(MdWorld w, MdState g,
     for (int j = tid; j < 2 * c.agents_per_env; j += 256) detected[(size_t)e * c.agents_per_env * 2 + j] = l_det[j];
 }
 
+// The move of an env onto a staged draw / pool scene: the snapshot rows and per-slot constants of live slots [row, + cap) from
+// staged slots [from, + cap), by threads tid of nthr (swap_draw_kernel, curriculum_kernel).
+__device__ void copy_draw_rows(const MdState& live, const MdState& staged, int cap, size_t row, size_t from, int tid, int nthr) {
+    auto words = [&](void* dst, const void* src, size_t elem_words) {   // cap slots of elem_words 4-byte words each
+        if (dst == nullptr || src == nullptr) return;
+        uint32_t* d = reinterpret_cast<uint32_t*>(dst) + row * elem_words;
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(src) + from * elem_words;
+        for (size_t i = tid; i < (size_t)cap * elem_words; i += nthr) d[i] = q[i];
+    };
+    words(const_cast<MdShape*>(live.shape0), staged.shape0, sizeof(MdShape) / 4);
+    words(const_cast<MdDyn*>(live.dyn0), staged.dyn0, sizeof(MdDyn) / 4);
+    words(const_cast<MdNav*>(live.nav0), staged.nav0, sizeof(MdNav) / 4);
+    words(const_cast<MdPid*>(live.pid0), staged.pid0, sizeof(MdPid) / 4);
+    words(live.param, staged.param, sizeof(MdParam) / 4);
+    words(const_cast<MdParam*>(live.param0), staged.param, sizeof(MdParam) / 4);
+    words(live.route_nodes, staged.route_nodes, MD_ROUTE_LEN);
+    words(const_cast<int32_t*>(live.route_nodes0), staged.route_nodes, MD_ROUTE_LEN);
+    words(live.route_roads, staged.route_roads, MD_ROUTE_LEN);
+    words(const_cast<int32_t*>(live.route_roads0), staged.route_roads, MD_ROUTE_LEN);
+    words(live.final_lane, staged.final_lane, 1);
+    words(const_cast<int32_t*>(live.final_lane0), staged.final_lane, 1);
+    words(const_cast<int32_t*>(live.idm_rand), staged.idm_rand, MD_IDM_RAND);
+}
+
 // random_traffic with auto-reset (PGTrafficManager with `random_traffic`: the traffic stream is not re-seeded at reset, every episode
 // sees other traffic, manager/traffic_manager.py:335-337): the caller stages n_draws host-built traffic draws on the device; an env
 // that has just finished its episode (need_reset != 0: md_step restores it from the snapshot at the NEXT step) takes the next draw --
@@ -3666,25 +3691,37 @@ __global__ __launch_bounds__(256) void swap_draw_kernel(MdState live, MdState st
         }
     }
     const size_t row = (size_t)e * c.cap, from = walk ? (size_t)k * c.cap : ((size_t)k * c.n_envs + e) * c.cap;
-    auto words = [&](void* dst, const void* src, size_t elem_words) {   // cap slots of elem_words 4-byte words each
-        if (dst == nullptr || src == nullptr) return;
-        uint32_t* d = reinterpret_cast<uint32_t*>(dst) + row * elem_words;
-        const uint32_t* q = reinterpret_cast<const uint32_t*>(src) + from * elem_words;
-        for (size_t i = tid; i < (size_t)c.cap * elem_words; i += 256) d[i] = q[i];
-    };
-    words(const_cast<MdShape*>(live.shape0), staged.shape0, sizeof(MdShape) / 4);
-    words(const_cast<MdDyn*>(live.dyn0), staged.dyn0, sizeof(MdDyn) / 4);
-    words(const_cast<MdNav*>(live.nav0), staged.nav0, sizeof(MdNav) / 4);
-    words(const_cast<MdPid*>(live.pid0), staged.pid0, sizeof(MdPid) / 4);
-    words(live.param, staged.param, sizeof(MdParam) / 4);
-    words(const_cast<MdParam*>(live.param0), staged.param, sizeof(MdParam) / 4);
-    words(live.route_nodes, staged.route_nodes, MD_ROUTE_LEN);
-    words(const_cast<int32_t*>(live.route_nodes0), staged.route_nodes, MD_ROUTE_LEN);
-    words(live.route_roads, staged.route_roads, MD_ROUTE_LEN);
-    words(const_cast<int32_t*>(live.route_roads0), staged.route_roads, MD_ROUTE_LEN);
-    words(live.final_lane, staged.final_lane, 1);
-    words(const_cast<int32_t*>(live.final_lane0), staged.final_lane, 1);
-    words(const_cast<int32_t*>(live.idm_rand), staged.idm_rand, MD_IDM_RAND);
+    copy_draw_rows(live, staged, c.cap, row, from, tid, 256);
+}
+
+// ScenarioEnv's curriculum manager (include/md_curriculum.h), one wave per env: lane 0 runs the env's state machine, and when the
+// env moves on (n_levels > 1) the whole wave copies the new scene's snapshot rows from the pool (`staged`, scene p at p * cap).
+// reset = 1: an env reset (every env restarts at its worker's first scene of its level; no report, no put).
+__global__ __launch_bounds__(64) void curriculum_kernel(MdState live, MdState staged, MdConfig c, MdCurriculum cu, int32_t* env_map,
+                                                        int reset) {
+    const int e = blockIdx.x;
+    if (e >= c.n_envs) return;
+    const int lane = threadIdx.x;
+    const bool moves = cu.n_levels > 1;
+    int p = -1;
+    if (lane == 0) {
+        const int follow = moves ? -1 : live.scene_of[e];   // one level: md_swap_draw has moved the env already
+        if (reset) {
+            p = md_cur_restart(&cu, e, follow);
+        } else {
+            const size_t a = (size_t)e * c.agents_per_env;
+            const int success = (live.flags[(size_t)e * c.cap] & MD_FL_ARRIVE_DEST) != 0;
+            p = md_cur_after_step(&cu, e, success, live.step_info[8 * a + 6], live.need_reset[e] != 0, follow);
+        }
+    }
+    p = __shfl(p, 0);
+    if (!moves || p < 0) return;   // wave-uniform
+    if (lane == 0) {
+        live.scene_of[e] = p;
+        live.walk_ep[e] = reset ? 0 : live.walk_ep[e] + 1;
+        env_map[e] = p;
+    }
+    copy_draw_rows(live, staged, c.cap, (size_t)e * c.cap, (size_t)p * c.cap, lane, 64);
 }
 
 // "Others" block of the observation (Lidar.get_surrounding_vehicles_info): one thread per agent, after the
@@ -4205,6 +4242,48 @@ __attribute__((visibility("default"))) int md_swap_draw(const MdState* s, const 
         }
     }
     hipLaunchKernelGGL(swap_draw_kernel, dim3(c->n_envs), dim3(256), 0, (hipStream_t)stream, *s, *staged, *c, n_draws, draw_idx);
+    return launch_status();
+}
+
+// include/md_curriculum.h
+__attribute__((visibility("default"))) int md_curriculum(const MdState* s, const MdState* staged, const MdConfig* c,
+                                                         const MdCurriculum* cu, int32_t* env_map, int reset, void* stream) {
+    if (!s || !staged || !c || !cu || !env_map) {
+        snprintf(g_err, sizeof g_err, "md_curriculum: null MdState / staged MdState / MdConfig / MdCurriculum / env_map");
+        return MD_EINVAL;
+    }
+    TRY(check_struct_size(c));
+    if (c->n_envs <= 0 || c->cap <= 0 || c->cap > MD_MAX_CAP || c->agents_per_env != 1 || c->traffic_mode != 4) {
+        snprintf(g_err, sizeof g_err, "md_curriculum: a single-agent scenario batch is required (n_envs=%d cap=%d agents=%d "
+                 "traffic_mode=%d)", c->n_envs, c->cap, c->agents_per_env, c->traffic_mode);
+        return MD_EINVAL;
+    }
+    const MdWalk& wk = s->walk;
+    if (wk.mode == 0 || wk.n_scenes != cu->n_scenes || wk.stride != cu->stride || wk.offset != cu->offset || !s->scene_of ||
+        !s->walk_ep || !s->need_reset || !s->flags || !s->step_info) {
+        snprintf(g_err, sizeof g_err, "md_curriculum: needs the scenario walk (MdState.walk mode %d, n_scenes %d / %d, stride %d / %d, "
+                 "offset %d / %d), MdState.scene_of / walk_ep / need_reset / flags / step_info", wk.mode, wk.n_scenes, cu->n_scenes,
+                 wk.stride, cu->stride, wk.offset, cu->offset);
+        return MD_EINVAL;
+    }
+    if (cu->n_levels < 1 || cu->n_scenes < 1 || cu->per_level * cu->n_levels != cu->n_scenes || cu->eval < 1 || cu->stride < 1 ||
+        cu->offset < 0 || cu->cover_words != (cu->n_scenes + 31) / 32 || (cu->n_levels > 1 && wk.mode != 1)) {
+        snprintf(g_err, sizeof g_err, "md_curriculum: n_levels=%d per_level=%d n_scenes=%d eval=%d stride=%d offset=%d cover_words=%d "
+                 "walk mode %d (levels > 1 need the sequential walk)", cu->n_levels, cu->per_level, cu->n_scenes, cu->eval, cu->stride,
+                 cu->offset, cu->cover_words, wk.mode);
+        return MD_EINVAL;
+    }
+    if (!cu->level || !cu->seed || !cu->q_len || !cu->q_key || !cu->q_success || !cu->q_route || !cu->cover || !cu->cover_n ||
+        !cu->rep_i || !cu->rep_f) {
+        snprintf(g_err, sizeof g_err, "md_curriculum: every MdCurriculum array is required");
+        return MD_EINVAL;
+    }
+    if (cu->n_levels > 1 && (!s->shape0 || !s->dyn0 || !s->nav0 || !s->pid0 || !staged->shape0 || !staged->dyn0 || !staged->nav0 ||
+                             !staged->pid0)) {
+        snprintf(g_err, sizeof g_err, "md_curriculum: the snapshot arrays shape0 / dyn0 / nav0 / pid0 (live and staged) are required");
+        return MD_EINVAL;
+    }
+    hipLaunchKernelGGL(curriculum_kernel, dim3(c->n_envs), dim3(64), 0, (hipStream_t)stream, *s, *staged, *c, *cu, env_map, reset);
     return launch_status();
 }
 

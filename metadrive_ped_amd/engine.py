@@ -515,6 +515,17 @@ class BatchedEngine:
             self._n_draws = int(h.walk_params[0])
         elif self._staged is not None:
             self._n_draws = len(self.draw_hosts_)
+        # the curriculum of a walk (include/md_curriculum.h): md_curriculum after every step; with more than one level it moves
+        # the envs itself, instead of md_swap_draw
+        self._cur = None
+        if self._walk:
+            L, per, Q, target = h.curriculum
+            n, _, W, off, _ = h.walk_params
+            cu = abi.MdCurriculum()
+            abi.fill_struct(cu, abi.CURRICULUM_FIELDS, {f: self.state_dev["cur_" + f] for f in abi.CURRICULUM_FIELDS}, ptr)
+            cu.n_levels, cu.per_level, cu.eval, cu.n_scenes, cu.stride, cu.offset = L, per, Q, n, W, off
+            cu.cover_words, cu.target = (n + 31) // 32, target
+            self._cur = cu
         sd = self.state_dev
         # typed views for the env API
         self.obs = sd["obs"].view(torch.float32).view(self.E, self.A, self.obs_dim)
@@ -573,8 +584,15 @@ class BatchedEngine:
         if self._walk:     # every env back to the first scene of its walk (episode 0), then the reset step
             self.state_dev["walk_ep"].view(self.torch.int32).fill_(-1)
             with self._on_device():
-                self._swap()
+                if self._cur is None or self._cur.n_levels == 1:
+                    self._swap()
+                if self._cur is not None:
+                    self._curriculum(1)     # the level check; more than one level: the first scene of the env's level
         self.step_raw()
+
+    def _curriculum(self, reset):
+        self._check(self.lib.md_curriculum(C.byref(self.s), C.byref(self._staged), C.byref(self.k), C.byref(self._cur),
+                                           C.c_void_p(self.draw_idx.data_ptr()), int(reset), self._stream()), "md_curriculum")
 
     def _swap(self):
         self._check(self.lib.md_swap_draw(C.byref(self.s), C.byref(self._staged), C.byref(self.k), self._n_draws,
@@ -589,7 +607,11 @@ class BatchedEngine:
 
     def _step_raw(self):
         self._check(self.lib.md_step(C.byref(self.w), C.byref(self.s), C.byref(self.k), self._stream()), "md_step")
-        if self._staged is not None:     # random_traffic / the scenario walk: the envs whose episode just ended get the next draw
+        if self._cur is not None:        # the scenario walk: the curriculum's step, and the envs whose episode just ended move on
+            if self._cur.n_levels == 1:
+                self._swap()
+            self._curriculum(0)
+        elif self._staged is not None:   # random_traffic: the envs whose episode just ended get the next draw
             self._swap()
         h = self.host
         vc = self.cfg["vehicle_config"]

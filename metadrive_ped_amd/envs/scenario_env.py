@@ -19,7 +19,15 @@ scene (md_swap_draw), so a walk step costs what a fixed-scene step does.  The or
   sequential_seed=False: a uniform draw over the slice per (env, episode), from a stream keyed by start_seed and the global env
     index -- reproducible, where the reference's draw is unseeded.
 reset() starts every env again at the first scenario of its walk; get_state() / set_state() carry each env's scene and walk
-position (MdState.scene_of / walk_ep) with the rest of the state."""
+position (MdState.scene_of / walk_ep) with the rest of the state.
+
+The curriculum of a walk (ScenarioEnv's curriculum manager, one per env as one per worker in the reference): curriculum_level=L > 1
+sorts the slice by difficulty (scenario.difficulty_score) and splits it into L windows of num_scenarios / L; each env plays its
+worker's scenarios of its window and moves one window up at an episode end once its recent success rate reaches
+target_success_rate (include/md_curriculum.h, md_curriculum after every step).  Walk batches report curriculum_level,
+scenario_difficulty, data_coverage, curriculum_success and curriculum_route_completion as [E] tensors; with L > 1
+scenario_index is the position in the sorted slice.  reset() keeps levels, queues and coverage and restarts each env at its
+worker's first scenario of its level."""
 import numpy as np
 
 from metadrive_ped_amd import abi
@@ -140,7 +148,20 @@ class BatchedScenarioEnv:
                 "crash": bit(abi.FL_CRASH_VEHICLE | abi.FL_CRASH_OBJECT | abi.FL_CRASH_BUILDING | abi.FL_CRASH_SIDEWALK |
                              abi.FL_CRASH_HUMAN),
                 "scenario_index": self._scenario_index}
+        if e.host.walk:     # the curriculum's keys (envs/scenario_env.py:279-285), as md_curriculum reported them for this step
+            torch = e.torch
+            rep_i = e.state_dev["cur_rep_i"].view(torch.int32).view(self.num_envs, 2)
+            rep_f = e.state_dev["cur_rep_f"].view(torch.float64).view(self.num_envs, 3)
+            eager.update(curriculum_level=rep_i[:, 0], curriculum_success=rep_f[:, 0], curriculum_route_completion=rep_f[:, 1],
+                         data_coverage=rep_f[:, 2])
+            lazy["scenario_difficulty"] = lambda: self._difficulty()[rep_i[:, 1].long()]
         return LazyInfo(eager, lazy)
+
+    def _difficulty(self):
+        e = self.engine
+        if getattr(e, "_difficulty_dev", None) is None:
+            e._difficulty_dev = e.torch.as_tensor(e.host.difficulty, device=e.device)
+        return e._difficulty_dev
 
     def _scenario_index(self):
         """[E] int64: the dataset index each env plays in this step (step_info["scenario_index"], envs/scenario_env.py:281).  In
@@ -150,6 +171,9 @@ class BatchedScenarioEnv:
         torch = e.torch
         if not e.host.walk:
             return torch.as_tensor(np.asarray(e.host.seeds, np.int64), device=e.device)
+        if e.host.curriculum[0] > 1:    # engine.current_seed: the position in the difficulty-sorted slice
+            seed = e.state_dev["cur_rep_i"].view(torch.int32).view(self.num_envs, 2)[:, 1]
+            return seed.long() + int(self.config["start_scenario_index"])
         from metadrive_ped_amd.scenario import walk_scene
         ep = e.state_dev["walk_ep"].view(torch.int32).cpu().numpy().astype(np.int64) - e.need_reset.cpu().numpy()
         p = walk_scene(self.config, np.arange(self.num_envs), np.maximum(ep, 0))

@@ -43,6 +43,8 @@ SCENARIO_DEFAULT_CONFIG = dict(
     walk_scenarios=False,
     walk_stride=None,             # W, the envs over all shards (sharding.shard_config sets it); None: num_envs
     scenario_pool_max_bytes=64 << 30,   # a walk's scene pool larger than this (device bytes) is refused
+    # ScenarioEnv's curriculum (envs/scenario_env.py:31-33), per env of a walk (include/md_curriculum.h, curriculum_params)
+    curriculum_level=1, episodes_to_evaluate_curriculum=None, target_success_rate=0.8,
 )
 SCENARIO_VEHICLE_CONFIG = dict(lidar=dict(num_lasers=120, distance=50), lane_line_detector=dict(num_lasers=0, distance=50),
                                side_detector=dict(num_lasers=12, distance=50))
@@ -51,7 +53,8 @@ _ONLY_SCENARIO_KEYS = ("data_directory", "start_scenario_index", "sequential_see
                        "default_vehicle_in_traffic", "on_lane_line_penalty", "crash_human_penalty",
                        "steering_range_penalty", "heading_penalty", "lateral_penalty", "max_lateral_dist",
                        "no_negative_reward", "crash_human_cost", "relax_out_of_road_done", "allowed_more_steps",
-                       "walk_scenarios", "walk_stride", "scenario_pool_max_bytes")
+                       "walk_scenarios", "walk_stride", "scenario_pool_max_bytes", "curriculum_level",
+                       "episodes_to_evaluate_curriculum", "target_success_rate")
 
 STATIC_THRESHOLD = 3.0        # ScenarioTrafficManager.STATIC_THRESHOLD
 IDM_CREATE_MIN_LENGTH = 5.0   # ScenarioTrafficManager.IDM_CREATE_MIN_LENGTH
@@ -96,7 +99,63 @@ def make_scenario_config(user=None):
         cfg["agent_policy"] = "ReplayEgoCarPolicy"
     if cfg["agent_policy"] == "IDMPolicy":
         raise NotImplementedError("agent_policy=IDMPolicy needs a road network: not in BatchedScenarioEnv (EnvInputPolicy, ReplayEgoCarPolicy)")
+    curriculum_params(cfg)
     return cfg
+
+
+def curriculum_params(cfg):
+    """(n_levels, per_level, eval per worker, target) of a scenario config's curriculum, with the reference's refusals
+    (envs/scenario_env.py:104-114, manager/scenario_curriculum_manager.py:41-55).  The workers are the walk's W envs.
+    One level and the default window, where the reference would refuse a window that W does not divide: ceil(num_scenarios / W)."""
+    L = int(cfg.get("curriculum_level", 1))
+    N = int(cfg["num_scenarios"])
+    W = int(cfg.get("walk_stride") or cfg["num_envs"])
+    ev = cfg.get("episodes_to_evaluate_curriculum")
+    if L < 1:
+        raise ValueError("Curriculum Level should be greater than 1")
+    if L > 1:
+        if not cfg.get("walk_scenarios"):
+            raise ValueError("curriculum_level > 1 needs walk_scenarios=True: without the walk an env never moves to another scenario")
+        if N % L != 0:
+            raise ValueError("Each level should have the same number of scenarios")
+        if W > 1 and (N // L) % W != 0:
+            raise ValueError("the {} scenarios per level must be divisible by num_workers (walk_stride) {}".format(N // L, W))
+        if not cfg["sequential_seed"]:
+            raise ValueError("Sort and sequential seed is required for curriculum seed")
+    if ev is None and L == 1 and N % W != 0:
+        return 1, N, -(-N // W), float(cfg.get("target_success_rate", 0.8))
+    ev = int(N / L) if ev is None else int(ev)
+    if ev == 0:
+        raise ValueError("episodes_to_evaluate_curriculum can not be 0")
+    if ev % W != 0:
+        raise ValueError("Can not be divisible by num_workers")
+    return L, N // L, ev // W, float(cfg.get("target_success_rate", 0.8))
+
+
+def difficulty_score(sc):
+    """ScenarioDataManager.sort_scenarios' _score (manager/scenario_data_manager.py:146-162): the SDC's moving distance times
+    1 + the summed absolute heading changes between its consecutive valid positions over pi (the object weight is 0).  The
+    distance comes from the metadata's object summary, or from the track (ScenarioDescription.sdc_moving_dist, :504-525)."""
+    meta = sc["metadata"]
+    sdc = meta["sdc_id"]
+    st = sc["tracks"][sdc]["state"]
+    xy = np.asarray(st["position"])[np.where(np.asarray(st["valid"]).astype(int))][..., :2]
+    d = xy[1:] - xy[:-1]
+    h = np.arctan2(d[..., 1], d[..., 0])
+    curvature = sum(abs(h[1:] - h[:-1]) / np.pi) + 1
+    info = (meta.get("object_summary") or {}).get(sdc) or {}
+    if "moving_distance" in info:
+        dist = info["moving_distance"]
+    else:
+        dist = float(sum(np.linalg.norm(xy[i] - xy[i + 1]) for i in range(xy.shape[0] - 1)))
+    return dist * curvature
+
+
+def sort_by_difficulty(scenarios):
+    """(the slice in ascending difficulty, stable; the scores in that order; the original positions): the curriculum's pool"""
+    scores = [difficulty_score(sc) for sc in scenarios]
+    order = sorted(range(len(scenarios)), key=lambda i: scores[i])
+    return [scenarios[i] for i in order], [float(scores[i]) for i in order], order
 
 
 class PolyLine:
@@ -564,11 +623,21 @@ class ScenarioHostScene:
         self.cfg = cfg
         E = cfg["num_envs"]
         walk = bool(cfg.get("walk_scenarios"))
+        self.curriculum, self.difficulty = None, None
+        order = None
         if walk:
             P = int(cfg["num_scenarios"])
             if len(scenarios) != P:
                 raise ValueError("walk_scenarios: need the num_scenarios={} scenarios of the slice, got {}".format(P, len(scenarios)))
             env_scene = [int(p) for p in walk_scene(cfg, np.arange(E), 0)]     # every env at the first scene of its walk
+            # the curriculum: the slice sorted by difficulty before the pool is built (ScenarioDataManager.sort_scenarios runs
+            # with more than one level only; scenario_difficulty is 0 otherwise)
+            self.curriculum = curriculum_params(cfg)
+            if self.curriculum[0] > 1:
+                scenarios, diff, order = sort_by_difficulty(scenarios)
+                self.difficulty = np.asarray(diff, np.float64)
+            else:
+                self.difficulty = np.zeros(P, np.float64)
         else:
             if len(scenarios) != E:
                 raise ValueError("need one scenario per env: got {} for {} envs".format(len(scenarios), E))
@@ -612,7 +681,8 @@ class ScenarioHostScene:
 
         # vehicle parameters are sampled from a stream seeded by the scenario's OWN seed where it carries one, so that a
         # scene behaves the same in whatever batch (slot, shard) it is loaded
-        jobs = [(p, scenarios[p], cap, T, int(scenarios[p]["metadata"].get("seed", self.seeds[p])), dt, bool(cfg["no_traffic"]),
+        fallback = self.seeds if order is None else [int(cfg["start_scenario_index"]) + i for i in order]   # the dataset index
+        jobs = [(p, scenarios[p], cap, T, int(scenarios[p]["metadata"].get("seed", fallback[p])), dt, bool(cfg["no_traffic"]),
                  float(cfg["map_region_size"])) for p in range(S)]
         from metadrive_ped_amd import hostpool
         built = hostpool.build_all(_build_scene, jobs, workers=int(cfg.get("build_workers", 0)))
@@ -688,6 +758,18 @@ class ScenarioHostScene:
         if walk:
             st["scene_of"] = np.asarray(env_scene, np.int32)
             st["walk_ep"] = np.zeros(E, np.int32)
+            # the curriculum's per-env state (include/md_curriculum.h MdCurriculum); every env starts at level 0, no seed yet
+            Q, CW = self.curriculum[2], (S + 31) // 32
+            st["cur_level"] = np.zeros(E, np.int32)
+            st["cur_seed"] = np.full(E, -1, np.int32)
+            st["cur_q_len"] = np.zeros(E, np.int32)
+            st["cur_q_key"] = np.full((E, Q), -1, np.int32)
+            st["cur_q_success"] = np.zeros((E, Q), np.int32)
+            st["cur_q_route"] = np.zeros((E, Q), np.float32)
+            st["cur_cover"] = np.zeros((E, CW), np.uint32)
+            st["cur_cover_n"] = np.zeros(E, np.int32)
+            st["cur_rep_i"] = np.zeros((E, 2), np.int32)
+            st["cur_rep_f"] = np.zeros((E, 3), np.float64)
         if cfg["reactive_traffic"]:
             st["route_n"] = np.zeros((N, 4), np.int32)
             st["route_segs"] = np.zeros((N, self.route_seg_cap), dtype=abi.SEG_DT)

@@ -1,14 +1,16 @@
 #!/usr/bin/env python
-"""Time a scenario step with the scenario walk off and on, on the same scenes: md_step (+ md_swap_draw when the walk is on) of
+"""Time a scenario step with the scenario walk off and on, on the same scenes: md_step (+ md_swap_draw + md_curriculum when the walk is on) of
 the bench.py scenario workload (reactive traffic, 240-beam lidar, side detector) at 2048 envs over a pool of --scenes synthetic
 scenarios.  Walk off: env e plays scene e % scenes for good (one built scene per env); walk on: the pool, each scene built
-once, the envs moving on as their episodes end.  Prints one JSON line per mode: us per step (torch events around --steps
+once, the envs moving on as their episodes end.  on-nocur: the walk without the md_curriculum launch (what a walk step cost before
+the curriculum); curriculum: two curriculum levels (walk_stride = scenes / 2), md_curriculum moving the envs instead of
+md_swap_draw.  Prints one JSON line per mode: us per step (torch events around --steps
 back-to-back steps after --warmup), and how many env resets fell inside the timed window.
 
 The swap kernel alone: run under `rocprofv3 --kernel-trace --stats -- python tools/walk_bench.py --modes on` and read the
 swap_draw_kernel row of the stats.
 
-    python tools/walk_bench.py [--envs 2048] [--scenes 64] [--steps 200] [--warmup 20] [--modes off,on] [--out FILE]
+    python tools/walk_bench.py [--envs 2048] [--scenes 64] [--steps 200] [--warmup 20] [--modes off,on,on-nocur,curriculum] [--out FILE]
 """
 import argparse
 import json
@@ -25,12 +27,15 @@ def run(mode, args, pool):
     from metadrive_ped_amd.envs.scenario_env import scenario_bench_config
     from metadrive_ped_amd.scenario import ScenarioHostScene
     E, n = args.envs, args.scenes
-    walk = mode == "on"
+    walk = mode != "off"
+    cur = dict(curriculum_level=2, walk_stride=n // 2, target_success_rate=0.5) if mode == "curriculum" else {}
     cfg = scenario_bench_config(dict(num_envs=E, num_scenarios=n if walk else E, walk_scenarios=walk, sequential_seed=True,
-                                     horizon=args.horizon, device="cuda:0"))
+                                     horizon=args.horizon, device="cuda:0", **cur))
     scenes = pool if walk else [pool[e % n] for e in range(E)]
     host = ScenarioHostScene(cfg, scenes)
     eng = BatchedEngine(cfg, host=host)
+    if mode == "on-nocur":     # the one-level walk without md_curriculum: md_step + md_swap_draw alone
+        eng._cur = None
     eng.reset()
     actions = torch.zeros((E, 2), dtype=torch.float32, device=eng.device)
     actions[:, 1] = 0.2
