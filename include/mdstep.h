@@ -33,6 +33,11 @@ extern "C" {
 
 #define MD_ABI_VERSION 12
 
+/* ---- MdConfig.agent_idm: the agents' policy on the device ---------------------------------- */
+#define MD_AGENT_INPUT 0
+#define MD_AGENT_IDM 1
+#define MD_AGENT_LANE_CHANGE 2
+
 /* ---- error codes ------------------------------------------------------------------------- */
 #define MD_OK 0
 #define MD_EINVAL (-1)   /* bad argument (null pointer, non-positive size, cap too large ...) */
@@ -444,9 +449,14 @@ typedef struct MdConfig {
     int32_t add_others_navi;   /* vehicle_config.lidar.add_others_navi                            */
     int32_t track_len;         /* frames in MdState.track_* (traffic_mode 3); later steps hold the last frame */
     int32_t random_agent_model;/* 1: two extra leading obs dims, length / 10 and width / 2.5 (obs/state_obs.py:70-75) */
-    int32_t agent_idm;         /* 1: config agent_policy = IDMPolicy (envs/base_env.py:53, manager/agent_manager.py:37-70): the
-                                * agents are driven by the IDM / PID policy of the traffic; MdState.agent_action is not read.
-                                * Single-agent envs only. */
+    int32_t agent_idm;         /* the agents' policy on the device (config agent_policy, envs/base_env.py:53,
+                                * manager/agent_manager.py:37-70): MD_AGENT_INPUT (0) = the caller's actions as they are;
+                                * MD_AGENT_IDM (1) = IDMPolicy: the agents are driven by the IDM / PID policy of the traffic,
+                                * MdState.agent_action is not read (single-agent envs only); MD_AGENT_LANE_CHANGE (2) =
+                                * LaneChangePolicy (include/md_lane_change.h): the caller's decoded discrete action chooses
+                                * left / keep / right (steering +1 / 0 / -1) and the throttle, and the steering is replaced by
+                                * the lane-change PIDs' output, their state in the agents' MdPid rows (single- and multi-agent
+                                * envs; not in scenario mode).  md_step refuses other values. */
     int32_t enable_reverse;    /* vehicle_config.enable_reverse: an agent's negative throttle drives it backwards instead of
                                 * braking (base_vehicle.py:476-484) */
     /* scenario mode (traffic_mode 4): ScenarioEnv reward / cost / termination scheme (envs/scenario_env.py:21-95) */

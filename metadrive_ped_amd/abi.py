@@ -16,6 +16,8 @@ MD_MAX_CAP = 128
 MD_MAX_BEAMS = 1024
 MD_ROUTE_LEN = 48
 MD_IDM_RAND = 8
+# MdConfig.agent_idm: the agents' policy on the device
+AGENT_INPUT, AGENT_IDM, AGENT_LANE_CHANGE = 0, 1, 2
 
 # mover kinds / flags
 KIND_NONE, KIND_VEHICLE, KIND_CONE, KIND_WARNING, KIND_BARRIER, KIND_PEDESTRIAN, KIND_CYCLIST, KIND_BUILDING = range(8)

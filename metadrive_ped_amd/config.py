@@ -22,7 +22,7 @@ BASE_DEFAULT_CONFIG = dict(
     allow_respawn=False,
     delay_done=0,
     # ===== action =====
-    agent_policy="EnvInputPolicy",   # or "IDMPolicy" / "ExpertPolicy" (the class of that name is accepted too): envs/base_env.py:53
+    agent_policy="EnvInputPolicy",   # or "IDMPolicy" / "ExpertPolicy" / "LaneChangePolicy" (the class of that name is accepted too): envs/base_env.py:53
     discrete_action=False,
     use_multi_discrete=False,
     discrete_steering_dim=5,
@@ -249,10 +249,13 @@ def make_config(user=None):
     # agent_policy: the reference takes a policy CLASS; here its name (or a class of that name)
     pol = cfg["agent_policy"]
     pol = pol if isinstance(pol, str) else getattr(pol, "__name__", repr(pol))
-    if pol not in ("EnvInputPolicy", "IDMPolicy", "ExpertPolicy"):
-        raise NotImplementedError("agent_policy={!r}: built are EnvInputPolicy (actions from step()), IDMPolicy, ExpertPolicy and, "
-                                  "in BatchedScenarioEnv only, ReplayEgoCarPolicy".format(pol))
+    if pol not in ("EnvInputPolicy", "IDMPolicy", "ExpertPolicy", "LaneChangePolicy"):
+        raise NotImplementedError("agent_policy={!r}: built are EnvInputPolicy (actions from step()), IDMPolicy, ExpertPolicy, "
+                                  "LaneChangePolicy and, in BatchedScenarioEnv only, ReplayEgoCarPolicy".format(pol))
     cfg["agent_policy"] = pol
+    if pol == "LaneChangePolicy":
+        # LaneChangePolicy.__init__ (policy/lange_change_policy.py:16)
+        assert cfg["discrete_action"], "Must set discrete_action=True for using this control policy"
     if pol == "ExpertPolicy":
         problem = expert_config_problem(cfg)
         if problem:

@@ -1734,7 +1734,7 @@ __device__ __forceinline__ void lifecycle_block(const MdWorld& w, const MdState&
                     nav->done = 0;
                     nav->toll_state = nav->toll_entry = nav->toll_exit = 0;
                     nav->toll_entry = space;
-                    md_agent_idm_init(&s, &c, slot);
+                    md_agent_policy_init(&s, &c, slot);
                     if (c.random_agent_model && w.n_vclass > 0) md_draw_vehicle_class(&w, &s, slot);
                     s.final_lane[slot] = w.spawn_route_meta[2 * ri + 1];
                     *new_slot = slot;
@@ -2087,7 +2087,10 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     // agent_policy = IDMPolicy (single-agent envs): the agents are planned like the traffic, in the reference's order
     // (decide, then move): the observation reports the action applied in THIS step.  Never in the lean fused variant:
     // the launcher sends such configs to the RESPAWN one.
-    const bool agent_idm = (kFused && !RESPAWN && !MULTI) ? false : (c.agent_idm != 0);
+    const bool agent_idm = (kFused && !RESPAWN && !MULTI) ? false : (c.agent_idm == MD_AGENT_IDM);
+    // agent_policy = LaneChangePolicy: each agent's decoded action is turned into the lane-change PIDs' steering just before it
+    // is integrated (md_lane_change_act, same thread as the integration).  Only the RESPAWN and MULTI variants carry the code.
+    const bool lane_change = (RESPAWN || MULTI) && c.agent_idm == MD_AGENT_LANE_CHANGE;
     constexpr bool kPlanAhead = kFused && kWaves > 1 && !MULTI;
     const bool plan_ahead = kPlanAhead && !agent_idm;
     if ((PH & PH_IDM) && !just_reset && !plan_ahead) {
@@ -2103,6 +2106,10 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     MD_STAMP_AT(3);
     if ((PH & PH_INTEGRATE) && !just_reset) {
         for (int j = tid; j < cap; j += kBlock) {
+            if (lane_change && j < c.agents_per_env) {
+                const int f = s.shape[j].flags;   // not on the step the slot was (re)spawned: it is not integrated then
+                if (md_drives(f) && !(f & MD_F_SPAWNED)) md_lane_change_act(lanes, roads, &s, j);
+            }
             if (RESPAWN) md_advance_mover(&s, &c, j);  // the non-trigger traffic modes' kernel (respawn / hybrid / replay)
             else md_integrate_mover(&s, &c, j);
         }
@@ -2274,7 +2281,8 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
             copy16(gv.param, l_param, cap * (int)sizeof(MdParam), tid, kBlock);   // a respawn / reset rewrote vehicle classes
         if ((PH & (PH_RESET | PH_INTEGRATE | PH_LIFECYCLE)) || respawns) copy16(gv.dyn, l_dyn, cap * (int)sizeof(MdDyn), tid, kBlock);
         if ((PH & (PH_RESET | PH_IDM | PH_LOCALIZE | PH_OBSERVE | PH_LIFECYCLE)) || respawns) copy16(gv.nav, l_nav, cap * (int)sizeof(MdNav), tid, kBlock);
-        if ((PH & (PH_RESET | PH_IDM | PH_OBSERVE | PH_LIFECYCLE)) || respawns) copy16(gv.pid, l_pid, cap * (int)sizeof(MdPid), tid, kBlock);
+        if ((PH & (PH_RESET | PH_IDM | PH_OBSERVE | PH_LIFECYCLE)) || respawns || (lane_change && (PH & PH_INTEGRATE)))
+            copy16(gv.pid, l_pid, cap * (int)sizeof(MdPid), tid, kBlock);
         if (((PH & (PH_RESET | PH_LIFECYCLE)) && MULTI) || ((PH & (PH_RESET | PH_TRAFFIC)) && RESPAWN)) {
             for (int j = tid; j < cap; j += kBlock) gv.final_lane[j] = l_final[j];
         }
@@ -2470,8 +2478,9 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
 
     // agent_policy = IDMPolicy: the agents are planned like the traffic, in the reference's order (decide, then move);
     // otherwise the traffic is planned one step AHEAD, at the end of the step (see env_kernel)
-    const bool agent_idm = RESPAWN && c.agent_idm != 0;
+    const bool agent_idm = RESPAWN && c.agent_idm == MD_AGENT_IDM;
     const bool plan_ahead = !agent_idm;
+    const bool lane_change = RESPAWN && c.agent_idm == MD_AGENT_LANE_CHANGE;   // LaneChangePolicy: see env_kernel
     if (!just_reset && !plan_ahead) {
         trigger_env(lanes, s, c, lane);
         wave_sync();
@@ -2488,6 +2497,10 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
     const unsigned long long drv_lo = drv.lo, drv_hi = drv.hi;
     if (!just_reset) {
         for (int j = lane; j < cap; j += 64) {
+            if (lane_change && j < A) {
+                const int f = s.shape[j].flags;
+                if (md_drives(f) && !(f & MD_F_SPAWNED)) md_lane_change_act(lanes, roads, &s, j);
+            }
             if (RESPAWN) md_advance_mover(&s, &c, j);
             else md_integrate_mover(&s, &c, j);
         }
@@ -4038,6 +4051,7 @@ Variant variant(const MdWorld* w, const MdState* s, const MdConfig* c) {
     v.wave = PH == PH_ALL && !c->is_multi_agent && c->step_kernel == 1;
     v.stage = w->max_lanes <= kStageMaxLanes;
     v.multi = (PH & (PH_LIFECYCLE | PH_RESET)) && c->is_multi_agent;
+    // agent_idm != 0: IDMPolicy and LaneChangePolicy agents are driven by code that only this variant (and MULTI) carries
     v.respawn = !v.multi && (PH & (PH_TRAFFIC | PH_RESET | PH_INTEGRATE)) &&
                 (c->traffic_mode != 0 || c->agent_idm != 0 || (PH == PH_ALL && s->detected != nullptr));
     // Multi-agent md_step: eight waves per env while every workgroup of the batch is resident at once at that size (the MULTI
@@ -4313,6 +4327,15 @@ MD_PHASE_ENTRY(md_lifecycle, PH_LIFECYCLE)
 
 __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdState* s, const MdConfig* c, void* stream) {
     TRY(check_phase(PH_ALL, w, s, c));
+    if (c->agent_idm < MD_AGENT_INPUT || c->agent_idm > MD_AGENT_LANE_CHANGE) {
+        snprintf(g_err, sizeof g_err, "agent_idm=%d: 0 (the caller's actions), 1 (IDMPolicy) or 2 (LaneChangePolicy)", c->agent_idm);
+        return MD_EINVAL;
+    }
+    if (c->agent_idm == MD_AGENT_LANE_CHANGE && c->traffic_mode == 4) {
+        snprintf(g_err, sizeof g_err, "agent_idm=2 (LaneChangePolicy) steers along the road network's lanes: not in scenario mode "
+                 "(traffic_mode 4)");
+        return MD_EINVAL;
+    }
     if (c->traffic_mode == 4) {   // scenario mode: its own kernel (ScenarioEnv step)
         TRY(need_fields(PH_ALL, SCENARIO, w, s, c));
         if (c->is_multi_agent || c->agents_per_env != 1 || c->track_len <= 0) {

@@ -320,7 +320,8 @@ class HostScene:
         self.md_config.n_side, self.md_config.n_lane_line = self.n_side, self.n_ll
         self.md_config.num_others, self.md_config.add_others_navi = self.num_others, int(self.add_others_navi)
         self.md_config.random_agent_model = int(bool(cfg["random_agent_model"]))
-        self.md_config.agent_idm = int(cfg["agent_policy"] == "IDMPolicy")
+        self.md_config.agent_idm = {"IDMPolicy": abi.AGENT_IDM, "LaneChangePolicy": abi.AGENT_LANE_CHANGE}.get(cfg["agent_policy"],
+                                                                                                          abi.AGENT_INPUT)
         self.md_config.enable_reverse = int(bool(cfg["vehicle_config"]["enable_reverse"]))
         self.step_kernel = pick_step_kernel(cfg, len(tables))
         self.md_config.step_kernel = {"wg": 0, "wave": 1}[self.step_kernel]
@@ -755,9 +756,11 @@ class BatchedEngine:
         """actions: tensor [E, A, 2] (or [E, 2] when A == 1), float32, on the engine's device.  With agent_policy =
         IDMPolicy the agents drive themselves: `actions` is ignored (None is fine), as the reference's IDMPolicy ignores
         what env.step() is given.  With agent_policy = ExpertPolicy likewise: the expert acts on the state the previous
-        step left (ExpertPolicy.act in before_step), then the world steps with that action.  An env that auto-resets in
+        step left (ExpertPolicy.act in before_step), then the world steps with that action.  With agent_policy = LaneChangePolicy
+        `actions` are the decoded discrete actions (steering -1 / 0 / +1 = right / keep / left): md_step turns the steering into the
+        lane-change PIDs' output before it integrates the agents (include/md_lane_change.h).  An env that auto-resets in
         this step discards it (md_step restores the env instead of moving it); its next action comes from the reset state."""
-        if self.k.agent_idm:
+        if self.k.agent_idm == abi.AGENT_IDM:
             self.s.agent_action = None
             self.step_raw()
             return

@@ -21,20 +21,28 @@ from metadrive_ped_amd.config import make_config
 from metadrive_ped_amd.envs.spaces import Box, LazyInfo, Discrete, MultiDiscrete
 
 
+def steering_dim(cfg):
+    """Steering grid size of the discrete action space: LaneChangePolicy has 3 (left, keep, right) whatever
+    discrete_steering_dim says (policy/lange_change_policy.py:22,57)."""
+    return 3 if cfg["agent_policy"] == "LaneChangePolicy" else int(cfg["discrete_steering_dim"])
+
+
 def make_action_space(cfg):
-    """EnvInputPolicy.get_input_space (policy/env_input_policy.py:50-69)."""
+    """EnvInputPolicy.get_input_space (policy/env_input_policy.py:50-69); LaneChangePolicy.get_input_space
+    (policy/lange_change_policy.py:50-62) with steering_dim(cfg) = 3."""
     if not cfg["discrete_action"]:
         return Box(-1.0, 1.0, (2, ), np.float32)
     if cfg["use_multi_discrete"]:
-        return MultiDiscrete([cfg["discrete_steering_dim"], cfg["discrete_throttle_dim"]])
-    return Discrete(cfg["discrete_steering_dim"] * cfg["discrete_throttle_dim"])
+        return MultiDiscrete([steering_dim(cfg), cfg["discrete_throttle_dim"]])
+    return Discrete(steering_dim(cfg) * cfg["discrete_throttle_dim"])
 
 
 def discrete_to_continuous(torch, cfg, actions, lead_shape, device):
     """EnvInputPolicy.convert_to_continuous_action (policy/env_input_policy.py:40-48) for a batch: Discrete
     index -> (index % steering_dim, index // steering_dim), MultiDiscrete -> (a[0], a[1]); each grid index i
-    maps to i * 2/(dim-1) - 1.  Returns float32 [*lead_shape, 2] on `device`."""
-    sd, td = int(cfg["discrete_steering_dim"]), int(cfg["discrete_throttle_dim"])
+    maps to i * 2/(dim-1) - 1.  Returns float32 [*lead_shape, 2] on `device`.  Under LaneChangePolicy the steering
+    grid has 3 values, so the steering is exactly -1 (right), 0 (keep) or +1 (left)."""
+    sd, td = steering_dim(cfg), int(cfg["discrete_throttle_dim"])
     a = actions if torch.is_tensor(actions) else torch.as_tensor(np.asarray(actions))
     if a.is_floating_point():
         raise TypeError("discrete_action=True expects integer actions, got dtype {}".format(a.dtype))

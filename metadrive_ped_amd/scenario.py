@@ -74,6 +74,9 @@ def make_scenario_config(user=None):
     ego_replay = pol == "ReplayEgoCarPolicy"
     if pol == "ExpertPolicy":
         raise NotImplementedError("agent_policy=ExpertPolicy: not in BatchedScenarioEnv (single-agent PG envs only)")
+    if pol == "LaneChangePolicy":
+        raise NotImplementedError("agent_policy=LaneChangePolicy needs a road network's lanes: not in BatchedScenarioEnv "
+                                  "(EnvInputPolicy, ReplayEgoCarPolicy)")
     if ego_replay:
         user.pop("agent_policy")
     own = {}
