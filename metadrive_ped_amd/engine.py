@@ -18,6 +18,7 @@ import numpy as np
 from metadrive_ped_amd import abi, hostpool
 from metadrive_ped_amd.mapgen.pg import PGMap
 from metadrive_ped_amd.mapgen.tables import MapTables, WorldTables, beam_table
+from metadrive_ped_amd.obs_layout import ObsLayout
 from metadrive_ped_amd.scene import EnvScene
 
 STATE_ARRAY_SPECS = None  # filled below
@@ -171,19 +172,7 @@ class HostScene:
         cap = cfg["mover_capacity"] or abi.MD_MAX_CAP  # 0 = auto: build with the maximum, trim below
         A = cfg["num_agents"]
         self.E, self.cap, self.A = E, cap, A
-        self.n_beams = int(cfg["vehicle_config"]["lidar"]["num_lasers"]) if cfg["vehicle_config"]["lidar"]["distance"] > 0 else 0
-        vc = cfg["vehicle_config"]
-        self.n_side = int(vc["side_detector"]["num_lasers"]) if vc["side_detector"]["distance"] > 0 else 0
-        self.n_ll = int(vc["lane_line_detector"]["num_lasers"]) if vc["lane_line_detector"]["distance"] > 0 else 0
-        self.obs_base = 2 if cfg["random_agent_model"] else 0            # [length, width] lead the state dims
-        self.tollgate = bool(cfg["is_multi_agent"]) and cfg["marl_map"] == "tollgate"
-        # 19 with everything off; the tollgate env's state observation has no navigation dims (marl_tollgate.py:62-74)
-        self.state_dim = self.obs_base + (self.n_side or 2) + 6 + (self.n_ll or 1) + (0 if self.tollgate else 10)
-        # "others" block only exists with the lidar on (obs/state_obs.py:172-183)
-        self.num_others = int(vc["lidar"]["num_others"]) if self.n_beams > 0 else 0
-        self.add_others_navi = bool(vc["lidar"]["add_others_navi"]) and self.num_others > 0
-        self.others_dim = self.num_others * (8 if self.add_others_navi else 4)
-        self.obs_dim = self.state_dim + self.others_dim + self.n_beams + (2 if self.tollgate else 0)   # + the two toll dims
+        ObsLayout(cfg, scenario=False).export_to(self)     # self.layout, and n_beams / n_side / n_ll / obs_base / ... / obs_dim
         mc = cfg["map_config"]
         seeds = [cfg["start_seed"] + ((cfg["env_seed_offset"] + e) % cfg["num_scenarios"]) for e in range(E)]
         self.seeds = seeds
@@ -450,6 +439,12 @@ class BatchedEngine:
             c["mover_capacity"] = cap
         return c
 
+    def rebuild(self, cfg):
+        """Drop the host scene and build() again from `cfg` (a new start_seed, a new traffic draw)."""
+        self.host = None
+        self.cfg = cfg
+        self.build()
+
     def build(self):
         """(Re)generate maps + scenes on the host and upload.  BaseEnv.reset's map/agent/traffic managers."""
         torch = self.torch
@@ -614,23 +609,26 @@ class BatchedEngine:
             self._curriculum(0)
         elif self._staged is not None:   # random_traffic: the envs whose episode just ended get the next draw
             self._swap()
-        h = self.host
+        L = self.host.layout
         vc = self.cfg["vehicle_config"]
-        if self._fused_detectors:
+        obs = self.state_dev["obs"]
+        if self._fused_detectors:        # md_step ran them itself
             pass
-        elif h.n_side and h.n_ll and h.n_side + h.n_ll <= 255:
+        elif L.n_side and L.n_ll and L.n_side + L.n_ll <= 255:
             # both detector clouds in ONE launch and one pass over the line pieces (md_line_detectors)
             self._check(self.lib.md_line_detectors(
                 C.byref(self.w), C.byref(self.s), C.byref(self.k),
-                C.c_void_p(self._side_beams.data_ptr()), h.n_side, C.c_float(float(vc["side_detector"]["distance"])), C.c_uint32(self.SIDE_MASK), h.obs_base,
-                C.c_void_p(self._ll_beams.data_ptr()), h.n_ll, C.c_float(float(vc["lane_line_detector"]["distance"])), C.c_uint32(self.LANE_LINE_MASK),
-                h.obs_base + (h.n_side or 2) + 6, C.c_void_p(self.state_dev["obs"].data_ptr()), h.obs_dim, self._stream()), "md_line_detectors")
-        elif h.n_side:   # SideDetector cloud replaces obs[0:2] (obs/state_obs.py:77-86)
-            self.line_detector(self._side_beams, h.n_side, float(self.cfg["vehicle_config"]["side_detector"]["distance"]),
-                               self.SIDE_MASK, self.state_dev["obs"], h.obs_dim, h.obs_base)
-        if h.n_ll and not self._fused_detectors and not (h.n_side and h.n_side + h.n_ll <= 255):     # LaneLineDetector cloud replaces the lateral dim (obs/state_obs.py:129-140)
-            self.line_detector(self._ll_beams, h.n_ll, float(self.cfg["vehicle_config"]["lane_line_detector"]["distance"]),
-                               self.LANE_LINE_MASK, self.state_dev["obs"], h.obs_dim, h.obs_base + (h.n_side or 2) + 6)
+                C.c_void_p(self._side_beams.data_ptr()), L.n_side, C.c_float(float(vc["side_detector"]["distance"])),
+                C.c_uint32(self.SIDE_MASK), L.side_off,
+                C.c_void_p(self._ll_beams.data_ptr()), L.n_ll, C.c_float(float(vc["lane_line_detector"]["distance"])),
+                C.c_uint32(self.LANE_LINE_MASK), L.ll_off,
+                C.c_void_p(obs.data_ptr()), L.obs_dim, self._stream()), "md_line_detectors")
+        else:
+            if L.n_side:     # SideDetector cloud replaces obs[0:2] (obs/state_obs.py:77-86)
+                self.line_detector(self._side_beams, L.n_side, float(vc["side_detector"]["distance"]), self.SIDE_MASK, obs, L.obs_dim, L.side_off)
+            if L.n_ll:       # LaneLineDetector cloud replaces the lateral dim (obs/state_obs.py:129-140)
+                self.line_detector(self._ll_beams, L.n_ll, float(vc["lane_line_detector"]["distance"]), self.LANE_LINE_MASK, obs, L.obs_dim,
+                                   L.ll_off)
         self._lidar_noise()
         if self._rec is not None:
             self._record_frame()
@@ -678,10 +676,9 @@ class BatchedEngine:
         unseeded numpy stream, so no stream can be 'the' stream; this one is a device generator seeded with
         start_seed + env_seed_offset (reproducible, shard-dependent)."""
         vc = self.cfg["vehicle_config"]
-        h = self.host
-        clouds = [(vc["lidar"], self.obs_dim - self.n_beams, self.n_beams),
-                  (vc["side_detector"], h.obs_base, h.n_side),
-                  (vc["lane_line_detector"], h.obs_base + (h.n_side or 2) + 6, h.n_ll)]
+        L = self.host.layout
+        clouds = [(vc["lidar"], L.lidar_off, L.n_beams), (vc["side_detector"], L.side_off, L.n_side),
+                  (vc["lane_line_detector"], L.ll_off, L.n_ll)]
         torch = self.torch
         for dc, off, n in clouds:
             g, p = float(dc["gaussian_noise"]), float(dc["dropout_prob"])

@@ -14,11 +14,15 @@ on the road as a static body for `delay_done` steps) or free.  Tensors are [E, A
 
 `to_dicts(e, ...)` rebuilds the reference's dict-of-agents view of one env for drop-in code.
 """
+import copy
+
 import numpy as np
 
 from metadrive_ped_amd import abi
 from metadrive_ped_amd.config import make_config
-from metadrive_ped_amd.envs.spaces import Box, LazyInfo
+from metadrive_ped_amd.envs.base import BatchedEnvBase, ObjectSpawnMixin
+from metadrive_ped_amd.envs.metadrive_env import make_action_space
+from metadrive_ped_amd.envs.spaces import LazyInfo
 
 MULTI_AGENT_DEFAULTS = dict(
     is_multi_agent=True, num_agents=40, crash_done=True, out_of_road_done=True, delay_done=25, allow_respawn=True,
@@ -39,74 +43,43 @@ def _deep_update(dst, src):
     return dst
 
 
-class BatchedMultiAgentRoundaboutEnv:
+class BatchedMultiAgentRoundaboutEnv(ObjectSpawnMixin, BatchedEnvBase):
+    MAP_DEFAULTS = {}         # a subclass's map: merged over MULTI_AGENT_DEFAULTS, under the user's config
+
+    @classmethod
+    def _merged(cls, config=None):
+        merged = _deep_update(copy.deepcopy(MULTI_AGENT_DEFAULTS), copy.deepcopy(cls.MAP_DEFAULTS))
+        return make_config(_deep_update(merged, dict(config or {})))
+
     @classmethod
     def default_config(cls):
-        import copy
-        return make_config(copy.deepcopy(MULTI_AGENT_DEFAULTS))
+        return cls._merged()
 
     def __init__(self, config=None):
-        import copy
-        merged = _deep_update(copy.deepcopy(MULTI_AGENT_DEFAULTS), dict(config or {}))
-        self.config = make_config(merged)
-        self.num_envs = self.config["num_envs"]
+        super().__init__(self._merged(config))
         self.num_agents = self.config["num_agents"]
-        lidar = self.config["vehicle_config"]["lidar"]
-        n = lidar["num_lasers"] if lidar["distance"] > 0 else 0
-        vc = self.config["vehicle_config"]
-        n_s = vc["side_detector"]["num_lasers"] if vc["side_detector"]["distance"] > 0 else 0
-        n_l = vc["lane_line_detector"]["num_lasers"] if vc["lane_line_detector"]["distance"] > 0 else 0
-        n_o = lidar["num_others"] * (8 if lidar["add_others_navi"] else 4) if n > 0 else 0
-        toll = self.config["marl_map"] == "tollgate"     # no navigation dims, two toll dims after the cloud
-        base = 2 if self.config["random_agent_model"] else 0     # [length, width] lead the observation (state_obs.py:70-75)
-        self.observation_space = Box(-0.0, 1.0, (base + (n_s or 2) + 6 + (n_l or 1) + (0 if toll else 10) + n_o + n + (2 if toll else 0), ),
-                                     np.float32)
-        from metadrive_ped_amd.envs.metadrive_env import make_action_space
         self.action_space = make_action_space(self.config)
-        self.engine = None
 
     def reset(self, seed=None):
         if seed is not None:
             self.config["start_seed"] = int(seed)
             if self.engine is not None:
-                self.engine.host = None
-                self.engine.cfg = self.config
-                self.engine.build()
+                self.engine.rebuild(self.config)
         self.lazy_init()
         self.engine.reset()
         return self.engine.obs, self._info()
 
-    def lazy_init(self, host=None):
-        """`host`: a HostScene already built from this env's config (e.g. before the GPU was touched)."""
-        if self.engine is None:
-            from metadrive_ped_amd.engine import BatchedEngine
-            self.engine = BatchedEngine(self.config, host=host)
-
     def step(self, actions):
-        if self.engine is None:
-            raise RuntimeError("call reset() before step()")
-        torch = self.engine.torch
+        self._require_engine("step")
         if self.config["agent_policy"] == "IDMPolicy":      # every agent is driven by its own IDMPolicy: `actions` is ignored
-            a = None
-        elif self.config["discrete_action"]:
-            from metadrive_ped_amd.envs.metadrive_env import discrete_to_continuous
-            a = discrete_to_continuous(torch, self.config, actions, (self.num_envs, self.num_agents), self.engine.device)
+            self.engine.step(None)
         else:
-            a = actions if torch.is_tensor(actions) else torch.as_tensor(np.asarray(actions, dtype=np.float32))
-        if a is not None and tuple(a.shape) != (self.num_envs, self.num_agents, 2):
-            raise ValueError("actions must have shape [{}, {}, 2], got {}".format(self.num_envs, self.num_agents, tuple(a.shape)))
-        self.engine.step(a)
-        A = self.num_agents
-        fl = self.engine.flags[:, :A]
+            self.engine.step(self._coerce_actions(actions, (self.num_envs, self.num_agents), self.config["discrete_action"]))
         info = self._info()
-        if self.engine.done_tt is not None:
-            # written by md_step itself (MdState.done_out), zero for slots without a live agent: no device op here -- one md_step
-            # launch per step and nothing else (every eager torch op costs ~5 us, 3 % of this step).
-            # Views of the engine's buffers, like obs and reward: .clone() what has to outlive the next step()
-            terminated, truncated = self.engine.done_tt[:, :A, 0], self.engine.done_tt[:, :A, 1]
-        else:
-            terminated = ((fl & abi.FL_TERMINATED) != 0) & info["active"]
-            truncated = ((fl & abi.FL_TRUNCATED) != 0) & info["active"]
+        # from md_step itself (MdState.done_out), zero for slots without a live agent: one md_step launch per step and nothing else
+        terminated, truncated = self._done_flags(slice(0, self.num_agents))
+        if self.engine.done_tt is None:
+            terminated, truncated = terminated & info["active"], truncated & info["active"]
         info._lazy["terminated_all"] = lambda: (terminated | ~info["active"]).all(dim=1)
         info._lazy["truncated_all"] = lambda: (truncated | ~info["active"]).all(dim=1)
         return self.engine.obs, self.engine.reward, terminated, truncated, info
@@ -115,8 +88,6 @@ class BatchedMultiAgentRoundaboutEnv:
         e = self.engine
         A = self.num_agents
         sf = e.shape_f.view(e.torch.int32)[:, :A, 6]
-        fl = e.flags[:, :A]
-        bit = lambda m: (lambda: (fl & m) != 0)
         eager = {
             "agent_id": e.agent_id[:, :A],
             "velocity": e.step_info[:, :, 1], "step_reward": e.step_info[:, :, 0], "episode_reward": e.step_info[:, :, 4],
@@ -126,21 +97,9 @@ class BatchedMultiAgentRoundaboutEnv:
             "active": lambda: (sf & (abi.F_ALIVE | abi.F_STATIC)) == abi.F_ALIVE,
             "dying": lambda: (sf & (abi.F_ALIVE | abi.F_STATIC)) == (abi.F_ALIVE | abi.F_STATIC),
             "spawned": lambda: ((sf & (abi.F_ALIVE | abi.F_STATIC)) == abi.F_ALIVE) & (e.nav_i[:, :A, 8] == 0),
-            "crash_vehicle": bit(abi.FL_CRASH_VEHICLE), "crash_object": bit(abi.FL_CRASH_OBJECT),
-            "crash_sidewalk": bit(abi.FL_CRASH_SIDEWALK), "out_of_road": bit(abi.FL_OUT_OF_ROAD),
-            "arrive_dest": bit(abi.FL_ARRIVE_DEST), "max_step": bit(abi.FL_MAX_STEP),
         }
+        lazy.update(self._flag_info(e.flags[:, :A]))
         return LazyInfo(eager, lazy)
-
-    # traffic participants (needs mover_capacity > num_agents: the agents' slots are never handed out)
-    def spawn_object(self, kind, position, heading_theta=0.0, envs=None):
-        return self.engine.spawn_object(kind, position, heading_theta, envs)
-
-    def set_velocity(self, handle, direction, value=None, in_local_frame=False, envs=None):
-        self.engine.set_velocity(handle, direction, value, in_local_frame, envs)
-
-    def clear_objects(self, handles, envs=None):
-        self.engine.clear_objects(list(handles), envs)
 
     def to_dicts(self, e, obs, reward, terminated, truncated, info):
         """The reference's per-agent dict view of env `e` (keys "agent{k}", plus "__all__")."""
@@ -171,30 +130,11 @@ class BatchedMultiAgentRoundaboutEnv:
                 out[e, slot_of[name]] = v
         return torch.from_numpy(out).to(self.engine.device)
 
-    def seed(self, seed=None):
-        """Scenario seeds are set through reset(seed=...); a no-op like the gymnasium API."""
-
-    def render(self, *args, **kwargs):
-        raise NotImplementedError("rendering lies outside this build (DESIGN.md section 1)")
-
-    def close(self):
-        self.engine = None
-
 
 class BatchedMultiAgentIntersectionEnv(BatchedMultiAgentRoundaboutEnv):
     """MultiAgentIntersectionEnv (envs/marl_envs/marl_intersection.py:11-110): 30 agents on a 4-way intersection
     with U-turns, spawn roads = the four arms, destination = a random arm (its own included)."""
     MAP_DEFAULTS = dict(marl_map="intersection", num_agents=30, map_config=dict(exit_length=60, lane_num=2))
-
-    @classmethod
-    def default_config(cls):
-        import copy
-        return make_config(_deep_update(copy.deepcopy(MULTI_AGENT_DEFAULTS), copy.deepcopy(cls.MAP_DEFAULTS)))
-
-    def __init__(self, config=None):
-        import copy
-        merged = _deep_update(copy.deepcopy(self.MAP_DEFAULTS), dict(config or {}))
-        super().__init__(merged)
 
 
 class BatchedMultiAgentTinyInter(BatchedMultiAgentIntersectionEnv):
@@ -242,16 +182,6 @@ class BatchedMultiAgentRacingEnv(BatchedMultiAgentRoundaboutEnv):
                         cross_yellow_line_done=False, out_of_road_done=True, on_continuous_line_done=False, out_of_route_done=False,
                         crash_done=False, horizon=3000, idle_done=True, crash_sidewalk_done=False, crash_vehicle_done=False)
 
-    @classmethod
-    def default_config(cls):
-        import copy
-        return make_config(_deep_update(copy.deepcopy(MULTI_AGENT_DEFAULTS), copy.deepcopy(cls.MAP_DEFAULTS)))
-
-    def __init__(self, config=None):
-        import copy
-        merged = _deep_update(copy.deepcopy(self.MAP_DEFAULTS), dict(config or {}))
-        super().__init__(merged)
-
     def _info(self):
         info = super()._info()
         e, A = self.engine, self.num_agents
@@ -267,16 +197,6 @@ class BatchedMultiAgentBottleneckEnv(BatchedMultiAgentRoundaboutEnv):
                         map_config=dict(exit_length=60, lane_num=4, neck_lane_num=1, neck_length=20),
                         vehicle_config=dict(side_detector=dict(num_lasers=4, distance=50),
                                             lane_line_detector=dict(num_lasers=4, distance=20)))
-
-    @classmethod
-    def default_config(cls):
-        import copy
-        return make_config(_deep_update(copy.deepcopy(MULTI_AGENT_DEFAULTS), copy.deepcopy(cls.MAP_DEFAULTS)))
-
-    def __init__(self, config=None):
-        import copy
-        merged = _deep_update(copy.deepcopy(self.MAP_DEFAULTS), dict(config or {}))
-        super().__init__(merged)
 
 
 class BatchedMultiAgentBidirectionEnv(BatchedMultiAgentBottleneckEnv):
@@ -299,16 +219,6 @@ class BatchedMultiAgentTollgateEnv(BatchedMultiAgentRoundaboutEnv):
                                             lane_line_detector=dict(num_lasers=4, distance=20),
                                             lidar=dict(num_lasers=72, distance=20)))
 
-    @classmethod
-    def default_config(cls):
-        import copy
-        return make_config(_deep_update(copy.deepcopy(MULTI_AGENT_DEFAULTS), copy.deepcopy(cls.MAP_DEFAULTS)))
-
-    def __init__(self, config=None):
-        import copy
-        merged = _deep_update(copy.deepcopy(self.MAP_DEFAULTS), dict(config or {}))
-        super().__init__(merged)
-
     def _info(self):
         info = super()._info()
         e, A = self.engine, self.num_agents
@@ -326,16 +236,6 @@ class BatchedMultiAgentParkingLotEnv(BatchedMultiAgentRoundaboutEnv):
     MAP_DEFAULTS = dict(marl_map="parking_lot", num_agents=10, parking_space_num=8, map_config=dict(exit_length=20, lane_num=1),
                         vehicle_config=dict(enable_reverse=True))
 
-    @classmethod
-    def default_config(cls):
-        import copy
-        return make_config(_deep_update(copy.deepcopy(MULTI_AGENT_DEFAULTS), copy.deepcopy(cls.MAP_DEFAULTS)))
-
-    def __init__(self, config=None):
-        import copy
-        merged = _deep_update(copy.deepcopy(self.MAP_DEFAULTS), dict(config or {}))
-        super().__init__(merged)
-
     def _info(self):
         info = super()._info()
         e, A = self.engine, self.num_agents
@@ -348,13 +248,3 @@ class BatchedMultiAgentMetaDrive(BatchedMultiAgentRoundaboutEnv):
     generated map (one per scenario seed, 3 blocks, 3 lanes), all spawning on the first block's exit road (5 slots x 3
     lanes) and driving to the far end of the map."""
     MAP_DEFAULTS = dict(marl_map="pg", num_agents=15, map=3, map_config=dict(exit_length=50, lane_num=3))
-
-    @classmethod
-    def default_config(cls):
-        import copy
-        return make_config(_deep_update(copy.deepcopy(MULTI_AGENT_DEFAULTS), copy.deepcopy(cls.MAP_DEFAULTS)))
-
-    def __init__(self, config=None):
-        import copy
-        merged = _deep_update(copy.deepcopy(self.MAP_DEFAULTS), dict(config or {}))
-        super().__init__(merged)

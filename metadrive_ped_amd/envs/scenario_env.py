@@ -31,6 +31,7 @@ worker's first scenario of its level."""
 import numpy as np
 
 from metadrive_ped_amd import abi
+from metadrive_ped_amd.envs.base import SINGLE_AGENT_FLAG_INFO, BatchedEnvBase
 from metadrive_ped_amd.envs.spaces import Box, LazyInfo
 from metadrive_ped_amd.scenario import ScenarioHostScene, make_scenario_config, synthetic_scenarios
 
@@ -42,16 +43,17 @@ def scenario_bench_config(common):
     return cfg
 
 
-class BatchedScenarioEnv:
+class BatchedScenarioEnv(BatchedEnvBase):
     metadata = {"render_modes": []}
+    FLAG_INFO = SINGLE_AGENT_FLAG_INFO
+    ASSIGNMENT = ("start_scenario_index", "tracks")
 
     @classmethod
     def default_config(cls):
         return make_scenario_config({})
 
     def __init__(self, config=None, scenarios=None):
-        self.config = make_scenario_config(config)
-        self.num_envs = self.config["num_envs"]
+        super().__init__(make_scenario_config(config), scenario=True)
         walk = bool(self.config["walk_scenarios"])
         if scenarios is None and self.config["data_directory"] is not None:
             from metadrive_ped_amd.scenario_data import load_scenarios
@@ -63,20 +65,14 @@ class BatchedScenarioEnv:
             scenarios = synthetic_scenarios(self.num_envs, self.config["start_scenario_index"] + self.config["env_seed_offset"])
         self.scenarios = scenarios
         self.host = None
-        self.engine = None
         self.action_space = Box(-1.0, 1.0, (2, ), np.float32)
-        vc = self.config["vehicle_config"]
-        n = vc["lidar"]["num_lasers"] if vc["lidar"]["distance"] > 0 else 0
-        n_s = vc["side_detector"]["num_lasers"] if vc["side_detector"]["distance"] > 0 else 0
-        n_l = vc["lane_line_detector"]["num_lasers"] if vc["lane_line_detector"]["distance"] > 0 else 0
-        self._obs_dim = (n_s or 2) + 6 + (n_l or 1) + 22 + n
-        self.observation_space = Box(-0.0, 1.0, (self._obs_dim, ), np.float32)
+
+    def _build_host(self):
+        return ScenarioHostScene(self.config, self.scenarios)
 
     def lazy_init(self, host=None):
-        if self.engine is None:
-            from metadrive_ped_amd.engine import BatchedEngine
-            self.host = host or ScenarioHostScene(self.config, self.scenarios)
-            self.engine = BatchedEngine(self.config, host=self.host)
+        super().lazy_init(host)
+        self.host = self.engine.host
 
     def reset(self, seed=None):
         self.lazy_init()
@@ -84,29 +80,17 @@ class BatchedScenarioEnv:
         return self.engine.obs[:, 0, :], self._info()
 
     def step(self, actions):
-        if self.engine is None:
-            raise RuntimeError("call reset() before step()")
-        torch = self.engine.torch
+        self._require_engine("step")
         if actions is None and self.config["agent_policy"] == "ReplayEgoCarPolicy":
             actions = np.zeros((self.num_envs, 2), np.float32)      # the agent replays the SDC track: actions are ignored
-        a = actions if torch.is_tensor(actions) else torch.as_tensor(np.asarray(actions, dtype=np.float32))
-        if a.dim() == 1:
-            a = a.unsqueeze(0).expand(self.num_envs, 2)
-        if tuple(a.shape) != (self.num_envs, 2):
-            raise ValueError("actions must have shape [{}, 2], got {}".format(self.num_envs, tuple(a.shape)))
-        self.engine.step(a)
-        fl = self.engine.flags[:, 0]
-        if self.engine.done_tt is not None:      # (terminated, truncated) written by md_step itself
-            return self.engine.obs[:, 0, :], self.engine.reward[:, 0], self.engine.done_tt[:, 0, 0], self.engine.done_tt[:, 0, 1], \
-                self._info()
-        return self.engine.obs[:, 0, :], self.engine.reward[:, 0], (fl & abi.FL_TERMINATED) != 0, (fl & abi.FL_TRUNCATED) != 0, \
-            self._info()
+        self.engine.step(self._coerce_actions(actions, (self.num_envs, ), False))
+        terminated, truncated = self._done_flags()
+        return self.engine.obs[:, 0, :], self.engine.reward[:, 0], terminated, truncated, self._info()
 
     # -- checkpoints (envs/base_env.py:775-836 get_state / set_state through the managers): a dict of numpy arrays; the routes the
     #    device cut at later spawn frames are state too and travel with it -----------------------------------------------------
     def get_state(self):
-        if self.engine is None:
-            raise RuntimeError("call reset() before get_state()")
+        self._require_engine("get_state")
         st = self.engine.download_state()
         st["__seeds__"] = np.asarray(self.engine.host.seeds, dtype=np.int64)
         st["__scenario_ids__"] = np.asarray(self.engine.host.scenario_ids)
@@ -114,21 +98,13 @@ class BatchedScenarioEnv:
         return st
 
     def set_state(self, state):
-        if self.engine is None:
-            raise RuntimeError("call reset() before set_state()")
+        self._require_engine("set_state")
         if "__abi__" in state and int(np.asarray(state["__abi__"])[0]) != abi.MD_ABI_VERSION:
             raise ValueError("the checkpoint was written by ABI v{}, this library is v{}: the record layouts differ".format(
                 int(np.asarray(state["__abi__"])[0]), abi.MD_ABI_VERSION))
-        if np.asarray(state["__seeds__"]).tolist() != list(self.engine.host.seeds):
-            raise ValueError("the checkpoint was taken with another scenario assignment (start_scenario_index / num_scenarios / "
-                             "env_seed_offset differ): tracks and routes would not match")
+        arrays = self._check_checkpoint(state)
         if "__scenario_ids__" in state and [str(x) for x in np.asarray(state["__scenario_ids__"]).tolist()] != list(self.engine.host.scenario_ids):
             raise ValueError("the checkpoint was taken on other scenarios (their ids differ): tracks and routes would not match")
-        arrays = {k: v for k, v in state.items() if not k.startswith("__")}
-        ref = self.engine.host.state
-        for k, v in arrays.items():
-            if k not in ref or np.asarray(v).nbytes != ref[k].nbytes:
-                raise ValueError("checkpoint array {!r} does not fit this batch".format(k))
         self.engine.upload_state(arrays)
         if "scene_of" in arrays:     # the walk: each env's line map is its scene
             self.engine.world_dev["env_map"].copy_(self.engine.state_dev["scene_of"])
@@ -137,17 +113,11 @@ class BatchedScenarioEnv:
         e = self.engine
         fl = e.flags[:, 0]
         si = e.step_info[:, 0, :]
-        bit = lambda m: (lambda: (fl & m) != 0)
         eager = {"velocity": si[:, 1], "step_energy": si[:, 2], "episode_energy": si[:, 3], "step_reward": si[:, 0],
                  "episode_reward": si[:, 4], "episode_length": e.nav_i[:, 0, 8], "cost": e.cost[:, 0], "total_cost": si[:, 5],
                  "route_completion": si[:, 6], "action": e.action[:, 0, :], "raw_action": e.action[:, 0, :]}
-        lazy = {"crash_vehicle": bit(abi.FL_CRASH_VEHICLE), "crash_object": bit(abi.FL_CRASH_OBJECT),
-                "crash_human": bit(abi.FL_CRASH_HUMAN), "crash_building": bit(abi.FL_CRASH_BUILDING),
-                "crash_sidewalk": bit(abi.FL_CRASH_SIDEWALK), "out_of_road": bit(abi.FL_OUT_OF_ROAD),
-                "arrive_dest": bit(abi.FL_ARRIVE_DEST), "max_step": bit(abi.FL_MAX_STEP),
-                "crash": bit(abi.FL_CRASH_VEHICLE | abi.FL_CRASH_OBJECT | abi.FL_CRASH_BUILDING | abi.FL_CRASH_SIDEWALK |
-                             abi.FL_CRASH_HUMAN),
-                "scenario_index": self._scenario_index}
+        lazy = self._flag_info(fl)
+        lazy["scenario_index"] = self._scenario_index
         if e.host.walk:     # the curriculum's keys (envs/scenario_env.py:279-285), as md_curriculum reported them for this step
             torch = e.torch
             rep_i = e.state_dev["cur_rep_i"].view(torch.int32).view(self.num_envs, 2)
@@ -178,6 +148,3 @@ class BatchedScenarioEnv:
         ep = e.state_dev["walk_ep"].view(torch.int32).cpu().numpy().astype(np.int64) - e.need_reset.cpu().numpy()
         p = walk_scene(self.config, np.arange(self.num_envs), np.maximum(ep, 0))
         return torch.as_tensor(int(self.config["start_scenario_index"]) + p, device=e.device)
-
-    def close(self):
-        self.engine = None

@@ -24,6 +24,7 @@ import numpy as np
 
 from metadrive_ped_amd import abi
 from metadrive_ped_amd.mapgen.tables import beam_table
+from metadrive_ped_amd.obs_layout import ObsLayout
 
 # ScenarioEnv's own defaults (envs/scenario_env.py:21-95); keys not listed keep BaseEnv's
 SCENARIO_DEFAULT_CONFIG = dict(
@@ -660,14 +661,7 @@ class ScenarioHostScene:
                                      S, frames / 2 ** 30, T, cap, int(cfg["scenario_pool_max_bytes"]) / 2 ** 30))
         A = 1
         self.E, self.cap, self.A, self.T = E, cap, A, T
-        vc = cfg["vehicle_config"]
-        self.n_beams = int(vc["lidar"]["num_lasers"]) if vc["lidar"]["distance"] > 0 else 0
-        self.n_side = int(vc["side_detector"]["num_lasers"]) if vc["side_detector"]["distance"] > 0 else 0
-        self.n_ll = int(vc["lane_line_detector"]["num_lasers"]) if vc["lane_line_detector"]["distance"] > 0 else 0
-        self.obs_base = 0
-        self.state_dim = (self.n_side or 2) + 6 + (self.n_ll or 1) + 22
-        self.num_others, self.add_others_navi, self.others_dim = 0, False, 0
-        self.obs_dim = self.state_dim + self.n_beams
+        ObsLayout(cfg, scenario=True).export_to(self)      # self.layout, and n_beams / n_side / n_ll / ... / obs_dim
         # scene e <-> dataset index start_scenario_index + (env_seed_offset + e) % num_scenarios (scenario_data.scenario_indices):
         # the identity checkpoints and track sets are checked against, and the fallback parameter seed of a description that
         # carries none -- tied to WHICH scenario it is, not to where it sits in the batch.  A walk's pool: the slice itself.
