@@ -124,6 +124,13 @@ BATCH_DEFAULT_CONFIG = dict(
     step_kernel="auto",     # single-agent md_step: "wg" = one 4-wave workgroup per env, "wave" = one wave per env, "auto" = by
                             # the number of distinct maps the batch shares (engine.WAVE_KERNEL_MAX_MAPS) (same
                             # results bit for bit; a machine-mapping choice)
+    # the PG walk (no key of the reference's: it draws a new scenario seed at every reset by itself, envs/base_env.py:886-891):
+    # True = an env moves on to another seed of [start_seed, start_seed + num_scenarios) whenever its episode ends, on the device
+    walk_scenarios=False,
+    walk_stride=None,       # W, the envs over all shards / sub-batches (sharding.shard_config and SubBatchedEnvs set it); None: num_envs
+    sequential_seed=False,  # walk order: False = a uniform draw over the slice per (global env index, episode), the reference's PG
+                            # rule from a reproducible stream; True = worker w = (env_seed_offset + e) % num_scenarios plays w, w + W, ...
+    scenario_pool_max_bytes=64 << 30,   # a walk's scene pool (maps + snapshot rows, device bytes) larger than this is refused
     expert_weights=None,    # agent_policy="ExpertPolicy" / expert.expert(): path of the reference's ppo_expert/expert_weights.npz;
                             # None = found in an installed reference package (metadrive_ped_amd/expert.py)
 )
@@ -288,6 +295,21 @@ def make_config(user=None):
             raise ValueError("parking_space_num > 20: the spawn tables hold 32 places")
     if not cfg["cross_yellow_line_done"] and cfg["marl_map"] not in ("tollgate", "racing"):
         raise NotImplementedError("cross_yellow_line_done=False is built for the tollgate env only")
+    if cfg["walk_scenarios"]:
+        # the PG walk: what this change does not build is refused by name
+        if cfg["is_multi_agent"]:
+            raise NotImplementedError("walk_scenarios=True in a multi-agent env is not built (marl_map='pg' included): the walk moves "
+                                      "single-agent PG envs")
+        if cfg["random_traffic"]:
+            raise NotImplementedError("walk_scenarios=True with random_traffic=True is not built: the staged traffic draws would "
+                                      "multiply the scenario pool")
+        if cfg["traffic_mode"] == "replay":
+            raise NotImplementedError("walk_scenarios=True with traffic_mode='replay' is not built: recorded traffic (load_tracks / "
+                                      "load_scenarios) belongs to one scenario assignment")
+        if not cfg["auto_reset"]:
+            raise ValueError("walk_scenarios=True needs auto_reset=True: an env moves on when it resets itself")
+        if cfg["walk_stride"] is not None and int(cfg["walk_stride"]) < 1:
+            raise ValueError("walk_stride must be >= 1 (the env count over all shards), got {!r}".format(cfg["walk_stride"]))
     if cfg["step_kernel"] not in ("auto", "wg", "wave"):
         raise ValueError("step_kernel must be 'auto', 'wg' or 'wave', got {!r}".format(cfg["step_kernel"]))
     if cfg["mover_capacity"] != 0 and (cfg["mover_capacity"] > 128 or cfg["mover_capacity"] < cfg["num_agents"]):

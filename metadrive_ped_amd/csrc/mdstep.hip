@@ -3688,6 +3688,9 @@ __device__ void copy_draw_rows(const MdState& live, const MdState& staged, int c
 // The scenario walk (traffic_mode 4, MdState.walk.mode > 0) is the same move with the scenes for draws: `staged` holds the snapshot rows
 // of the n_draws = n_scenes scenes of the pool (scene p at p * cap), `draw_idx` is MdWorld.env_map (the scene's line map); the env
 // takes scene md_walk_scene(c, e, walk_ep[e] + 1) and scene_of / walk_ep / env_map follow.  The per-scene tables are only redirected.
+// The PG walk (traffic_mode 0 / 1 / 2 with MdState.walk.mode > 0) is that move over a pool of PG scenes: scene p = scenario seed
+// start_seed + p, env_map[e] = p picks its map, and the scene's traffic stream state (MdState.rng, the respawn modes) comes along
+// with the rows -- the reference re-seeds the traffic manager with the scenario seed at every reset.
 __global__ __launch_bounds__(256) void swap_draw_kernel(MdState live, MdState staged, MdConfig c, int n_draws, int32_t* draw_idx) {
     const int e = blockIdx.x;
     if (e >= c.n_envs || live.need_reset[e] == 0) return;   // block-uniform
@@ -3701,6 +3704,7 @@ __global__ __launch_bounds__(256) void swap_draw_kernel(MdState live, MdState st
         if (walk) {
             live.scene_of[e] = k;
             live.walk_ep[e] = ep;
+            if (live.rng && staged.rng) live.rng[e] = staged.rng[k];
         }
     }
     const size_t row = (size_t)e * c.cap, from = walk ? (size_t)k * c.cap : ((size_t)k * c.n_envs + e) * c.cap;
@@ -3936,7 +3940,7 @@ enum When : unsigned {
     REPLAY = 16, SPAWN_TRAFFIC = 32,                     // check_phase, after traffic_mode is validated
     SCENARIO = 64, ROUTE = 128, OTHERS = 256,            // md_step, each after the config checks of its branch
 };
-constexpr int kLidarEntry = 1 << 9, kDetectorEntry = 1 << 10, kExpertEntry = 1 << 11;
+constexpr int kLidarEntry = 1 << 9, kDetectorEntry = 1 << 10, kExpertEntry = 1 << 11, kPgWalkEntry = 1 << 12;
 constexpr int kMapPhases = PH_LOCALIZE | PH_CONTACTS | PH_OBSERVE | PH_IDM | PH_LIFECYCLE;
 constexpr int kTrafficPhases = PH_INTEGRATE | PH_TRAFFIC;
 
@@ -3970,6 +3974,8 @@ const Need kNeeds[] = {
     {kDetectorEntry, ALWAYS, {FW(env_map), FW(quad_off), FW(quads), FW(quad_kind)}},
     {kExpertEntry, ALWAYS, {FS(obs), FS(detected), FS(dyn), FS(param), FS(nav), FW(env_map), FW(lanes), FW(lane_off), FW(roads),
                             FW(road_off)}},
+    {kPgWalkEntry, ALWAYS, {FS(scene_of), FS(walk_ep), FS(param), FS(route_nodes), FS(route_roads), FS(final_lane), FS(idm_rand)}},
+    {kPgWalkEntry, SPAWN_TRAFFIC, {FS(rng), FS(route_nodes0), FS(route_roads0), FS(final_lane0)}},
 };
 #undef FW
 #undef FS
@@ -4246,7 +4252,24 @@ __attribute__((visibility("default"))) int md_swap_draw(const MdState* s, const 
         return MD_EINVAL;
     }
     const MdWalk& wk = s->walk;
-    if (wk.mode != 0) {   // the scenario walk: n_draws scenes, draw_idx = MdWorld.env_map
+    if (wk.mode != 0 && c->traffic_mode >= 0 && c->traffic_mode <= 2) {   // the PG walk: n_draws PG scenes, draw_idx = MdWorld.env_map
+        if (wk.mode < 0 || wk.mode > 2 || c->is_multi_agent || c->agents_per_env != 1 || wk.n_scenes != n_draws || wk.stride < 1 ||
+            wk.offset < 0) {
+            snprintf(g_err, sizeof g_err, "md_swap_draw: the PG walk needs mode 1 or 2 (got %d), a single-agent batch (agents=%d), "
+                     "n_scenes == n_draws (%d, %d), stride >= 1 (%d) and offset >= 0 (%d)", wk.mode, c->agents_per_env, wk.n_scenes,
+                     n_draws, wk.stride, wk.offset);
+            return MD_EINVAL;
+        }
+        // the live batch and the pool hold the same per-slot constants: what the in-kernel reset of the next step reads
+        TRY(need_fields(kPgWalkEntry, ALWAYS | SPAWN_TRAFFIC, nullptr, s, c));
+        const bool spawn = c->traffic_mode == 1 || c->traffic_mode == 2;
+        if (!staged->param || !staged->route_nodes || !staged->route_roads || !staged->final_lane || !staged->idm_rand ||
+            (spawn && !staged->rng)) {
+            snprintf(g_err, sizeof g_err, "md_swap_draw: the PG walk's pool (staged) needs param / route_nodes / route_roads / "
+                     "final_lane / idm_rand, and rng in the respawn / hybrid modes");
+            return MD_EINVAL;
+        }
+    } else if (wk.mode != 0) {   // the scenario walk: n_draws scenes, draw_idx = MdWorld.env_map
         if (wk.mode < 0 || wk.mode > 2 || c->traffic_mode != 4 || wk.n_scenes != n_draws || wk.stride < 1 || wk.offset < 0 ||
             !s->scene_of || !s->walk_ep) {
             snprintf(g_err, sizeof g_err, "md_swap_draw: the scenario walk needs mode 1 or 2 (got %d), traffic_mode 4, n_scenes == "

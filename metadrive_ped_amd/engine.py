@@ -174,9 +174,22 @@ class HostScene:
         self.E, self.cap, self.A = E, cap, A
         ObsLayout(cfg, scenario=False).export_to(self)     # self.layout, and n_beams / n_side / n_ll / obs_base / ... / obs_dim
         mc = cfg["map_config"]
-        seeds = [cfg["start_seed"] + ((cfg["env_seed_offset"] + e) % cfg["num_scenarios"]) for e in range(E)]
-        self.seeds = seeds
-        uniq = sorted(set(seeds))
+        # the PG walk (walk_scenarios): the scene pool is every seed of the slice, built once whatever the env count; env e starts at
+        # the first scene of its walk (scenario.walk_scene), and md_swap_draw moves it on through the pool on the device
+        walk = bool(cfg.get("walk_scenarios"))
+        self.walk, self.pool, self.walk_params = walk, None, (0, 0, 0, 0, 0)
+        if walk:
+            from metadrive_ped_amd.scenario import walk_params, walk_scene
+            self.walk_params = walk_params(cfg)
+            pool_seeds = [cfg["start_seed"] + p for p in range(cfg["num_scenarios"])]
+            env_scene = [int(p) for p in walk_scene(cfg, np.arange(E), 0)]
+            seeds = [pool_seeds[p] for p in env_scene]
+            self.seeds = pool_seeds       # names the slice, like ScenarioHostScene.seeds of a walk
+            uniq = pool_seeds
+        else:
+            seeds = [cfg["start_seed"] + ((cfg["env_seed_offset"] + e) % cfg["num_scenarios"]) for e in range(E)]
+            self.seeds = seeds
+            uniq = sorted(set(seeds))
         map_of_seed = {}
         tables, scenes = [], {}
         scene_cfg = dict(cap=cap, agents_per_env=A, physics_world_step_size=cfg["physics_world_step_size"],
@@ -251,25 +264,33 @@ class HostScene:
                 a[k] = np.ascontiguousarray(self.spawn[k])
         N = E * cap
 
-        def stack(field):
-            return np.concatenate([getattr(scenes[s], field) for s in seeds], axis=0)
+        def draw_rows(of_seeds):
+            """The snapshot rows and per-slot constants (BatchedEngine.DRAW_ARRAYS) of the scenes `of_seeds`, cap slots each"""
+            def stack(field):
+                return np.concatenate([getattr(scenes[s], field) for s in of_seeds], axis=0)
+            d = {}
+            d["shape0"] = stack("shape")
+            d["dyn0"] = stack("dyn")
+            d["nav0"] = stack("nav")
+            d["pid0"] = stack("pid")
+            d["param"] = stack("param")
+            d["route_nodes"] = stack("route_nodes")
+            d["route_roads"] = stack("route_roads")
+            d["final_lane"] = stack("final_lane")
+            d["idm_rand"] = stack("idm_rand")
+            # MdNav.road0 / road1: the road ids under the two route cursors, kept beside them (ABI v7) so that the per-step
+            # logic never indexes the route arrays
+            n = len(of_seeds) * cap
+            rows = np.arange(n)
+            rr = d["route_roads"].reshape(n, abi.MD_ROUTE_LEN)
+            d["nav0"]["road0"] = rr[rows, np.clip(d["nav0"]["ck0"], 0, abi.MD_ROUTE_LEN - 1)]
+            d["nav0"]["road1"] = rr[rows, np.clip(d["nav0"]["ck1"], 0, abi.MD_ROUTE_LEN - 1)]
+            return d
 
-        st = {}
-        st["shape0"] = stack("shape")
-        st["dyn0"] = stack("dyn")
-        st["nav0"] = stack("nav")
-        st["pid0"] = stack("pid")
-        st["param"] = stack("param")
-        st["route_nodes"] = stack("route_nodes")
-        st["route_roads"] = stack("route_roads")
-        st["final_lane"] = stack("final_lane")
-        st["idm_rand"] = stack("idm_rand")
-        # MdNav.road0 / road1: the road ids under the two route cursors, kept beside them (ABI v7) so that the per-step
-        # logic never indexes the route arrays
-        rows = np.arange(N)
-        rr = st["route_roads"].reshape(N, abi.MD_ROUTE_LEN)
-        st["nav0"]["road0"] = rr[rows, np.clip(st["nav0"]["ck0"], 0, abi.MD_ROUTE_LEN - 1)]
-        st["nav0"]["road1"] = rr[rows, np.clip(st["nav0"]["ck1"], 0, abi.MD_ROUTE_LEN - 1)]
+        def rng_of(of_seeds):   # xorshift32 needs a non-zero state; derive it from the scenario seed
+            return np.asarray([((s * 2654435761) ^ 0x9E3779B9) & 0xFFFFFFFF or 1 for s in of_seeds], np.uint32)
+
+        st = draw_rows(seeds)
         st["shape"] = st["shape0"].copy()
         st["dyn"] = st["dyn0"].copy()
         st["nav"] = st["nav0"].copy()
@@ -288,8 +309,7 @@ class HostScene:
             st["route_nodes0"] = st["route_nodes"].copy()
             st["route_roads0"] = st["route_roads"].copy()
             st["final_lane0"] = st["final_lane"].copy()
-            # xorshift32 needs a non-zero state; derive it from the env's scenario seed
-            st["rng"] = np.asarray([((s * 2654435761) ^ 0x9E3779B9) & 0xFFFFFFFF or 1 for s in seeds], np.uint32)
+            st["rng"] = rng_of(seeds)
         if cfg["is_multi_agent"] and cfg["random_agent_model"]:
             from metadrive_ped_amd.marl import vehicle_class_table
             st["param0"] = st["param"].copy()
@@ -304,6 +324,21 @@ class HostScene:
             st["detected"] = np.zeros((E * A, 2), np.uint64)
         if cfg["is_multi_agent"] and cfg["marl_map"] == "racing":
             st["idle_ring"] = np.zeros((E * A, abi.MD_IDLE_WINDOW), np.float32)     # movement_between_steps of every agent
+        if walk:
+            # what md_swap_draw copies into an env that moves on to pool scene p: its rows at p * cap, and the scene's traffic
+            # stream (the reference re-seeds the traffic manager with the scenario seed at every reset)
+            st["scene_of"] = np.asarray(env_scene, np.int32)
+            st["walk_ep"] = np.zeros(E, np.int32)
+            self.pool = draw_rows(pool_seeds)
+            if "rng" in st:
+                self.pool["rng"] = rng_of(pool_seeds)
+            dev_bytes = sum(v.nbytes for v in self.world.arrays.values()) + sum(v.nbytes for v in self.pool.values())
+            if dev_bytes > int(cfg["scenario_pool_max_bytes"]):
+                raise ValueError("walk_scenarios: the pool of num_scenarios={} scenes needs {:.2f} GiB on the device (maps and snapshot "
+                                 "rows, mover capacity {}), more than scenario_pool_max_bytes={:.2f} GiB: walk a smaller slice".format(
+                                     len(pool_seeds), dev_bytes / 2 ** 30, cap, int(cfg["scenario_pool_max_bytes"]) / 2 ** 30))
+            print("walk_scenarios: scene pool of num_scenarios={} scenes (mover capacity {}): {:.1f} MiB on the device".format(
+                len(pool_seeds), cap, dev_bytes / 2 ** 20), flush=True)
         self.state = st
         self.md_config = make_md_config(cfg, E, A, cap, self.n_beams)
         self.md_config.n_side, self.md_config.n_lane_line = self.n_side, self.n_ll
@@ -514,7 +549,7 @@ class BatchedEngine:
         # the curriculum of a walk (include/md_curriculum.h): md_curriculum after every step; with more than one level it moves
         # the envs itself, instead of md_swap_draw
         self._cur = None
-        if self._walk:
+        if self._walk and getattr(h, "curriculum", None) is not None:     # scenario mode; the PG walk has no curriculum
             L, per, Q, target = h.curriculum
             n, _, W, off, _ = h.walk_params
             cu = abi.MdCurriculum()
@@ -603,12 +638,6 @@ class BatchedEngine:
 
     def _step_raw(self):
         self._check(self.lib.md_step(C.byref(self.w), C.byref(self.s), C.byref(self.k), self._stream()), "md_step")
-        if self._cur is not None:        # the scenario walk: the curriculum's step, and the envs whose episode just ended move on
-            if self._cur.n_levels == 1:
-                self._swap()
-            self._curriculum(0)
-        elif self._staged is not None:   # random_traffic: the envs whose episode just ended get the next draw
-            self._swap()
         L = self.host.layout
         vc = self.cfg["vehicle_config"]
         obs = self.state_dev["obs"]
@@ -630,6 +659,14 @@ class BatchedEngine:
                 self.line_detector(self._ll_beams, L.n_ll, float(vc["lane_line_detector"]["distance"]), self.LANE_LINE_MASK, obs, L.obs_dim,
                                    L.ll_off)
         self._lidar_noise()
+        # Only now, with the step's observation complete, do the envs whose episode just ended move on: the swap of a walk rewrites
+        # MdWorld.env_map, and the detector launches above trace the map of the episode that ended
+        if self._cur is not None:        # the scenario walk: the curriculum's step, and the envs whose episode just ended move on
+            if self._cur.n_levels == 1:
+                self._swap()
+            self._curriculum(0)
+        elif self._staged is not None:   # random_traffic / the PG walk: the envs whose episode just ended get the next draw / scene
+            self._swap()
         if self._rec is not None:
             self._record_frame()
 
@@ -639,6 +676,9 @@ class BatchedEngine:
         """Call right after reset(): frame 0 is the reset state, frame k the state after the k-th step.  Frames are
         device tensors (32 + 8 bytes per slot and step); recording stops by itself when the buffer is full."""
         torch = self.torch
+        if self._walk and not self.cfg.get("scenario_mode"):
+            raise NotImplementedError("start_recording with walk_scenarios=True: the recorded frames belong to one scenario assignment; "
+                                      "record a batch without the walk")
         n = self.E * self.cap
         self._rec = dict(shape=torch.empty((max_steps + 1, n * 32), dtype=torch.uint8, device=self.device),
                          dyn=torch.empty((max_steps + 1, n, 2), dtype=torch.float32, device=self.device), n=0)

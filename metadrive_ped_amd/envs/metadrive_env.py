@@ -13,6 +13,14 @@ Everything returned is a torch tensor on the engine's device (views of the engin
 them if you keep them across steps).  With config auto_reset=True an env that terminated or was
 truncated at step t is restored from its reset snapshot during step t+1, which then returns the
 reset observation with reward 0 (gymnasium's NEXT_STEP autoreset convention).
+
+walk_scenarios=True (the PG walk): an env whose episode ends moves on, on the device (md_swap_draw), to another scenario seed of
+[start_seed, start_seed + num_scenarios) -- its map, spawn, route, traffic, props and vehicle parameters -- as the reference draws
+a new seed at every reset (BaseEnv._reset_global_seed, envs/base_env.py:886-891).  Every seed of the slice is built once into a
+scene pool.  sequential_seed=False: a uniform draw per (global env index, episode) from a reproducible stream; True: env e is worker
+w = (env_seed_offset + e) % num_scenarios of walk_stride workers and plays start_seed + w + k * walk_stride.  info["env_seed"],
+current_seeds and info["scenario_index"] (the position in the slice) follow each env's current scenario as device tensors;
+reset() restarts every env at episode 0 of its walk; get_state() / set_state() carry the walk.
 """
 import copy
 
@@ -112,7 +120,7 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
             self.config["traffic_epoch"] = int(self.config.get("traffic_epoch", 0)) + 1
             self.engine.rebuild(self.config)
         self.lazy_init()
-        self.engine.reset()
+        self.engine.reset()        # a walk: every env back to episode 0 of its walk
         return self._obs(), self._info()
 
     def step(self, actions):
@@ -142,6 +150,7 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
         """traffic_mode='replay' from scenario descriptions written by export_scenarios() (one per env, same scenario
         seeds): ScenarioEnv-style replay of data recorded here."""
         from metadrive_ped_amd.scenario_export import scenarios_to_tracks
+        self._refuse_tracks_while_walking("load_scenarios")
         self.lazy_init()
         tracks = scenarios_to_tracks(scenarios, self.engine.host)
         torch = self.engine.torch
@@ -151,10 +160,16 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
     def load_tracks(self, tracks):
         """For an env built with traffic_mode='replay': the traffic follows `tracks` (from stop_recording() of an env
         with the same scenarios) instead of reacting; call before reset()."""
+        self._refuse_tracks_while_walking("load_tracks")
         if self.config["traffic_mode"] != "replay":
             raise ValueError("load_tracks needs config traffic_mode='replay'")
         self.lazy_init()
         self.engine.set_tracks(tracks)
+
+    def _refuse_tracks_while_walking(self, what):
+        if self.config["walk_scenarios"]:
+            raise NotImplementedError("{} with walk_scenarios=True is not built: recorded traffic belongs to one scenario assignment; "
+                                      "replay a batch without the walk".format(what))
 
     # -- state checkpoint (the role of BaseEngine/BaseManager get_state / set_state, manager/base_manager.py:116-135,
     #    and of BaseVehicle.get_state / set_state, component/vehicle/base_vehicle.py:808-846: everything that
@@ -164,18 +179,31 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
         arrays, plus the scenario assignment.  set_state() of the result resumes bit-identically."""
         self._require_engine("get_state")
         st = self.engine.download_state()
-        st["__seeds__"] = np.asarray(self.engine.host.seeds, dtype=np.int64)
-        if getattr(self.engine, "_staged", None) is not None:       # random_traffic: which staged draw every env is on
+        st["__seeds__"] = np.asarray(self.engine.host.seeds, dtype=np.int64)     # a walk: the slice
+        if self.engine.host.walk:       # each env's scene and walk position travel in scene_of / walk_ep; which walk it is, here
+            st["__walk__"] = np.asarray(self.engine.host.walk_params, dtype=np.int64)
+        elif getattr(self.engine, "_staged", None) is not None:       # random_traffic: which staged draw every env is on
             st["__draw_idx__"] = self.engine.draw_idx.cpu().numpy().copy()
         return st
 
     def set_state(self, state):
         self._require_engine("set_state")
         arrays = self._check_checkpoint(state)
+        if self.engine.host.walk != ("scene_of" in arrays):
+            raise ValueError("the checkpoint was taken with walk_scenarios={}, this batch has walk_scenarios={}".format(
+                "scene_of" in arrays, self.engine.host.walk))
+        if self.engine.host.walk and np.asarray(state.get("__walk__", ())).tolist() != list(self.engine.host.walk_params):
+            # the same slice walked in another order (sequential_seed), by other workers (walk_stride, env_seed_offset): walk_ep
+            # would continue a different schedule
+            raise ValueError("the checkpoint was taken on another walk (num_scenarios, sequential_seed, walk_stride, env_seed_offset, "
+                             "start_seed = {}, this batch has {})".format(np.asarray(state.get("__walk__", ())).tolist(),
+                                                                          list(self.engine.host.walk_params)))
         draw_idx = state.get("__draw_idx__")
-        if draw_idx is not None and getattr(self.engine, "_staged", None) is not None:
+        if draw_idx is not None and getattr(self.engine, "_staged", None) is not None and not self.engine.host.walk:
             self.engine.draw_idx.copy_(self.engine.torch.from_numpy(np.asarray(draw_idx, dtype=np.int32)))
         self.engine.upload_state(arrays)
+        if self.engine.host.walk:     # the walk: each env's line map is its scene's
+            self.engine.world_dev["env_map"].copy_(self.engine.state_dev["scene_of"])
 
     # -- helpers --------------------------------------------------------------------------------
     def _obs(self):
@@ -193,10 +221,21 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
         }
         lazy = self._flag_info(fl)
         lazy["env_seed"] = self._env_seed_tensor
+        lazy["scenario_index"] = self._scenario_index
         return LazyInfo(eager, lazy)
+
+    def _scenario_index(self):
+        """[E] int64: each env's position in the slice [start_seed, start_seed + num_scenarios).  A walk: MdState.scene_of, on the
+        device (an env whose episode ended in this step has already been moved on: it names the scenario of its reset)."""
+        e = self.engine
+        if e.host.walk:
+            return e.state_dev["scene_of"].view(e.torch.int32).long()
+        return self._env_seed_tensor() - int(e.cfg["start_seed"])
 
     def _env_seed_tensor(self):
         e = self.engine
+        if e.host.walk:     # follows the env's current scenario: no host copy to cache
+            return self._scenario_index() + int(e.cfg["start_seed"])
         key = tuple(e.host.seeds)
         if getattr(self, "_seed_cache", (None, None))[0] != key:
             self._seed_cache = (key, e.torch.as_tensor(np.asarray(e.host.seeds, dtype=np.int64), device=e.device))
@@ -219,6 +258,9 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
 
     @property
     def current_seeds(self):
+        """The scenario seed of every env: a list; under walk_scenarios the [E] device tensor start_seed + scene_of."""
+        if self.engine.host.walk:
+            return self._env_seed_tensor()
         return list(self.engine.host.seeds)
 
 
@@ -252,4 +294,7 @@ class BatchedVaryingDynamicsEnv(BatchedMetaDriveEnv):
         self.lazy_init()
         keys = ("max_engine_force", "max_brake_force", "wheel_friction", "max_steering", "mass")
         h = self.engine.host
-        return [{k: h.scenes[s].vehicle_cfgs[0][k] for k in keys if k in h.scenes[s].vehicle_cfgs[0]} for s in h.seeds]
+        seeds = h.seeds
+        if h.walk:      # the scenario each env is on now (one device read)
+            seeds = [int(s) for s in self.current_seeds.cpu().numpy()]
+        return [{k: h.scenes[s].vehicle_cfgs[0][k] for k in keys if k in h.scenes[s].vehicle_cfgs[0]} for s in seeds]

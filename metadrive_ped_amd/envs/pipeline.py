@@ -37,6 +37,8 @@ class SubBatchedEnvs:
             c = copy.deepcopy(config)
             c["num_envs"] = E // S
             c["env_seed_offset"] = base + k * (E // S)
+            if c.get("walk_scenarios") and not c.get("walk_stride"):     # the sub-batches are workers of ONE walk
+                c["walk_stride"] = E
             self.envs.append(env_cls(c))
         self.streams = None
         self._hosts = None
