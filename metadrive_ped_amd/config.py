@@ -22,7 +22,7 @@ BASE_DEFAULT_CONFIG = dict(
     allow_respawn=False,
     delay_done=0,
     # ===== action =====
-    agent_policy="EnvInputPolicy",   # or "IDMPolicy" / "ExpertPolicy" / "LaneChangePolicy" (the class of that name is accepted too): envs/base_env.py:53
+    agent_policy="EnvInputPolicy",   # or "IDMPolicy" / "ExpertPolicy" / "LaneChangePolicy" / "AIProtectPolicy" (the class of that name is accepted too): envs/base_env.py:53
     discrete_action=False,
     use_multi_discrete=False,
     discrete_steering_dim=5,
@@ -162,7 +162,11 @@ _OFF_ONLY = dict(use_render=False, image_observation=False, manual_control=False
                  save_level=0.5)
 _OFF_ONLY_VEHICLE = dict(no_wheel_friction=False, navigation_module=None, spawn_position_heading=None, light=False)
 _OFF_HINT = dict(record_episode="use env.start_recording() / stop_recording() / export_scenarios()",
-                 replay_episode="use traffic_mode='replay' with env.load_tracks()")
+                 replay_episode="use traffic_mode='replay' with env.load_tracks()",
+                 use_AI_protector="the saver is built as agent_policy='AIProtectPolicy' (with config['save_level'])",
+                 save_level="any value in [0, 1] is read by agent_policy='AIProtectPolicy' only")
+# the policies whose step runs the PPO expert (expert_config_problem applies)
+EXPERT_POLICIES = ("ExpertPolicy", "AIProtectPolicy")
 
 
 def _merge(dst, src, path=""):
@@ -224,8 +228,15 @@ def make_config(user=None):
     if isinstance(user.get("sensors"), dict) and not user["sensors"]:
         user["sensors"] = None                                  # an empty sensor table is the default
     _merge(cfg, user)
+    # agent_policy: the reference takes a policy CLASS; here its name (or a class of that name)
+    pol = cfg["agent_policy"]
+    pol = pol if isinstance(pol, str) else getattr(pol, "__name__", repr(pol))
     for where, table in ((cfg, _OFF_ONLY), (cfg["vehicle_config"], _OFF_ONLY_VEHICLE)):
         for k, off in table.items():
+            if k == "save_level" and pol == "AIProtectPolicy":      # the saver's grade (policy/AI_protect_policy.py:15)
+                if isinstance(where[k], bool) or not isinstance(where[k], (int, float)) or not 0.0 <= where[k] <= 1.0:
+                    raise ValueError("config['save_level']={!r}: a number in [0, 1]".format(where[k]))
+                continue
             if where[k] != off:
                 raise NotImplementedError("config['{}']={!r}: this option lies outside the batched step() path built so far "
                                           "(only {!r} is accepted){}".format(k, where[k], off,
@@ -253,20 +264,17 @@ def make_config(user=None):
             raise KeyError("random_dynamics: unknown parameter(s) {}".format(sorted(unknown)))
     if cfg["is_multi_agent"] and abs(cfg["accident_prob"]) >= 1e-2:
         raise NotImplementedError("accident scenes in a multi-agent env are not built")
-    # agent_policy: the reference takes a policy CLASS; here its name (or a class of that name)
-    pol = cfg["agent_policy"]
-    pol = pol if isinstance(pol, str) else getattr(pol, "__name__", repr(pol))
-    if pol not in ("EnvInputPolicy", "IDMPolicy", "ExpertPolicy", "LaneChangePolicy"):
+    if pol not in ("EnvInputPolicy", "IDMPolicy", "ExpertPolicy", "LaneChangePolicy", "AIProtectPolicy"):
         raise NotImplementedError("agent_policy={!r}: built are EnvInputPolicy (actions from step()), IDMPolicy, ExpertPolicy, "
-                                  "LaneChangePolicy and, in BatchedScenarioEnv only, ReplayEgoCarPolicy".format(pol))
+                                  "LaneChangePolicy, AIProtectPolicy and, in BatchedScenarioEnv only, ReplayEgoCarPolicy".format(pol))
     cfg["agent_policy"] = pol
     if pol == "LaneChangePolicy":
         # LaneChangePolicy.__init__ (policy/lange_change_policy.py:16)
         assert cfg["discrete_action"], "Must set discrete_action=True for using this control policy"
-    if pol == "ExpertPolicy":
+    if pol in EXPERT_POLICIES:
         problem = expert_config_problem(cfg)
         if problem:
-            raise ValueError(problem)
+            raise ValueError(problem if pol == "ExpertPolicy" else problem.replace("agent_policy=ExpertPolicy", "agent_policy=" + pol))
     if cfg["num_agents"] == -1:
         # "infinite agents" (spawn_manager.py:74-78, agent_manager.py:272-279, multi_agent_metadrive.py:86-92): every spawn
         # point holds an agent at reset and a new agent enters whenever a spawn region is clear, whatever the number on

@@ -30,6 +30,7 @@
 
 #include "md_curriculum.h"
 #include "md_expert.h"
+#include "md_ai_protect.h"
 #include "md_scenario.h"
 
 namespace {
@@ -3813,15 +3814,12 @@ __device__ __forceinline__ void expert_hidden(const float* __restrict__ W, const
         for (int r = 0; r < 4; ++r) out[((lane >> 4) * 4 + r) * kExpHS + (4 * wave + j) * 16 + (lane & 15)] = md_tanh(acc[j][r]);
 }
 
-__global__ __launch_bounds__(256) void expert_kernel(MdWorld w, MdState g, MdConfig c, const float* __restrict__ wts,
-                                                     const float* __restrict__ noise, float* __restrict__ action_out,
-                                                     float* __restrict__ mlp_out, float* __restrict__ obs_out) {
-    __shared__ __attribute__((aligned(16))) float l_x[kExpM * kExpXS];   // x; later h2 (stride kExpHS)
-    __shared__ __attribute__((aligned(16))) float l_h[kExpM * kExpHS];   // h1
-    __shared__ float l_out[kExpM * MD_EXPERT_OUT];
+// Stages 1-3 for the tile of envs [e0, e0 + n_here): leaves mean | log_std of row r in l_out[r * MD_EXPERT_OUT ...], behind a barrier.
+// l_x [kExpM * kExpXS] (x; later h2 at stride kExpHS), l_h [kExpM * kExpHS] (h1) and l_out are the calling kernel's LDS.
+__device__ __forceinline__ void expert_tile_forward(const MdWorld& w, const MdState& g, const MdConfig& c, const float* __restrict__ wts,
+                                                    float* __restrict__ obs_out, float* l_x, float* l_h, float* l_out, int e0,
+                                                    int n_here) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int e0 = blockIdx.x * kExpM;
-    const int n_here = min(kExpM, c.n_envs - e0);
     const int od = c.obs_dim;   // 259: state 19 | cloud 240
     // 1. the expert's observation
     for (int i = tid; i < kExpM * kExpXS; i += 256) {
@@ -3868,6 +3866,18 @@ __global__ __launch_bounds__(256) void expert_kernel(MdWorld w, MdState g, MdCon
             for (int r = 0; r < 4; ++r) l_out[((lane >> 4) * 4 + r) * MD_EXPERT_OUT + (lane & 15)] = acc[0][r];
     }
     __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void expert_kernel(MdWorld w, MdState g, MdConfig c, const float* __restrict__ wts,
+                                                     const float* __restrict__ noise, float* __restrict__ action_out,
+                                                     float* __restrict__ mlp_out, float* __restrict__ obs_out) {
+    __shared__ __attribute__((aligned(16))) float l_x[kExpM * kExpXS];   // x; later h2 (stride kExpHS)
+    __shared__ __attribute__((aligned(16))) float l_h[kExpM * kExpHS];   // h1
+    __shared__ float l_out[kExpM * MD_EXPERT_OUT];
+    const int tid = threadIdx.x;
+    const int e0 = blockIdx.x * kExpM;
+    const int n_here = min(kExpM, c.n_envs - e0);
+    expert_tile_forward(w, g, c, wts, obs_out, l_x, l_h, l_out, e0, n_here);
     if (tid < n_here * MD_EXPERT_OUT) {
         const int r = tid >> 2, q = tid & 3;
         const size_t e = (size_t)(e0 + r);
@@ -3877,6 +3887,51 @@ __global__ __launch_bounds__(256) void expert_kernel(MdWorld w, MdState g, MdCon
             action_out[e * 2 + q] = noise ? md_expert_sample(mean, l_out[r * MD_EXPERT_OUT + 2 + q], noise[e * 2 + q]) : mean;
         }
     }
+}
+
+// md_ai_protect: AIProtectPolicy (include/md_ai_protect.h) in one launch.  The expert's draw exactly as expert_kernel computes it (the
+// same tile, the same chains), then the rule as an epilogue, one thread per env: obs[0], obs[1] and the four lidar windows come from
+// the env's obs row in HBM (l_x holds h2 by now), speed / heading / lane from the env's state and the map tables.  No LDS beyond
+// expert_kernel's.
+__global__ __launch_bounds__(256) void ai_protect_kernel(MdWorld w, MdState g, MdConfig c, const float* __restrict__ wts,
+                                                         const float* __restrict__ noise, const float* __restrict__ actions,
+                                                         float save_level, unsigned char* __restrict__ takeover,
+                                                         unsigned char* __restrict__ expert_takeover, float* __restrict__ applied_out,
+                                                         unsigned char* __restrict__ flags_out, float* __restrict__ saver_out) {
+    __shared__ __attribute__((aligned(16))) float l_x[kExpM * kExpXS];
+    __shared__ __attribute__((aligned(16))) float l_h[kExpM * kExpHS];
+    __shared__ float l_out[kExpM * MD_EXPERT_OUT];
+    const int tid = threadIdx.x;
+    const int e0 = blockIdx.x * kExpM;
+    const int n_here = min(kExpM, c.n_envs - e0);
+    expert_tile_forward(w, g, c, wts, nullptr, l_x, l_h, l_out, e0, n_here);
+    if (tid >= n_here) return;
+    const int e = e0 + tid;
+    const float* o4 = l_out + tid * MD_EXPERT_OUT;
+    float sv[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) sv[q] = noise ? md_expert_sample(o4[q], o4[2 + q], noise[(size_t)e * 2 + q]) : o4[q];
+    if (saver_out) {
+        saver_out[(size_t)e * 2] = sv[0];
+        saver_out[(size_t)e * 2 + 1] = sv[1];
+    }
+    const float raw[2] = {actions[(size_t)e * 2], actions[(size_t)e * 2 + 1]};
+    float applied[2];
+    unsigned char tk = takeover[e], et = expert_takeover[e];
+    unsigned fl;
+    if (g.need_reset[e] != 0) {
+        fl = md_ai_protect_reset(raw, &tk, &et, applied);
+    } else {
+        const MdState s = md_env_view(&g, &c, e);
+        MdProtectIn in;
+        md_ai_protect_inputs(w.lanes + w.lane_off[w.env_map[e]], &s, &c, &in);
+        fl = md_ai_protect_act(raw, sv, &in, save_level, et != 0, &tk, applied);
+    }
+    takeover[e] = tk;
+    expert_takeover[e] = et;
+    applied_out[(size_t)e * 2] = applied[0];
+    applied_out[(size_t)e * 2 + 1] = applied[1];
+    flags_out[e] = (unsigned char)fl;
 }
 
 __global__ void probe_kernel(int op, const float* a, const float* b, float* out, int n) {
@@ -3940,7 +3995,7 @@ enum When : unsigned {
     REPLAY = 16, SPAWN_TRAFFIC = 32,                     // check_phase, after traffic_mode is validated
     SCENARIO = 64, ROUTE = 128, OTHERS = 256,            // md_step, each after the config checks of its branch
 };
-constexpr int kLidarEntry = 1 << 9, kDetectorEntry = 1 << 10, kExpertEntry = 1 << 11, kPgWalkEntry = 1 << 12;
+constexpr int kLidarEntry = 1 << 9, kDetectorEntry = 1 << 10, kExpertEntry = 1 << 11, kPgWalkEntry = 1 << 12, kProtectEntry = 1 << 13;
 constexpr int kMapPhases = PH_LOCALIZE | PH_CONTACTS | PH_OBSERVE | PH_IDM | PH_LIFECYCLE;
 constexpr int kTrafficPhases = PH_INTEGRATE | PH_TRAFFIC;
 
@@ -3974,6 +4029,7 @@ const Need kNeeds[] = {
     {kDetectorEntry, ALWAYS, {FW(env_map), FW(quad_off), FW(quads), FW(quad_kind)}},
     {kExpertEntry, ALWAYS, {FS(obs), FS(detected), FS(dyn), FS(param), FS(nav), FW(env_map), FW(lanes), FW(lane_off), FW(roads),
                             FW(road_off)}},
+    {kProtectEntry, ALWAYS, {FS(shape), FS(need_reset)}},
     {kPgWalkEntry, ALWAYS, {FS(scene_of), FS(walk_ep), FS(param), FS(route_nodes), FS(route_roads), FS(final_lane), FS(idm_rand)}},
     {kPgWalkEntry, SPAWN_TRAFFIC, {FS(rng), FS(route_nodes0), FS(route_roads0), FS(final_lane0)}},
 };
@@ -4417,26 +4473,52 @@ __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdSta
     return launch_status();
 }
 
+// the configs where the reference's rewrite of the vehicle config (numpy_expert.py:58-62) changes nothing
+static int check_expert_config(const MdConfig* c, const char* who) {
+    if (c->is_multi_agent || c->agents_per_env != 1 || c->traffic_mode == 4 || c->n_beams != 240 || c->lidar_range != 50.0f ||
+        c->num_others != 0 || c->n_side != 0 || c->n_lane_line != 0 || c->random_agent_model != 0 ||
+        c->obs_dim != MD_EXPERT_IN - 4 * MD_EXPERT_OTHERS) {
+        snprintf(g_err, sizeof g_err, "%s: needs a single-agent batch with the expert's lidar (240 beams, 50 m, num_others 0), "
+                 "no side / lane-line detector and random_agent_model off (obs_dim 259)", who);
+        return MD_EINVAL;
+    }
+    return MD_OK;
+}
+
 __attribute__((visibility("default"))) int md_expert(const MdWorld* w, const MdState* s, const MdConfig* c, const float* weights,
                                                     const float* noise, float* action_out, float* mlp_out, float* obs_out,
                                                     void* stream) {
     TRY(check_common(w, s, c));
     NEED(weights); NEED(action_out);
     TRY(need_fields(kExpertEntry, ALWAYS, w, s, c));
-    // the configs where the reference's rewrite of the vehicle config (numpy_expert.py:58-62) changes nothing
-    if (c->is_multi_agent || c->agents_per_env != 1 || c->traffic_mode == 4 || c->n_beams != 240 || c->lidar_range != 50.0f ||
-        c->num_others != 0 || c->n_side != 0 || c->n_lane_line != 0 || c->random_agent_model != 0 ||
-        c->obs_dim != MD_EXPERT_IN - 4 * MD_EXPERT_OTHERS) {
-        snprintf(g_err, sizeof g_err, "md_expert: needs a single-agent batch with the expert's lidar (240 beams, 50 m, num_others 0), "
-                 "no side / lane-line detector and random_agent_model off (obs_dim 259)");
-        return MD_EINVAL;
-    }
+    TRY(check_expert_config(c, "md_expert"));
     if ((uintptr_t)weights & 15) {
         snprintf(g_err, sizeof g_err, "md_expert: the packed weights must be 16-byte aligned");
         return MD_EINVAL;
     }
     hipLaunchKernelGGL(expert_kernel, dim3((c->n_envs + kExpM - 1) / kExpM), dim3(256), 0, (hipStream_t)stream, *w, *s, *c, weights,
                        noise, action_out, mlp_out, obs_out);
+    return launch_status();
+}
+
+__attribute__((visibility("default"))) int md_ai_protect(const MdWorld* w, const MdState* s, const MdConfig* c, const float* weights,
+                                                        const float* noise, const float* actions, float save_level,
+                                                        unsigned char* takeover, unsigned char* expert_takeover, float* applied_out,
+                                                        unsigned char* flags_out, float* saver_out, void* stream) {
+    TRY(check_common(w, s, c));
+    NEED(weights); NEED(actions); NEED(takeover); NEED(expert_takeover); NEED(applied_out); NEED(flags_out);
+    TRY(need_fields(kExpertEntry | kProtectEntry, ALWAYS, w, s, c));
+    TRY(check_expert_config(c, "md_ai_protect"));
+    if ((uintptr_t)weights & 15) {
+        snprintf(g_err, sizeof g_err, "md_ai_protect: the packed weights must be 16-byte aligned");
+        return MD_EINVAL;
+    }
+    if (!(save_level >= 0.0f && save_level <= 1.0f)) {
+        snprintf(g_err, sizeof g_err, "md_ai_protect: save_level=%g is not in [0, 1]", (double)save_level);
+        return MD_EINVAL;
+    }
+    hipLaunchKernelGGL(ai_protect_kernel, dim3((c->n_envs + kExpM - 1) / kExpM), dim3(256), 0, (hipStream_t)stream, *w, *s, *c, weights,
+                       noise, actions, save_level, takeover, expert_takeover, applied_out, flags_out, saver_out);
     return launch_status();
 }
 

@@ -318,10 +318,14 @@ class HostScene:
             st["env_steps"] = np.zeros(E, np.int32)
             st["agent_id"] = np.tile(np.arange(cap, dtype=np.int32), E)
             st["next_agent_id"] = np.full(E, cfg["initial_agents"] or A, np.int32)   # names agent0 .. agent{n-1} are taken
-        if self.num_others > 0 or cfg["agent_policy"] == "ExpertPolicy":
-            # ExpertPolicy: the expert's own "others" block (num_others=4) is computed by md_expert from these sets; the env's
+        if self.num_others > 0 or cfg["agent_policy"] in ("ExpertPolicy", "AIProtectPolicy"):
+            # ExpertPolicy / AIProtectPolicy: the expert's own "others" block (num_others=4) is computed by md_expert from these sets; the env's
             # obs keeps its 259 dims (md_step tracks the sets whenever the array is there)
             st["detected"] = np.zeros((E * A, 2), np.uint64)
+        if cfg["agent_policy"] == "AIProtectPolicy":
+            # vehicle.takeover / vehicle.expert_takeover (base_vehicle.py:361,367), one byte per env: md_ai_protect's arguments, not MdState's
+            st["takeover"] = np.zeros(E, np.uint8)
+            st["expert_takeover"] = np.zeros(E, np.uint8)
         if cfg["is_multi_agent"] and cfg["marl_map"] == "racing":
             st["idle_ring"] = np.zeros((E * A, abi.MD_IDLE_WINDOW), np.float32)     # movement_between_steps of every agent
         if walk:
@@ -765,17 +769,18 @@ class BatchedEngine:
             self._expert_w = self.torch.from_numpy(load_expert_weights(self.cfg.get("expert_weights"))).to(self.device)
         return self._expert_w
 
-    def expert_forward(self, deterministic=False, need_obs=False, action_out=None, mlp_out=None):
+    def expert_forward(self, deterministic=False, need_obs=False, action_out=None, mlp_out=None, noise=None):
         """ONE md_expert launch on the current observation -> action [E, 2] (+ the corrected expert obs [E, 275] with
         need_obs).  deterministic=False: action = mean + exp(log_std) * N(0, 1), one [E, 2] draw of the engine's expert
-        generator (seeded with start_seed + env_seed_offset)."""
+        generator (seeded with start_seed + env_seed_offset), or `noise` [E, 2] float32 on the device when given."""
         torch = self.torch
         if self.A != 1:
             raise ValueError("the expert drives single-agent envs")
         self._track_detected()
         w = self.expert_weights()
-        noise = None
-        if not deterministic:
+        if deterministic:
+            noise = None
+        elif noise is None:
             if self._expert_gen is None:
                 self._expert_gen = torch.Generator(device=self.device)
                 self._expert_gen.manual_seed(int(self.cfg["start_seed"]) + int(self.cfg["env_seed_offset"]))
@@ -789,14 +794,48 @@ class BatchedEngine:
                                            ptr(mlp_out), ptr(obs), self._stream()), "md_expert")
         return (action_out, obs) if need_obs else action_out
 
-    def step(self, actions):
+    def ai_protect_forward(self, actions, noise=None, saver_out=None):
+        """agent_policy = AIProtectPolicy (include/md_ai_protect.h): ONE md_ai_protect launch on the current observation -- the expert's
+        draw (the weights, the generator and the one [E, 2] draw per step of expert_forward) and the saver's rule on the agents'
+        decoded `actions` [E, 2].  -> the applied action [E, 2] (an engine buffer, rewritten by the next call); the flag bytes are left
+        in self.protect_flags, the vehicles' takeover / expert_takeover bytes updated in place.  `noise`: the draw to use instead."""
+        torch = self.torch
+        if "takeover" not in self.state_dev:
+            raise ValueError("ai_protect_forward needs agent_policy='AIProtectPolicy'")
+        w = self.expert_weights()
+        if noise is None:
+            if self._expert_gen is None:
+                self._expert_gen = torch.Generator(device=self.device)
+                self._expert_gen.manual_seed(int(self.cfg["start_seed"]) + int(self.cfg["env_seed_offset"]))
+            noise = torch.randn((self.E, 2), dtype=torch.float32, device=self.device, generator=self._expert_gen)
+        a = actions
+        if tuple(a.shape) != (self.E, 2):
+            raise ValueError("actions must have shape [{}, 2], got {}".format(self.E, tuple(a.shape)))
+        if a.dtype != torch.float32 or a.device != self.device or not a.is_contiguous():
+            a = a.to(self.device, torch.float32).contiguous()
+        if tuple(noise.shape) != (self.E, 2) or noise.dtype != torch.float32 or noise.device != self.device or not noise.is_contiguous():
+            raise ValueError("noise must be a contiguous float32 [{}, 2] tensor on the engine's device".format(self.E))
+        if getattr(self, "_protect_action", None) is None or self._protect_action.shape[0] != self.E:
+            self._protect_action = torch.empty((self.E, 2), dtype=torch.float32, device=self.device)
+            self.protect_flags = torch.zeros(self.E, dtype=torch.uint8, device=self.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+        with self._on_device():
+            self._check(self.lib.md_ai_protect(C.byref(self.w), C.byref(self.s), C.byref(self.k), ptr(w), ptr(noise), ptr(a),
+                                               C.c_float(float(self.cfg["save_level"])), ptr(self.state_dev["takeover"]),
+                                               ptr(self.state_dev["expert_takeover"]), ptr(self._protect_action), ptr(self.protect_flags),
+                                               ptr(saver_out), self._stream()), "md_ai_protect")
+        return self._protect_action
+
+    def step(self, actions, noise=None):
         """actions: tensor [E, A, 2] (or [E, 2] when A == 1), float32, on the engine's device.  With agent_policy =
         IDMPolicy the agents drive themselves: `actions` is ignored (None is fine), as the reference's IDMPolicy ignores
         what env.step() is given.  With agent_policy = ExpertPolicy likewise: the expert acts on the state the previous
         step left (ExpertPolicy.act in before_step), then the world steps with that action.  With agent_policy = LaneChangePolicy
         `actions` are the decoded discrete actions (steering -1 / 0 / +1 = right / keep / left): md_step turns the steering into the
         lane-change PIDs' output before it integrates the agents (include/md_lane_change.h).  An env that auto-resets in
-        this step discards it (md_step restores the env instead of moving it); its next action comes from the reset state."""
+        this step discards it (md_step restores the env instead of moving it); its next action comes from the reset state.
+        With agent_policy = AIProtectPolicy `actions` are the agents' own (decoded) actions and ai_protect_forward decides what the world
+        is stepped with; `noise` [E, 2]: the expert's draw of this step instead of the generator's (that policy only)."""
         if self.k.agent_idm == abi.AGENT_IDM:
             self.s.agent_action = None
             self.step_raw()
@@ -805,6 +844,8 @@ class BatchedEngine:
             if getattr(self, "_expert_action", None) is None or self._expert_action.shape[0] != self.E:
                 self._expert_action = self.torch.empty((self.E, 2), dtype=self.torch.float32, device=self.device)
             actions = self.expert_forward(deterministic=False, action_out=self._expert_action)
+        if self.cfg["agent_policy"] == "AIProtectPolicy":     # the saver looks at the agents' actions on the state the previous step left
+            actions = self.ai_protect_forward(actions.reshape(self.E, 2) if actions.dim() == 3 else actions, noise=noise)
         a = actions
         if a.dim() == 2:
             a = a.unsqueeze(1)

@@ -121,6 +121,11 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
             self.engine.rebuild(self.config)
         self.lazy_init()
         self.engine.reset()        # a walk: every env back to episode 0 of its walk
+        if self.config["agent_policy"] == "AIProtectPolicy":     # BaseVehicle.reset (base_vehicle.py:361,367)
+            self.engine.state_dev["takeover"].zero_()
+            self.engine.state_dev["expert_takeover"].zero_()
+            if getattr(self.engine, "protect_flags", None) is not None:
+                self.engine.protect_flags.zero_()
         return self._obs(), self._info()
 
     def step(self, actions):
@@ -131,6 +136,32 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
             self.engine.step(self._coerce_actions(actions, (self.num_envs, ), self.config["discrete_action"]))
         terminated, truncated = self._done_flags()
         return self._obs(), self.engine.reward[:, 0], terminated, truncated, self._info()
+
+    # -- agent_policy = AIProtectPolicy: vehicle.expert_takeover of every env (include/md_ai_protect.h) --------------------
+    @property
+    def expert_takeover(self):
+        """[E] bool tensor on the device (a copy): the envs whose wheel the expert holds outright.  Cleared by reset() and by an
+        env's auto-reset."""
+        self._require_protect("expert_takeover")
+        return self.engine.state_dev["expert_takeover"].bool()
+
+    def set_expert_takeover(self, mask, envs=None):
+        """vehicle.expert_takeover = mask (ManualControlPolicy.toggle_takeover sets it in the reference): one bool, or one per
+        chosen env; `envs`: indices (None: every env)."""
+        self._require_protect("set_expert_takeover")
+        torch = self.engine.torch
+        m = torch.as_tensor(mask, device=self.engine.device).to(torch.uint8).ne(0).to(torch.uint8)
+        et = self.engine.state_dev["expert_takeover"]
+        if envs is None:
+            et.copy_(m.expand(self.num_envs))
+        else:
+            idx = torch.as_tensor(envs, dtype=torch.long, device=self.engine.device).reshape(-1)
+            et[idx] = m.expand(idx.numel())
+
+    def _require_protect(self, what):
+        if self.config["agent_policy"] != "AIProtectPolicy":
+            raise ValueError("{} belongs to agent_policy='AIProtectPolicy'".format(what))
+        self._require_engine(what)
 
     # -- record / replay of the traffic (RecordManager / ReplayManager / ReplayTrafficParticipantPolicy) ------------
     def start_recording(self, max_steps):
@@ -221,8 +252,16 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
         }
         lazy = self._flag_info(fl)
         lazy["env_seed"] = self._env_seed_tensor
+        if self.config["agent_policy"] == "AIProtectPolicy":     # AIProtectPolicy.action_info (AI_protect_policy.py:54-58)
+            for k, bit in (("takeover", abi.AIP_TAKEOVER), ("takeover_start", abi.AIP_TAKEOVER_START), ("takeover_end", abi.AIP_TAKEOVER_END)):
+                lazy[k] = (lambda bit=bit: self._protect_flags() & bit != 0)
         lazy["scenario_index"] = self._scenario_index
         return LazyInfo(eager, lazy)
+
+    def _protect_flags(self):
+        e = self.engine
+        fl = getattr(e, "protect_flags", None)      # None before the first step: nothing reported yet
+        return fl if fl is not None else e.torch.zeros(self.num_envs, dtype=e.torch.uint8, device=e.device)
 
     def _scenario_index(self):
         """[E] int64: each env's position in the slice [start_seed, start_seed + num_scenarios).  A walk: MdState.scene_of, on the

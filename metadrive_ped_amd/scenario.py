@@ -73,8 +73,8 @@ def make_scenario_config(user=None):
     pol = user.get("agent_policy", "EnvInputPolicy")
     pol = pol if isinstance(pol, str) else getattr(pol, "__name__", repr(pol))
     ego_replay = pol == "ReplayEgoCarPolicy"
-    if pol == "ExpertPolicy":
-        raise NotImplementedError("agent_policy=ExpertPolicy: not in BatchedScenarioEnv (single-agent PG envs only)")
+    if pol in ("ExpertPolicy", "AIProtectPolicy"):
+        raise NotImplementedError("agent_policy={}: not in BatchedScenarioEnv (single-agent PG envs only)".format(pol))
     if pol == "LaneChangePolicy":
         raise NotImplementedError("agent_policy=LaneChangePolicy needs a road network's lanes: not in BatchedScenarioEnv "
                                   "(EnvInputPolicy, ReplayEgoCarPolicy)")
