@@ -93,6 +93,14 @@ __host__ __device__ constexpr uint32_t align_up(uint32_t b, uint32_t a) { return
 __device__ __forceinline__ float bcast_f(float v, int src) { return __shfl(v, src, 64); }
 __device__ __forceinline__ int bcast_i(int v, int src) { return __shfl(v, src, 64); }
 
+// One wave's LDS hand-over: what its lanes wrote before is visible to all of its lanes after.  The LDS unit executes a wave's
+// ds_write / ds_read in order; the fences keep the compiler from moving reads above the other lanes' writes.
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // The env state is read once and written once per step: streaming accesses (the nt hint keeps them from displacing the map
 // tables -- read again next step by the same env, on the same XCD -- from L2).  Measured: workgroup kernel 88.6 -> 86.7 us,
 // wave kernel on 4096 distinct maps 93.5 -> 89.0 us (-DMD_NT_STAGE=0 switches the hint off).
@@ -314,19 +322,45 @@ __device__ __forceinline__ void detector_drain(const MdWorld& w, const MdShape& 
     }
 }
 
-__device__ __forceinline__ void detector_wave(const MdWorld& w, const MdShape& me, int qa, int qb, const float* beam_cs, int n_beams,
-                              float range, uint32_t kind_mask, int* best, int* pairs, int lane_id) {
-    const float reach = range * 1.001f;
-    // is the table a uniform fan?  beam i = (cos, sin)(phase0 + i 2 pi / n): one lane per beam compares
+// is the table a uniform fan?  beam i = (cos, sin)(phase0 + i 2 pi / n): one lane per beam compares
+__device__ __forceinline__ bool detector_uniform_fan(const float* beam_cs, int n_beams, int lane_id, float* phase0_out) {
     const float phase0 = atan2f(beam_cs[1], beam_cs[0]);
-    const float dphi = 6.283185307179586f / (float)n_beams, inv_dphi = 1.0f / dphi;
+    const float dphi = 6.283185307179586f / (float)n_beams;
     bool fan_ok = true;
     for (int i = lane_id; i < n_beams; i += 64) {
         float sn, cs;
         sincosf(phase0 + (float)i * dphi, &sn, &cs);
         fan_ok = fan_ok && md_fabs(cs - beam_cs[2 * i]) < 1.0e-3f && md_fabs(sn - beam_cs[2 * i + 1]) < 1.0e-3f;
     }
-    const bool uniform_fan = __ballot(!fan_ok) == 0ull && n_beams >= 4;
+    *phase0_out = phase0;
+    return __ballot(!fan_ok) == 0ull && n_beams >= 4;
+}
+
+// Which beams can meet a quad at all?  For a uniform fan (beam i at phase0 + i dphi from the heading -- every detector table
+// is one; the callers check, else all beams are tried) only those within asin(r / d) of the direction to the quad's centre
+// (px, py from the agent, circle radius rr): a handful instead of all 12 ... 72, n_try of them from beam i_lo on, cyclically.
+// Hardware atan2 / asin are good enough here, a margin covers them and the exact circle test follows anyway.  An agent
+// inside the circle keeps the all-beams window that the caller set.
+__device__ __forceinline__ void detector_beam_window(const MdShape& me, float px, float py, float rr, float phase0, float inv_dphi,
+                                                     int n_beams, int& i_lo, int& n_try) {
+    const float d2 = px * px + py * py;
+    if (d2 > rr * rr * 1.0201f) {
+        const float lx = px * me.c + py * me.s, ly = py * me.c - px * me.s;   // the centre in the agent's frame
+        const float half = asinf(md_min(rr * 1.01f * rsqrtf(d2), 1.0f)) + 0.02f;
+        float rel = atan2f(ly, lx) - phase0;
+        const float lo = (rel - half) * inv_dphi, hi = (rel + half) * inv_dphi;
+        i_lo = (int)floorf(lo);
+        n_try = min((int)ceilf(hi) - i_lo + 1, n_beams);
+        i_lo = ((i_lo % n_beams) + n_beams) % n_beams;
+    }
+}
+
+__device__ __forceinline__ void detector_wave(const MdWorld& w, const MdShape& me, int qa, int qb, const float* beam_cs, int n_beams,
+                              float range, uint32_t kind_mask, int* best, int* pairs, int lane_id) {
+    const float reach = range * 1.001f;
+    float phase0 = 0.0f;
+    const bool uniform_fan = detector_uniform_fan(beam_cs, n_beams, lane_id, &phase0);
+    const float inv_dphi = 1.0f / (6.283185307179586f / (float)n_beams);
     int cnt = 0;   // wave-uniform
     // the 16-byte records of the NEXT 64 quads are requested before this round's are worked on: the rounds are a dependent chain
     // (ballot, pair list), and a cold fetch per round was most of the phase
@@ -348,23 +382,8 @@ __device__ __forceinline__ void detector_wave(const MdWorld& w, const MdShape& m
             near = ((kind_mask >> b.kind) & 1u) && !(px * px + py * py > far * far);
         }
         if (__ballot(near) == 0ull) continue;
-        // Which beams can meet this quad at all?  For a uniform fan (beam i at phase0 + i dphi from the heading -- every
-        // detector table is one; checked below, else all beams are tried) only those within asin(r / d) of the direction
-        // to the quad's centre: a handful instead of all 12 ... 72.  Hardware atan2 / asin are good enough here, a margin
-        // covers them and the exact circle test follows anyway.
-        int i_lo = 0, n_try = n_beams;
-        if (uniform_fan && near) {
-            const float d2 = px * px + py * py;
-            if (d2 > rr * rr * 1.0201f) {
-                const float lx = px * me.c + py * me.s, ly = py * me.c - px * me.s;   // the centre in the agent's frame
-                const float half = asinf(md_min(rr * 1.01f * rsqrtf(d2), 1.0f)) + 0.02f;
-                float rel = atan2f(ly, lx) - phase0;
-                const float lo = (rel - half) * inv_dphi, hi = (rel + half) * inv_dphi;
-                i_lo = (int)floorf(lo);
-                n_try = min((int)ceilf(hi) - i_lo + 1, n_beams);
-                i_lo = ((i_lo % n_beams) + n_beams) % n_beams;
-            }
-        }
+        int i_lo = 0, n_try = n_beams;   // the beams that can meet this quad
+        if (uniform_fan && near) detector_beam_window(me, px, py, rr, phase0, inv_dphi, n_beams, i_lo, n_try);
         int max_try = near ? n_try : 0;
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) max_try = max(max_try, __shfl_xor(max_try, off, 64));
@@ -379,9 +398,7 @@ __device__ __forceinline__ void detector_wave(const MdWorld& w, const MdShape& m
             const unsigned long long m = __ballot(pass);
             if (m == 0ull) continue;
             if (cnt + 64 > kDetPairs) {   // keep room for a whole ballot
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_sync();
                 detector_drain(w, me, beam_cs, range, pairs, cnt, qa, best, lane_id);
                 __builtin_amdgcn_wave_barrier();
                 cnt = 0;
@@ -390,9 +407,7 @@ __device__ __forceinline__ void detector_wave(const MdWorld& w, const MdShape& m
             cnt += __popcll(m);
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     detector_drain(w, me, beam_cs, range, pairs, cnt, qa, best, lane_id);
     __builtin_amdgcn_wave_barrier();
 }
@@ -428,20 +443,6 @@ __device__ __forceinline__ void detector_drain2(const MdWorld& w, const MdShape&
     }
 }
 
-// is the table a uniform fan?  beam i = (cos, sin)(phase0 + i 2 pi / n): one lane per beam compares
-__device__ __forceinline__ bool detector_uniform_fan(const float* beam_cs, int n_beams, int lane_id, float* phase0_out) {
-    const float phase0 = atan2f(beam_cs[1], beam_cs[0]);
-    const float dphi = 6.283185307179586f / (float)n_beams;
-    bool fan_ok = true;
-    for (int i = lane_id; i < n_beams; i += 64) {
-        float sn, cs;
-        sincosf(phase0 + (float)i * dphi, &sn, &cs);
-        fan_ok = fan_ok && md_fabs(cs - beam_cs[2 * i]) < 1.0e-3f && md_fabs(sn - beam_cs[2 * i + 1]) < 1.0e-3f;
-    }
-    *phase0_out = phase0;
-    return __ballot(!fan_ok) == 0ull && n_beams >= 4;
-}
-
 __device__ __forceinline__ void detector_wave2(const MdWorld& w, const MdShape& me, int qa, int qb, const DetFan2& f, int* pairs, int lane_id) {
     float ph0 = 0.0f, ph1 = 0.0f;
     const bool uni0 = detector_uniform_fan(f.cs0, f.n0, lane_id, &ph0);
@@ -463,9 +464,7 @@ __device__ __forceinline__ void detector_wave2(const MdWorld& w, const MdShape& 
     int n_near = 0;                    // wave-uniform
     const bool across_rounds = f.n0 > kAllBeamsMax || f.n1 > kAllBeamsMax;
     auto work_off = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     for (int t0 = 0; t0 < n_near; t0 += 64) {
         const bool in_reach = t0 + lane_id < n_near;
         const int q0 = qa + (in_reach ? near_list[t0 + lane_id] : 0);   // this lane's quad (no longer q0 + lane)
@@ -492,23 +491,9 @@ __device__ __forceinline__ void detector_wave2(const MdWorld& w, const MdShape& 
             const float far = reach + rr;
             const bool near = in_reach && ((kind_mask >> b.kind) & 1u) && !(px * px + py * py > far * far);
             if (__ballot(near) == 0ull) continue;
-            // Which beams can meet this quad at all?  For a uniform fan (beam i at phase0 + i dphi from the heading -- every
-            // detector table is one; checked above, else all beams are tried) only those within asin(r / d) of the direction
-            // to the quad's centre: a handful instead of all 12 ... 72.  Hardware atan2 / asin are good enough here, a margin
-            // covers them and the exact circle test follows anyway.
-            int i_lo = 0, n_try = n_beams;
-            if (uniform_fan && near && n_beams > kAllBeamsMax) {   // a handful of beams: trying all costs less than asin + atan2
-                const float d2 = px * px + py * py;
-                if (d2 > rr * rr * 1.0201f) {
-                    const float lx = px * me.c + py * me.s, ly = py * me.c - px * me.s;   // the centre in the agent's frame
-                    const float half = asinf(md_min(rr * 1.01f * rsqrtf(d2), 1.0f)) + 0.02f;
-                    float rel = atan2f(ly, lx) - phase0;
-                    const float lo = (rel - half) * inv_dphi, hi = (rel + half) * inv_dphi;
-                    i_lo = (int)floorf(lo);
-                    n_try = min((int)ceilf(hi) - i_lo + 1, n_beams);
-                    i_lo = ((i_lo % n_beams) + n_beams) % n_beams;
-                }
-            }
+            int i_lo = 0, n_try = n_beams;   // the beams that can meet this quad
+            if (uniform_fan && near && n_beams > kAllBeamsMax)   // a handful of beams: trying all costs less than asin + atan2
+                detector_beam_window(me, px, py, rr, phase0, inv_dphi, n_beams, i_lo, n_try);
             // The (quad, beam) candidates of this round, FLAT: lane t of a pass takes candidate t -- beam k of the quad in the lane l
             // that owns it (the largest l whose exclusive prefix count is <= t: a six-step search through the wave's registers).
             // A loop over k as long as the NEAREST quad needs (up to all 72 beams, one lane busy) ran 5x as many passes.
@@ -544,9 +529,7 @@ __device__ __forceinline__ void detector_wave2(const MdWorld& w, const MdShape& 
                 const unsigned long long m = __ballot(pass);
                 if (m == 0ull) continue;
                 if (cnt + 64 > kPairs) {   // keep room for a whole ballot
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_lds_sync();
                     detector_drain2(w, me, f, pair_list, cnt, qa, lane_id);
                     __builtin_amdgcn_wave_barrier();
                     cnt = 0;
@@ -577,9 +560,7 @@ __device__ __forceinline__ void detector_wave2(const MdWorld& w, const MdShape& 
         if (!across_rounds) work_off();   // fans of a few beams: round by round (measured: collecting across rounds costs them 1 %)
     }
     work_off();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     detector_drain2(w, me, f, pair_list, cnt, qa, lane_id);
     __builtin_amdgcn_wave_barrier();
 }
@@ -662,6 +643,48 @@ __device__ __forceinline__ int grid_clampi(int v, int lo, int hi) { return v < l
 // ------------------------------------------------------------------------------------------------
 // Localisation, one wave per vehicle.
 // ------------------------------------------------------------------------------------------------
+// pass B for one candidate lane L that contains the point (cx, cy; heading c, s): Frenet coordinates, heading filter, L1
+// distance.  dist / road stay as the caller set them (3.0e38f / -1) for a lane that fails the heading filter.
+__device__ __forceinline__ void localize_candidate(const MdLane* L, float cx, float cy, float c, float s, float& dist, float& ls,
+                                                   int& road) {
+    float llat;
+    md_lane_local(L, cx, cy, &ls, &llat);
+    if (md_lane_heading_dot(L, cx, cy, c, s) > 0.0f) {
+        dist = md_lane_distance(L, ls, llat);
+        road = L->road;
+    }
+}
+
+// Commit of vehicle n by ONE lane: its lane (the caller's choice by preference, ls the longitudinal on it; -1: the previous lane
+// stays) and the route cursors' advance within the first 5 m of a lane whose road starts at a later route node.  nav_*: the
+// vehicle's MdNav fields before the step; rroads / rnodes: its route (global: read only when the cursors advance).
+__device__ __forceinline__ void localize_commit(const MdLane* lanes, const MdRoad* roads, const MdState& s, int n, int lane, float ls,
+                                                float cx, float cy, int nav_lane, int nav_ck0, int nav_ck1,
+                                                int nav_route_len, const int32_t* rroads, const int32_t* rnodes) {
+    const bool kept = lane < 0;  // found nothing: the previous lane stays, its longitudinal was not evaluated above
+    if (kept) lane = nav_lane;
+    s.nav[n].lane = lane;
+    if (lane < 0) return;
+    if (nav_ck0 == nav_ck1) return;
+    if (kept) {
+        float llat;
+        md_lane_local(&lanes[lane], cx, cy, &ls, &llat);
+    }
+    if (!(ls < 5.0f)) return;
+    const int start_node = roads[lanes[lane].road].start_node;
+    const int k = nav_route_len;
+    int idx = -1;
+    for (int j = nav_ck1; j < k - 1; ++j) {
+        if (rnodes[j] == start_node) { idx = j; break; }
+    }
+    if (idx < 0) return;
+    const int nck1 = (idx + 1 == k - 1) ? idx : idx + 1;
+    s.nav[n].ck0 = idx;
+    s.nav[n].ck1 = nck1;
+    s.nav[n].road0 = rroads[idx];
+    s.nav[n].road1 = rroads[nck1];
+}
+
 // onlane_out: nullptr = write the ON_LANE bit into s.flags[n] (stand-alone phase); otherwise store the bare
 // decision there and leave s.flags alone (fused step: contacts run concurrently and own the other bits).
 __device__ __forceinline__ void localize_vehicle(const MdWorld& w, const MdLane* lanes, const MdRoad* roads, const MdState& s, int e,
@@ -737,15 +760,7 @@ __device__ __forceinline__ void localize_vehicle(const MdWorld& w, const MdLane*
         // pass B: my lane's candidate (if contained): Frenet coordinates, heading filter, L1 distance
         float my_dist = 3.0e38f, my_ls = 0.0f;
         int my_road = -1;
-        if ((inside >> lane_id) & 1ull) {
-            const MdLane* L = &lanes[l];
-            float llat;
-            md_lane_local(L, sh.cx, sh.cy, &my_ls, &llat);
-            if (md_lane_heading_dot(L, sh.cx, sh.cy, sh.c, sh.s) > 0.0f) {
-                my_dist = md_lane_distance(L, my_ls, llat);
-                my_road = L->road;
-            }
-        }
+        if ((inside >> lane_id) & 1ull) localize_candidate(&lanes[l], sh.cx, sh.cy, sh.c, sh.s, my_dist, my_ls, my_road);
         // pass C (the winner's longitudinal is kept: the checkpoint update below needs it)
         while (inside) {
             const int k = __ffsll((long long)inside) - 1;
@@ -775,28 +790,7 @@ __device__ __forceinline__ void localize_vehicle(const MdWorld& w, const MdLane*
         if (on_lane) fl |= MD_FL_ON_LANE;
         s.flags[n] = fl;
     }
-    const bool kept = lane < 0;  // found nothing: the previous lane stays, its longitudinal was not evaluated above
-    if (kept) lane = nav.lane;
-    s.nav[n].lane = lane;
-    if (lane < 0) return;
-    if (nav.ck0 == nav.ck1) return;
-    if (kept) {
-        float llat;
-        md_lane_local(&lanes[lane], sh.cx, sh.cy, &ls, &llat);
-    }
-    if (!(ls < 5.0f)) return;
-    const int start_node = roads[lanes[lane].road].start_node;
-    const int k = nav.route_len;
-    int idx = -1;
-    for (int j = nav.ck1; j < k - 1; ++j) {
-        if (rnodes[j] == start_node) { idx = j; break; }
-    }
-    if (idx < 0) return;
-    const int nck1 = (idx + 1 == k - 1) ? idx : idx + 1;
-    s.nav[n].ck0 = idx;
-    s.nav[n].ck1 = nck1;
-    s.nav[n].road0 = rroads[idx];
-    s.nav[n].road1 = rroads[nck1];
+    localize_commit(lanes, roads, s, n, lane, ls, sh.cx, sh.cy, nav.lane, nav.ck0, nav.ck1, nav.route_len, rroads, rnodes);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -882,15 +876,7 @@ __device__ __forceinline__ void localize_group(const MdWorld& w, const MdLane* l
         if (inside != 0u) on_lane = 1;
         float my_dist = 3.0e38f, my_ls = 0.0f;
         int my_road = -1;
-        if ((inside >> hl) & 1u) {
-            const MdLane* L = &lanes[l];
-            float llat;
-            md_lane_local(L, sh.cx, sh.cy, &my_ls, &llat);
-            if (md_lane_heading_dot(L, sh.cx, sh.cy, sh.c, sh.s) > 0.0f) {
-                my_dist = md_lane_distance(L, my_ls, llat);
-                my_road = L->road;
-            }
-        }
+        if ((inside >> hl) & 1u) localize_candidate(&lanes[l], sh.cx, sh.cy, sh.c, sh.s, my_dist, my_ls, my_road);
         while (__ballot(inside != 0u) != 0ull) {
             const bool mine = inside != 0u;
             const int k = mine ? (__ffs((int)inside) - 1) : 0;
@@ -913,28 +899,7 @@ __device__ __forceinline__ void localize_group(const MdWorld& w, const MdLane* l
     else if (best_next >= 0) { lane = best_next; ls = ls_next; }
     else { lane = best_any; ls = ls_any; }
     onlane_out[n] = on_lane ? MD_FL_ON_LANE : 0u;
-    const bool kept = lane < 0;  // found nothing: the previous lane stays, its longitudinal was not evaluated above
-    if (kept) lane = nav.lane;
-    s.nav[n].lane = lane;
-    if (lane < 0) return;
-    if (nav.ck0 == nav.ck1) return;
-    if (kept) {
-        float llat;
-        md_lane_local(&lanes[lane], sh.cx, sh.cy, &ls, &llat);
-    }
-    if (!(ls < 5.0f)) return;
-    const int start_node = roads[lanes[lane].road].start_node;
-    const int kk = nav.route_len;
-    int idx = -1;
-    for (int j = nav.ck1; j < kk - 1; ++j) {
-        if (rnodes[j] == start_node) { idx = j; break; }
-    }
-    if (idx < 0) return;
-    const int nck1 = (idx + 1 == kk - 1) ? idx : idx + 1;
-    s.nav[n].ck0 = idx;
-    s.nav[n].ck1 = nck1;
-    s.nav[n].road0 = rroads[idx];
-    s.nav[n].road1 = rroads[nck1];
+    localize_commit(lanes, roads, s, n, lane, ls, sh.cx, sh.cy, nav.lane, nav.ck0, nav.ck1, nav.route_len, rroads, rnodes);
 }
 
 __device__ __forceinline__ void localize_pair(const MdWorld& w, const MdLane* lanes, const MdRoad* roads, const MdState& s, int e,
@@ -1049,12 +1014,6 @@ __device__ __forceinline__ float gap_of_key(unsigned long long k) {
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Reads the six minima back into fb (wave-uniform); returns bit i*2 (front) / i*2+1 (back) for every bucket that holds one.
 __device__ __forceinline__ int gap_keys_read(const unsigned long long* keys, FrontBack& fb) {
     int found = 0;
@@ -1090,18 +1049,97 @@ __device__ __forceinline__ void wave_argmin(float& key, int& slot) {
     slot = bs;
 }
 
+// Nothing found on any scanned lane, and no lane scanned yet (the scans set exist[] from their plan).
+__device__ __forceinline__ void front_back_clear(FrontBack& fb) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        fb.front[i] = fb.back[i] = -1;
+        fb.exist[i] = 0;
+        fb.front_d[i] = fb.back_d[i] = IDM_MAX_LONG_DIST;
+    }
+}
+
+// The candidate objects of the vehicle in `slot` at (px, py) (get_surrounding_objects: within 50 m, present, not the vehicle
+// itself), compacted in ascending slot order into wave_list: usually a handful, whatever the slot capacity is.  Returns their
+// number (wave-uniform); only the first 21 are listed.  The caller syncs the wave's LDS before it reads wave_list.
+__device__ __forceinline__ int idm_candidates_wave(const MdState& s, const MdConfig& c, int slot, int lane_id, float px, float py,
+                                                   int* wave_list, MdIdmPlan& plan) {
+    int n_cand = 0;
+    bool sees_participant = false;  // a pedestrian / cyclist among them: the reference's object loop raises (md_idm_sees_participant)
+    for (int j0 = 0; j0 < c.cap; j0 += 64) {
+        const int j = j0 + lane_id;
+        const bool is_c = j < c.cap && j != slot && md_idm_is_candidate(&s.shape[j < c.cap ? j : 0], px, py);
+        const unsigned long long mk = __ballot(is_c);
+        if (__ballot(is_c && md_is_participant_kind(md_kind_of(s.shape[j < c.cap ? j : 0].flags))) != 0ull) sees_participant = true;
+        const int rank = n_cand + __popcll(mk & ((1ull << lane_id) - 1ull));
+        if (is_c && rank < 21) wave_list[rank] = j;
+        n_cand += __popcll(mk);
+    }
+    if (sees_participant) {  // wave-uniform: bare-except fallback, nothing is scanned
+        plan.fail = 1;
+        n_cand = 0;
+    }
+    return n_cand;
+}
+
+// More than 21 candidates (three pairs each no longer fit the wave), the general capacity: per scanned lane, lanes = objects
+// (two passes, chunks of 64 objects), arg-min walks.
+__device__ __forceinline__ void idm_scan_walks(const MdLane* lanes, const MdState& s, const MdConfig& c, int slot, int lane_id, float px,
+                                               float py, const MdIdmPlan& plan, const float (&cur_long)[3],
+                                               const float (&left_long)[3], FrontBack& fb) {
+    constexpr float kInf = 3.0e38f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        if (plan.ids[i] < 0) continue;  // wave-uniform
+        const MdLane* L = &lanes[plan.ids[i]];
+        int found_front = 0, found_back = 0;
+        for (int j0 = 0; j0 < c.cap; j0 += 64) {
+            const int j = j0 + lane_id;
+            float kf = kInf, kb = kInf;
+            if (j < c.cap && j != slot && md_idm_is_candidate(&s.shape[j], px, py) &&
+                md_obj_lane_of(&s, j) == plan.ids[i]) {
+                const float lg = md_fb_same_lane_gap(L, cur_long[i], &s.shape[j]);
+                if (lg > 0.0f && lg < IDM_MAX_LONG_DIST) kf = lg;
+                if (lg < 0.0f && md_fabs(lg) < IDM_MAX_LONG_DIST) kb = md_fabs(lg);
+            }
+            int jf = j, jb = j;
+            wave_argmin(kf, jf);
+            wave_argmin(kb, jb);
+            if (kf < fb.front_d[i]) { fb.front_d[i] = kf; fb.front[i] = jf; found_front = 1; }
+            if (kb < fb.back_d[i]) { fb.back_d[i] = kb; fb.back[i] = jb; found_back = 1; }
+        }
+        if (found_front && found_back) continue;
+        for (int j0 = 0; j0 < c.cap; j0 += 64) {
+            const int j = j0 + lane_id;
+            float kf = kInf, kb = kInf;
+            if (j < c.cap && j != slot && md_idm_is_candidate(&s.shape[j], px, py)) {
+                const int ol = md_obj_lane_of(&s, j);
+                if (ol >= 0 && ol != plan.ids[i]) {
+                    float lg;
+                    const int cls = md_fb_neighbour(L, &lanes[ol], cur_long[i], left_long[i], &s.shape[j],
+                                                    !found_front, !found_back, &lg);
+                    if (cls == 1 && lg > 0.0f && lg < IDM_MAX_LONG_DIST) kf = lg;
+                    if (cls == 2 && lg < IDM_MAX_LONG_DIST) kb = lg;
+                }
+            }
+            int jf = j, jb = j;
+            wave_argmin(kf, jf);
+            wave_argmin(kb, jb);
+            if (kf < fb.front_d[i]) { fb.front_d[i] = kf; fb.front[i] = jf; }
+            if (kb < fb.back_d[i]) { fb.back_d[i] = kb; fb.back[i] = jb; }
+        }
+    }
+}
+
 // The object scan of one vehicle by the whole wave.  `plan` is wave-uniform (may come back with fail = 1: a traffic
 // participant among the candidates), `fb` is the wave-uniform result.
 // wave_list: >= 24 ints of LDS private to this wave (the compacted candidate list)
 __device__ __forceinline__ void idm_scan_wave(const MdLane* lanes, const MdState& s, const MdConfig& c, int slot, int lane_id,
                               int* wave_list, MdIdmPlan& plan, FrontBack& fb) {
     constexpr float kInf = 3.0e38f;
+    front_back_clear(fb);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        fb.front[i] = fb.back[i] = -1;
-        fb.exist[i] = plan.ids[i] >= 0 && !plan.fail;
-        fb.front_d[i] = fb.back_d[i] = IDM_MAX_LONG_DIST;
-    }
+    for (int i = 0; i < 3; ++i) fb.exist[i] = plan.ids[i] >= 0 && !plan.fail;
     if (!plan.fail) {
         const float px = s.shape[slot].cx, py = s.shape[slot].cy;
         // (1) ego longitudinal on the three scanned lanes: lanes 0..2 evaluate one each, then broadcast
@@ -1119,26 +1157,8 @@ __device__ __forceinline__ void idm_scan_wave(const MdLane* lanes, const MdState
             cur_long[i] = bcast_f(my_cur, i);
             left_long[i] = (plan.ids[i] >= 0) ? lanes[plan.ids[i]].length - cur_long[i] : 0.0f;
         }
-        // candidate objects (get_surrounding_objects: within 50 m, present, not the vehicle itself), compacted in
-        // ascending slot order into wave_list: usually a handful, whatever the slot capacity is
-        int n_cand = 0;
-        bool sees_participant = false;  // a pedestrian / cyclist among them: the reference's object loop raises (md_idm_sees_participant)
-        for (int j0 = 0; j0 < c.cap; j0 += 64) {
-            const int j = j0 + lane_id;
-            const bool is_c = j < c.cap && j != slot && md_idm_is_candidate(&s.shape[j < c.cap ? j : 0], px, py);
-            const unsigned long long mk = __ballot(is_c);
-            if (__ballot(is_c && md_is_participant_kind(md_kind_of(s.shape[j < c.cap ? j : 0].flags))) != 0ull) sees_participant = true;
-            const int rank = n_cand + __popcll(mk & ((1ull << lane_id) - 1ull));
-            if (is_c && rank < 21) wave_list[rank] = j;
-            n_cand += __popcll(mk);
-        }
-        if (sees_participant) {  // wave-uniform: bare-except fallback, nothing is scanned
-            plan.fail = 1;
-            n_cand = 0;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int n_cand = idm_candidates_wave(s, c, slot, lane_id, px, py, wave_list, plan);
+        wave_lds_sync();
         const int npairs = n_cand * 3;
         if (npairs <= 63) {
             // (2) every (scanned lane i, candidate j) pair on its own lane of the wave: ONE Frenet evaluation
@@ -1205,48 +1225,7 @@ __device__ __forceinline__ void idm_scan_wave(const MdLane* lanes, const MdState
                 if (kb < fb.back_d[i]) { fb.back_d[i] = kb; fb.back[i] = jb; }
             }
         } else {
-            // general capacity: per scanned lane, lanes = objects (two passes, chunks of 64 objects)
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                if (plan.ids[i] < 0) continue;  // wave-uniform
-                const MdLane* L = &lanes[plan.ids[i]];
-                int found_front = 0, found_back = 0;
-                for (int j0 = 0; j0 < c.cap; j0 += 64) {
-                    const int j = j0 + lane_id;
-                    float kf = kInf, kb = kInf;
-                    if (j < c.cap && j != slot && md_idm_is_candidate(&s.shape[j], px, py) &&
-                        md_obj_lane_of(&s, j) == plan.ids[i]) {
-                        const float lg = md_fb_same_lane_gap(L, cur_long[i], &s.shape[j]);
-                        if (lg > 0.0f && lg < IDM_MAX_LONG_DIST) kf = lg;
-                        if (lg < 0.0f && md_fabs(lg) < IDM_MAX_LONG_DIST) kb = md_fabs(lg);
-                    }
-                    int jf = j, jb = j;
-                    wave_argmin(kf, jf);
-                    wave_argmin(kb, jb);
-                    if (kf < fb.front_d[i]) { fb.front_d[i] = kf; fb.front[i] = jf; found_front = 1; }
-                    if (kb < fb.back_d[i]) { fb.back_d[i] = kb; fb.back[i] = jb; found_back = 1; }
-                }
-                if (found_front && found_back) continue;
-                for (int j0 = 0; j0 < c.cap; j0 += 64) {
-                    const int j = j0 + lane_id;
-                    float kf = kInf, kb = kInf;
-                    if (j < c.cap && j != slot && md_idm_is_candidate(&s.shape[j], px, py)) {
-                        const int ol = md_obj_lane_of(&s, j);
-                        if (ol >= 0 && ol != plan.ids[i]) {
-                            float lg;
-                            const int cls = md_fb_neighbour(L, &lanes[ol], cur_long[i], left_long[i], &s.shape[j],
-                                                            !found_front, !found_back, &lg);
-                            if (cls == 1 && lg > 0.0f && lg < IDM_MAX_LONG_DIST) kf = lg;
-                            if (cls == 2 && lg < IDM_MAX_LONG_DIST) kb = lg;
-                        }
-                    }
-                    int jf = j, jb = j;
-                    wave_argmin(kf, jf);
-                    wave_argmin(kb, jb);
-                    if (kf < fb.front_d[i]) { fb.front_d[i] = kf; fb.front[i] = jf; }
-                    if (kb < fb.back_d[i]) { fb.back_d[i] = kb; fb.back[i] = jb; }
-                }
-            }
+            idm_scan_walks(lanes, s, c, slot, lane_id, px, py, plan, cur_long, left_long, fb);   // more than 21 candidates
         }
     }
 }
@@ -1260,12 +1239,9 @@ __device__ __forceinline__ void idm_scan_wave(const MdLane* lanes, const MdState
 __device__ __forceinline__ void idm_scan_wave_keys(const MdLane* lanes, const MdState& s, const MdConfig& c, int slot, int lane_id,
                                    int* wave_list, MdIdmPlan& plan, FrontBack& fb) {
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(wave_list + kIdmKeyWord);
+    front_back_clear(fb);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        fb.front[i] = fb.back[i] = -1;
-        fb.exist[i] = plan.ids[i] >= 0 && !plan.fail;
-        fb.front_d[i] = fb.back_d[i] = IDM_MAX_LONG_DIST;
-    }
+    for (int i = 0; i < 3; ++i) fb.exist[i] = plan.ids[i] >= 0 && !plan.fail;
     if (!plan.fail) {
         const float px = s.shape[slot].cx, py = s.shape[slot].cy;
         // (1) ego Frenet coordinates on the three scanned lanes: lanes 0..2 evaluate one each, then broadcast
@@ -1288,23 +1264,7 @@ __device__ __forceinline__ void idm_scan_wave_keys(const MdLane* lanes, const Md
             cur_long[i] = bcast_f(my_cur, i);
             left_long[i] = (plan.ids[i] >= 0) ? bcast_f(my_left, i) : 0.0f;
         }
-        // candidate objects (get_surrounding_objects: within 50 m, present, not the vehicle itself), compacted in
-        // ascending slot order into wave_list: usually a handful, whatever the slot capacity is
-        int n_cand = 0;
-        bool sees_participant = false;  // a pedestrian / cyclist among them: the reference's object loop raises (md_idm_sees_participant)
-        for (int j0 = 0; j0 < c.cap; j0 += 64) {
-            const int j = j0 + lane_id;
-            const bool is_c = j < c.cap && j != slot && md_idm_is_candidate(&s.shape[j < c.cap ? j : 0], px, py);
-            const unsigned long long mk = __ballot(is_c);
-            if (__ballot(is_c && md_is_participant_kind(md_kind_of(s.shape[j < c.cap ? j : 0].flags))) != 0ull) sees_participant = true;
-            const int rank = n_cand + __popcll(mk & ((1ull << lane_id) - 1ull));
-            if (is_c && rank < 21) wave_list[rank] = j;
-            n_cand += __popcll(mk);
-        }
-        if (sees_participant) {  // wave-uniform: bare-except fallback, nothing is scanned
-            plan.fail = 1;
-            n_cand = 0;
-        }
+        const int n_cand = idm_candidates_wave(s, c, slot, lane_id, px, py, wave_list, plan);
         wave_lds_sync();
         if (n_cand == 0) return;
         const int npairs = n_cand * 3;
@@ -1371,50 +1331,7 @@ __device__ __forceinline__ void idm_scan_wave_keys(const MdLane* lanes, const Md
                 }
             }
         } else {
-            // general capacity: per scanned lane, lanes = objects (two passes, chunks of 64 objects), arg-min walks as in
-            // idm_scan_wave
-            constexpr float kInf = 3.0e38f;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                if (plan.ids[i] < 0) continue;  // wave-uniform
-                const MdLane* L = &lanes[plan.ids[i]];
-                int found_front = 0, found_back = 0;
-                for (int j0 = 0; j0 < c.cap; j0 += 64) {
-                    const int j = j0 + lane_id;
-                    float kf = kInf, kb = kInf;
-                    if (j < c.cap && j != slot && md_idm_is_candidate(&s.shape[j], px, py) &&
-                        md_obj_lane_of(&s, j) == plan.ids[i]) {
-                        const float lg = md_fb_same_lane_gap(L, cur_long[i], &s.shape[j]);
-                        if (lg > 0.0f && lg < IDM_MAX_LONG_DIST) kf = lg;
-                        if (lg < 0.0f && md_fabs(lg) < IDM_MAX_LONG_DIST) kb = md_fabs(lg);
-                    }
-                    int jf = j, jb = j;
-                    wave_argmin(kf, jf);
-                    wave_argmin(kb, jb);
-                    if (kf < fb.front_d[i]) { fb.front_d[i] = kf; fb.front[i] = jf; found_front = 1; }
-                    if (kb < fb.back_d[i]) { fb.back_d[i] = kb; fb.back[i] = jb; found_back = 1; }
-                }
-                if (found_front && found_back) continue;
-                for (int j0 = 0; j0 < c.cap; j0 += 64) {
-                    const int j = j0 + lane_id;
-                    float kf = kInf, kb = kInf;
-                    if (j < c.cap && j != slot && md_idm_is_candidate(&s.shape[j], px, py)) {
-                        const int ol = md_obj_lane_of(&s, j);
-                        if (ol >= 0 && ol != plan.ids[i]) {
-                            float lg;
-                            const int cls = md_fb_neighbour(L, &lanes[ol], cur_long[i], left_long[i], &s.shape[j],
-                                                            !found_front, !found_back, &lg);
-                            if (cls == 1 && lg > 0.0f && lg < IDM_MAX_LONG_DIST) kf = lg;
-                            if (cls == 2 && lg < IDM_MAX_LONG_DIST) kb = lg;
-                        }
-                    }
-                    int jf = j, jb = j;
-                    wave_argmin(kf, jf);
-                    wave_argmin(kb, jb);
-                    if (kf < fb.front_d[i]) { fb.front_d[i] = kf; fb.front[i] = jf; }
-                    if (kb < fb.back_d[i]) { fb.back_d[i] = kb; fb.back[i] = jb; }
-                }
-            }
+            idm_scan_walks(lanes, s, c, slot, lane_id, px, py, plan, cur_long, left_long, fb);   // more than 21 candidates
         }
     }
 }
@@ -1492,12 +1409,7 @@ __device__ __forceinline__ void idm_group_wave(const MdWorld& w, const MdLane* l
     plan.ids[0] = plan.ids[1] = plan.ids[2] = -1;
     if (mine) md_idm_plan(&w, lanes, roads, &s, &c, m, my_slot, &plan);
     FrontBack fb;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        fb.front[i] = fb.back[i] = -1;
-        fb.exist[i] = 0;
-        fb.front_d[i] = fb.back_d[i] = IDM_MAX_LONG_DIST;
-    }
+    front_back_clear(fb);
     unsigned long long todo = mask;
     while (todo) {
         const int v = __ffsll((long long)todo) - 1;
@@ -1511,9 +1423,7 @@ __device__ __forceinline__ void idm_group_wave(const MdWorld& w, const MdLane* l
         up.ids[2] = bcast_i(plan.ids[2], v);
         FrontBack ufb;
         idm_scan_wave(lanes, s, c, j0 + v, lane_id, wave_list, up, ufb);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the next scan reuses wave_list
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();   // the next scan reuses wave_list
         if (lane_id == v) {
             plan.fail = up.fail;
             fb = ufb;
@@ -1539,9 +1449,7 @@ __device__ __forceinline__ void observe_agent_wave1(const MdLane* lanes, const M
 #pragma unroll
         for (int i = 0; i < 5; ++i) wave_scratch[lane_id * 5 + i] = mine[i];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     MD_FINE_STAMP(a == 0 && lane_id == 0, 10);
     if (lane_id == 0) md_observe_combine(&k, &s, &c, a, just_reset, (const float (*)[5])wave_scratch);
     __builtin_amdgcn_wave_barrier();
@@ -1569,9 +1477,7 @@ __device__ __forceinline__ void observe_agent_wave(const MdLane* lanes, const Md
     }
     // same wave: the LDS unit executes a wave's ds_write / ds_read in order; the fence keeps the
     // compiler from moving the combining lanes' reads above the other lanes' writes
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     if (live && sub == 0) md_observe_combine(&k, &s, &c, a, just_reset, (const float (*)[5])scratch);
     __builtin_amdgcn_wave_barrier();
 }
@@ -2325,12 +2231,6 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
 #endif
 constexpr int kWaveEnvs = MD_WAVE_ENVS;   // envs (= waves) per workgroup
 
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // LDS image of one env (= one wave) in wave_step_kernel; the images of a workgroup's envs follow each other every `bytes`
 struct WaveEnvLds { uint32_t shape, dyn, pid, param, nav, action, flags, final_lane, onlane, cfl, scratch, det, bytes; };
 __host__ __device__ inline WaveEnvLds wave_env_lds(int cap, int agents) {
@@ -2449,7 +2349,7 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
     const bool do_reset = reset_flag != 0;   // wave-uniform
     const int just_reset = do_reset ? 1 : 0;
     if (do_reset) {
-        wave_sync();
+        wave_lds_sync();
         const uint4* s0 = reinterpret_cast<const uint4*>(gv.shape0);
         const uint4* d0 = reinterpret_cast<const uint4*>(gv.dyn0);
         const uint4* p0 = reinterpret_cast<const uint4*>(gv.pid0);
@@ -2474,7 +2374,7 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
         }
     }
     MdState s = local_view(gv, img);   // env-local view whose hot arrays live in this wave's LDS image
-    wave_sync();
+    wave_lds_sync();
     MD_STAMP_AT(1);
 
     // agent_policy = IDMPolicy: the agents are planned like the traffic, in the reference's order (decide, then move);
@@ -2484,13 +2384,13 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
     const bool lane_change = RESPAWN && c.agent_idm == MD_AGENT_LANE_CHANGE;   // LaneChangePolicy: see env_kernel
     if (!just_reset && !plan_ahead) {
         trigger_env(lanes, s, c, lane);
-        wave_sync();
+        wave_lds_sync();
         for (int j0 = 0; j0 < cap; j0 += 64) {
             const int jj = j0 + lane;
             const unsigned long long mk = __ballot(jj < cap && md_drives(s.shape[jj < cap ? jj : 0].flags));
             if (mk) idm_group_wave(w, lanes, roads, s, c, m, j0, mk, lane, reinterpret_cast<int*>(l_scratch));
         }
-        wave_sync();
+        wave_lds_sync();
     }
     MD_STAMP_AT(3);
     // the slots that drive in this step (the integration does not change any slot's flags)
@@ -2507,7 +2407,7 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
         }
         if (!RESPAWN)
             for (int j = lane; j < cap; j += 64) md_walk_mover(&s, &c, j);
-        wave_sync();
+        wave_lds_sync();
     }
     MD_STAMP_AT(4);
     // ---- localisation of every driving vehicle, contacts of every driving agent ----
@@ -2524,7 +2424,7 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
                                    kth_bit(drv_lo, drv_hi, item + 2), kth_bit(drv_lo, drv_hi, item + 3), lane, l_onlane);
         for (int k = 0; k < na; ++k) contacts_vehicle(w, s, c, e, kth_bit(adrv_lo, adrv_hi, k), lane, l_cfl);
     }
-    wave_sync();
+    wave_lds_sync();
     MD_STAMP_AT(6);
     // ---- flags of the slots that drove; traffic that left every lane is removed ----
     for (int j = lane; j < cap; j += 64) {
@@ -2537,14 +2437,14 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
             l_cfl[j] = kRemovedMark;
         }
     }
-    wave_sync();
+    wave_lds_sync();
     if (plan_ahead) {   // next step's trigger: the agents' final lanes, the PENDING slots
         trigger_env(lanes, s, c, lane);
-        wave_sync();
+        wave_lds_sync();
     }
     if (RESPAWN) {   // respawn / hybrid: the removed vehicle re-enters on a respawn lane (rare; serial)
         if (lane == 0) md_traffic_respawn_env(&w, lanes, &s, &c, m);
-        wave_sync();
+        wave_lds_sync();
     }
     MD_STAMP_AT(7);
     // ---- next step's traffic decisions, then the agents' observations (disjoint data: either order gives the same) ----
@@ -2554,7 +2454,7 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
             const unsigned long long mk = __ballot(jj < cap && jj >= A && md_drives(s.shape[jj < cap ? jj : 0].flags) &&
                                                    !(s.shape[jj < cap ? jj : 0].flags & MD_F_AGENT));
             if (mk) idm_group_wave(w, lanes, roads, s, c, m, j0, mk, lane, reinterpret_cast<int*>(l_scratch));
-            wave_sync();
+            wave_lds_sync();
         }
     }
     MD_STAMP_AT(8);
@@ -2568,7 +2468,7 @@ __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, Md
             for (int sec = 0; sec < nsec; ++sec) lidar_item(w, s, c, a, sec, lane, row, track_det ? l_det + 2 * a : nullptr);
         }
     }
-    wave_sync();
+    wave_lds_sync();
     MD_STAMP_AT(10);
     // ---- write-back (16-byte stores) ----
     if (!do_reset) {
@@ -2994,7 +2894,7 @@ __device__ __forceinline__ void tidm_prepare_wave(const MdWorld& w, const MdStat
         // outline's bounding box (a point outside it is outside the outline).  The survivors go on the pair list; when the list
         // is full (never in practice: kPairCap pairs per scene) this wave works its pairs off itself, after publishing cur_long.
         if (lane_id == 0) dl.cur_long[slot] = cur_long;
-        wave_sync();
+        wave_lds_sync();
         for (int j0 = 0; j0 < c.cap; j0 += 64) {
             const int jl = j0 + lane_id;
             int want = 0;
@@ -3097,7 +2997,7 @@ __device__ __forceinline__ void build_route_wave(int32_t* rn, MdSeg* segs, int s
         ++nl;
         i = j;
     }
-    wave_sync();
+    wave_lds_sync();
     int ns = 0;
     for (int p0 = 0; p0 < nl; p0 += 64) {
         const int p = p0 + lane;
@@ -3117,7 +3017,7 @@ __device__ __forceinline__ void build_route_wave(int32_t* rn, MdSeg* segs, int s
         ns += __popcll(m);
     }
     __threadfence_block();
-    wave_sync();
+    wave_lds_sync();
     const int never_moved = ns == 0;
     if (lane == 0) {
         if (never_moved) {
@@ -3134,7 +3034,7 @@ __device__ __forceinline__ void build_route_wave(int32_t* rn, MdSeg* segs, int s
     }
     if (never_moved) ns = 1;
     __threadfence_block();
-    wave_sync();
+    wave_lds_sync();
     const int n_long = md_route_n_long(l_len[seg_cap]);
     const int nv = 2 * (n_long + 2);
     if (nv > vert_cap) {   // (the host sizes the buffers by the longest run: never) the slot keeps its static polyline
@@ -3513,7 +3413,7 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
             if (in) md_scenario_slot_after_step(&w, &s, &c, e, j, k, before, 0);
             __builtin_amdgcn_wave_barrier();
             if (lane == 0) *l_count += __popcll(m);
-            wave_sync();
+            wave_lds_sync();
             // a reactive policy created at a frame other than its first run's start: its route is cut at this frame.  Rare
             // (a few per scene and episode): the wave stages the run's remaining positions, lane 0 builds (md_build_route).
             unsigned long long mb = __ballot(in && s.route_n != nullptr && s.route_n[4 * (in ? j : 0) + 3] > 0);
@@ -3527,11 +3427,11 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
                     l_pts[2 * i] = fr.cx;
                     l_pts[2 * i + 1] = fr.cy;
                 }
-                wave_sync();
+                wave_lds_sync();
                 build_route_wave(s.route_n + 4 * jb, s.route_segs + (size_t)jb * c.route_seg_cap, c.route_seg_cap,
                                  s.route_verts + 2 * (size_t)jb * c.route_vert_cap, c.route_vert_cap, s.route_aux + 8 * (size_t)jb, l_pts, nb,
                                  l_link, l_len, lane);
-                wave_sync();
+                wave_lds_sync();
             }
         }
     }

@@ -440,6 +440,20 @@ def test_agent_policy_idm_rollout_parity(mode):
     assert (sp > 1.0).sum() > E // 2, "the agents are not driving"
 
 
+def _crowded_movers(state, E):
+    """Moving traffic vehicles (|speed| > 0.5) with more than 21 other present objects' centres within 48 m: every such object
+    touches the 50 m circle of md_idm_is_candidate, so the vehicle's IDM scan has more candidates than its pair form holds."""
+    from metadrive_ped_amd import abi
+    sh = state["shape"].reshape(E, -1)
+    fl = sh["flags"]
+    present = ((fl & abi.F_ALIVE) != 0) & ((fl & abi.KIND_MASK) != 0)
+    mover = present & ((fl & abi.KIND_MASK) == abi.KIND_VEHICLE) & ((fl & (abi.F_PENDING | abi.F_STATIC | abi.F_AGENT)) == 0) & \
+        (np.abs(state["dyn"]["speed"].reshape(E, -1)) > 0.5)
+    d = np.hypot(sh["cx"][:, :, None] - sh["cx"][:, None, :], sh["cy"][:, :, None] - sh["cy"][:, None, :])
+    around = ((d < 48.0) & present[:, None, :]).sum(2) - 1   # without the vehicle itself
+    return int((mover & (around > 21)).sum())
+
+
 @pytest.mark.parametrize("step_kernel", ["wave", "wg"])
 @pytest.mark.parametrize("name,cfg_kw,steps", [
     ("default_maps", dict(num_envs=48, num_scenarios=48, horizon=200), 260),
@@ -448,6 +462,8 @@ def test_agent_policy_idm_rollout_parity(mode):
     ("dense_many_awake", dict(num_envs=12, num_scenarios=12, map=5, traffic_density=0.5, horizon=300), 300),
     ("hybrid_idm_agent", dict(num_envs=16, num_scenarios=16, traffic_density=0.2, traffic_mode="hybrid", agent_policy="IDMPolicy",
                               horizon=250), 300),
+    # more than 21 candidates around a traffic vehicle: the IDM scans' arg-min walks ("general capacity"), which no other case reaches
+    ("four_lane_dense", dict(num_envs=4, num_scenarios=4, map="SS", map_config=dict(lane_num=4), traffic_density=0.9, horizon=300), 80),
 ])
 def test_alternative_step_kernels_parity(step_kernel, name, cfg_kw, steps):
     """The other machine mappings of md_step for single-agent envs (MdConfig.step_kernel): "wave" = one wave per env,
@@ -464,6 +480,7 @@ def test_alternative_step_kernels_parity(step_kernel, name, cfg_kw, steps):
     eng.reset()
     orc.reset()
     assert_state_equal(eng.download_state(), orc.state, where="%s/%s reset" % (step_kernel, name))
+    crowded = 0   # over the compared steps from step 40 on
     for t in range(steps):
         a = scripted_actions(E, 1, t, seed=31)
         a[:, :, 0] *= 0.4
@@ -472,4 +489,9 @@ def test_alternative_step_kernels_parity(step_kernel, name, cfg_kw, steps):
         orc.step(None if act is None else a)
         if t % 40 == 0:
             assert_state_equal(eng.download_state(), orc.state, where="%s/%s step %d" % (step_kernel, name, t))
+            if t >= 40:
+                crowded += _crowded_movers(orc.state, E)
     assert_state_equal(eng.download_state(), orc.state, where="%s/%s final" % (step_kernel, name))
+    crowded += _crowded_movers(orc.state, E)
+    if name == "four_lane_dense":
+        assert crowded > 0, "no moving traffic vehicle with more than 21 objects around it: the walks were not reached"
