@@ -272,40 +272,23 @@ MD_HD void md_observe_task(int task, const MdObsCtx* k, const MdState* s, const 
     }
 }
 
-MD_HD void md_observe_combine(const MdObsCtx* k, const MdState* s, const MdConfig* c, int a, int env_just_reset,
-                              const float (*r)[5]) {
-    int n = a;
-    /* a vehicle (re)spawned at the start of this step only reports its first observation
-     * (multi_agent_metadrive.py:190-212: new_obs, reward 0, not terminated) */
-    int just_reset = env_just_reset || ((s->shape[n].flags & MD_F_SPAWNED) != 0);
-    s->shape[n].flags &= ~MD_F_SPAWNED;
-    int ai = a; /* env-local view: agent a of this env */
-    float* obs = s->obs + (size_t)ai * c->obs_dim;
-    float* info = s->step_info + (size_t)ai * 8;
-    MdDyn* d = &s->dyn[n];
-    MdNav* nav = &s->nav[n];
+/* dist to left/right of the route (base_vehicle.py:491-499) from the lateral on the current road's first lane */
+MD_HD void md_route_borders(const MdObsCtx* k, const float (*r)[5], float* to_left, float* to_right) {
+    *to_left = r[0][1] + k->cur_w / 2.0f;
+    *to_right = k->cur_w * k->cur_n - *to_left;
+}
+
+/* The dims of slot n's observation row that precede the "others" block, [0, md_obs_others(c)), under the layout of `c`:
+ * vehicle size (random_agent_model), route borders, state, lane-line and navigation dims from the task results r (tasks 0, 1,
+ * 2, 3, 4 and 8 are read).  For a slot that holds a driving agent (k->valid): the row of any other slot is zeros, which is
+ * the caller's to write.  Dims that a side / lane-line detector of `c` owns are left alone.  Reads the state, writes nothing
+ * but `obs`: md_observe_combine calls it for the env's own row, the expert's own sensors (md_expert_sense) for a row under
+ * the expert's layout. */
+MD_HD void md_observe_state_dims(const MdObsCtx* k, const MdState* s, const MdConfig* c, int n, const float (*r)[5], float* obs) {
+    const MdDyn* d = &s->dyn[n];
     const int o_mid = md_obs_mid(c), o_ll = md_obs_ll(c), o_navi = md_obs_navi(c);
-    const int toll = md_is_tollgate(c);
-    if (!k->valid) {
-        if (s->done_out) ((uint32_t*)s->done_out)[ai] = 0u;
-        for (int i = 0; i < md_obs_lidar(c); ++i) obs[i] = 0.0f;
-        for (int i = c->obs_dim - md_obs_tail(c); i < c->obs_dim; ++i) obs[i] = 0.0f;
-        s->reward[ai] = 0.0f;
-        s->cost[ai] = 0.0f;
-        for (int i = 0; i < 8; ++i) info[i] = 0.0f;
-        return;
-    }
-    float cur_w = k->cur_w, cur_n = k->cur_n;
-
-    /* dist to left/right of the route (base_vehicle.py:491-499) */
-    float lat0 = r[0][1];
-    float to_left = lat0 + cur_w / 2.0f;
-    float to_right = cur_w * cur_n - to_left;
-    uint32_t fl = s->flags[n] & (MD_FL_CRASH_VEHICLE | MD_FL_CRASH_OBJECT | MD_FL_CRASH_HUMAN | MD_FL_CRASH_BUILDING |
-                                 MD_FL_CRASH_SIDEWALK | MD_FL_ON_WHITE_CONT | MD_FL_ON_YELLOW_CONT | MD_FL_ON_BROKEN |
-                                 MD_FL_ON_CROSSWALK | MD_FL_ON_LANE);
-    if (to_right < 0.0f || to_left < 0.0f) fl |= MD_FL_OUT_OF_ROUTE;
-
+    float to_left, to_right;
+    md_route_borders(k, r, &to_left, &to_right);
     /* ---- state obs (obs/state_obs.py:64-151) ---- */
     float speed_kmh = md_fabs(d->speed) * 3.6f;
     const MdParam* P = &s->param[n];
@@ -324,14 +307,51 @@ MD_HD void md_observe_combine(const MdObsCtx* k, const MdState* s, const MdConfi
     obs[o_mid + 3] = md_clip((s->action[2 * n] + 1.0f) / 2.0f, 0.0f, 1.0f);
     obs[o_mid + 4] = md_clip((s->action[2 * n + 1] + 1.0f) / 2.0f, 0.0f, 1.0f);
     obs[o_mid + 5] = r[8][0];
-    float ls = r[2][0], llat = r[2][1];
+    float llat = r[2][1];
     if (c->n_lane_line <= 0) obs[o_ll] = md_clip((llat * 2.0f / c->max_lane_width + 1.0f) / 2.0f, 0.0f, 1.0f);
     /* ---- navi (node_network_navigation.py:160-168, 243-292) ---- */
-    if (!toll)
+    if (!md_is_tollgate(c))
         for (int i = 0; i < 5; ++i) {
             obs[o_navi + i] = r[3][i];
             obs[o_navi + 5 + i] = r[4][i];
         }
+}
+
+MD_HD void md_observe_combine(const MdObsCtx* k, const MdState* s, const MdConfig* c, int a, int env_just_reset,
+                              const float (*r)[5]) {
+    int n = a;
+    /* a vehicle (re)spawned at the start of this step only reports its first observation
+     * (multi_agent_metadrive.py:190-212: new_obs, reward 0, not terminated) */
+    int just_reset = env_just_reset || ((s->shape[n].flags & MD_F_SPAWNED) != 0);
+    s->shape[n].flags &= ~MD_F_SPAWNED;
+    int ai = a; /* env-local view: agent a of this env */
+    float* obs = s->obs + (size_t)ai * c->obs_dim;
+    float* info = s->step_info + (size_t)ai * 8;
+    MdDyn* d = &s->dyn[n];
+    MdNav* nav = &s->nav[n];
+    const int toll = md_is_tollgate(c);
+    if (!k->valid) {
+        if (s->done_out) ((uint32_t*)s->done_out)[ai] = 0u;
+        for (int i = 0; i < md_obs_lidar(c); ++i) obs[i] = 0.0f;
+        for (int i = c->obs_dim - md_obs_tail(c); i < c->obs_dim; ++i) obs[i] = 0.0f;
+        s->reward[ai] = 0.0f;
+        s->cost[ai] = 0.0f;
+        for (int i = 0; i < 8; ++i) info[i] = 0.0f;
+        return;
+    }
+    float cur_w = k->cur_w, cur_n = k->cur_n;
+
+    float to_left, to_right;
+    md_route_borders(k, r, &to_left, &to_right);
+    uint32_t fl = s->flags[n] & (MD_FL_CRASH_VEHICLE | MD_FL_CRASH_OBJECT | MD_FL_CRASH_HUMAN | MD_FL_CRASH_BUILDING |
+                                 MD_FL_CRASH_SIDEWALK | MD_FL_ON_WHITE_CONT | MD_FL_ON_YELLOW_CONT | MD_FL_ON_BROKEN |
+                                 MD_FL_ON_CROSSWALK | MD_FL_ON_LANE);
+    if (to_right < 0.0f || to_left < 0.0f) fl |= MD_FL_OUT_OF_ROUTE;
+
+    md_observe_state_dims(k, s, c, n, r, obs);
+    float speed_kmh = md_fabs(d->speed) * 3.6f;
+    const MdParam* P = &s->param[n];
+    float ls = r[2][0], llat = r[2][1];
 
     /* ---- arrive destination (metadrive_env.py:213-227) ---- */
     float fs = r[5][0], flat = r[5][1];

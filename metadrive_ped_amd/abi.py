@@ -198,6 +198,8 @@ ENTRY_POINTS = {
 EXPERT_ENTRY_POINTS = {"md_expert": (_i, [_W, _S, _K, P, P, P, P, P, P])}
 # include/md_ai_protect.h: (w, s, c, weights, noise, actions, save_level, takeover, expert_takeover, applied_out, flags_out, saver_out, stream)
 AI_PROTECT_ENTRY_POINTS = {"md_ai_protect": (_i, [_W, _S, _K, P, P, P, _f, P, P, P, P, P, P])}
+# include/md_expert_sense.h: (w, s, c, weights, beam_cs240, noise, action_out, mlp_out, obs_out, stream)
+EXPERT_SENSE_ENTRY_POINTS = {"md_expert_sense": (_i, [_W, _S, _K, P, P, P, P, P, P, P])}
 AIP_TAKEOVER, AIP_TAKEOVER_START, AIP_TAKEOVER_END = 1, 2, 4      # md_ai_protect's flag byte
 # include/md_curriculum.h
 CURRICULUM_ENTRY_POINTS = {"md_curriculum": (_i, [_S, _S, _K, C.POINTER(MdCurriculum), P, _i, P])}

@@ -133,6 +133,10 @@ BATCH_DEFAULT_CONFIG = dict(
     scenario_pool_max_bytes=64 << 30,   # a walk's scene pool (maps + snapshot rows, device bytes) larger than this is refused
     expert_weights=None,    # agent_policy="ExpertPolicy" / expert.expert(): path of the reference's ppo_expert/expert_weights.npz;
                             # None = found in an installed reference package (metadrive_ped_amd/expert.py)
+    expert_own_sensors=False,   # True: the expert observes through its own sensors (240 lasers at 50 m, num_others=4, no noise, no
+                            # detectors: numpy_expert.py:39-62) from the live state (md_expert_sense), so agent_policy="ExpertPolicy"
+                            # and expert() take any vehicle_config and the multi-agent envs (all but tollgate); False: from the
+                            # env's own obs row (md_expert), which only the 259-dim default vehicle config allows
 )
 
 # Keys of the reference's BASE_DEFAULT_CONFIG (envs/base_env.py:32-266) that only concern rendering, cameras, the GUI,
@@ -190,13 +194,29 @@ def _merge(dst, src, path=""):
             dst[k] = v
 
 
-def expert_config_problem(cfg):
+OWN_SENSORS_HINT = "; expert_own_sensors=True lets the expert observe through its own sensors instead"
+
+
+def expert_config_problem(cfg, own_sensors=None):
     """None if the PPO expert can drive envs of this config, else why not.  numpy_expert.py:58-62 rewrites the vehicle's
     config to lidar (240 beams, 50 m, num_others=0, no noise, no dropout) and random_agent_model=False on every call, and
-    its observation must be 275-dim (:48): only the configs where that rewrite changes nothing are taken."""
+    its observation must be 275-dim (:48): reading the env's own obs row, only the configs where that rewrite changes
+    nothing are taken.  own_sensors (None: config["expert_own_sensors"]): the expert observes for itself (md_expert_sense),
+    whatever the vehicle config, in every env whose vehicles navigate a road network with the plain observation layout."""
     why = "the reference's expert (examples/ppo_expert/numpy_expert.py) rewrites the vehicle config to this on every call"
+    own = bool(cfg.get("expert_own_sensors")) if own_sensors is None else bool(own_sensors)
     if cfg.get("scenario_mode"):
         return "agent_policy=ExpertPolicy / expert(): not in BatchedScenarioEnv (single-agent PG envs only)"
+    if own:
+        if cfg["is_multi_agent"] and cfg["marl_map"] == "tollgate":
+            return ("agent_policy=ExpertPolicy / expert(): not in the tollgate env, with expert_own_sensors=True either (its "
+                    "observation has no navigation dims)")
+        return None
+    problem = _obs_row_expert_problem(cfg, why)
+    return problem + OWN_SENSORS_HINT if problem else None
+
+
+def _obs_row_expert_problem(cfg, why):
     if cfg["is_multi_agent"]:
         return "agent_policy=ExpertPolicy / expert(): not in the multi-agent envs (single-agent PG envs only)"
     vc = cfg["vehicle_config"]
@@ -271,6 +291,9 @@ def make_config(user=None):
     if pol == "LaneChangePolicy":
         # LaneChangePolicy.__init__ (policy/lange_change_policy.py:16)
         assert cfg["discrete_action"], "Must set discrete_action=True for using this control policy"
+    if pol == "AIProtectPolicy" and cfg["expert_own_sensors"]:
+        raise NotImplementedError("agent_policy=AIProtectPolicy with expert_own_sensors=True is not built: the saver's rule reads the "
+                                  "env's own lidar cloud (use ExpertPolicy / expert(), or the default vehicle config without the key)")
     if pol in EXPERT_POLICIES:
         problem = expert_config_problem(cfg)
         if problem:

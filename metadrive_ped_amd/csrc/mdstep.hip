@@ -30,6 +30,7 @@
 
 #include "md_curriculum.h"
 #include "md_expert.h"
+#include "md_expert_sense.h"
 #include "md_ai_protect.h"
 #include "md_scenario.h"
 
@@ -153,6 +154,8 @@ __device__ __forceinline__ int wave_min_i(int v, bool valid, int none) {
 // Lidar for one (agent, sector) work item, executed by one wave.
 // ------------------------------------------------------------------------------------------------
 // det: LDS words [2] of agent a's detected set (nullptr = not tracked)
+// kLdsRow: out_row is a row in LDS (md_expert_sense): a plain store instead of the streaming one meant for HBM
+template <bool kLdsRow = false>
 __device__ __forceinline__ void lidar_item(const MdWorld& w, const MdState& s, const MdConfig& c, int a, int sec, int lane,
                            float* __restrict__ out_row, unsigned long long* det) {
     const MdShape me = s.shape[a];  // wave-uniform (s is the env-local, LDS-staged view)
@@ -227,7 +230,10 @@ __device__ __forceinline__ void lidar_item(const MdWorld& w, const MdState& s, c
             }
         }
     }
-    if (valid) st_stream_f(&out_row[beam], best);
+    if (valid) {
+        if (kLdsRow) out_row[beam] = best;
+        else st_stream_f(&out_row[beam], best);
+    }
     if (det) {
         // union of the 64 beams' first hits: peel one distinct slot per iteration (<= a handful)
         unsigned long long todo = __ballot(valid && best_j >= 0);
@@ -3714,14 +3720,11 @@ __device__ __forceinline__ void expert_hidden(const float* __restrict__ W, const
         for (int r = 0; r < 4; ++r) out[((lane >> 4) * 4 + r) * kExpHS + (4 * wave + j) * 16 + (lane & 15)] = md_tanh(acc[j][r]);
 }
 
-// Stages 1-3 for the tile of envs [e0, e0 + n_here): leaves mean | log_std of row r in l_out[r * MD_EXPERT_OUT ...], behind a barrier.
-// l_x [kExpM * kExpXS] (x; later h2 at stride kExpHS), l_h [kExpM * kExpHS] (h1) and l_out are the calling kernel's LDS.
-__device__ __forceinline__ void expert_tile_forward(const MdWorld& w, const MdState& g, const MdConfig& c, const float* __restrict__ wts,
-                                                    float* __restrict__ obs_out, float* l_x, float* l_h, float* l_out, int e0,
-                                                    int n_here) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+// Stage 1 of md_expert for the tile of envs [e0, e0 + n_here): x from the env's obs row (state 19 | cloud 240) and the "others"
+// block of md_others_block on the env's detected sets, corrected, in l_x [kExpM * kExpXS]; behind a barrier.
+__device__ __forceinline__ void expert_fill_x(const MdWorld& w, const MdState& g, const MdConfig& c, float* l_x, int e0, int n_here) {
+    const int tid = threadIdx.x;
     const int od = c.obs_dim;   // 259: state 19 | cloud 240
-    // 1. the expert's observation
     for (int i = tid; i < kExpM * kExpXS; i += 256) {
         const int r = i / kExpXS, k = i - r * kExpXS;
         float v = 0.0f;
@@ -3746,10 +3749,18 @@ __device__ __forceinline__ void expert_tile_forward(const MdWorld& w, const MdSt
         md_expert_correct(x);
     }
     __syncthreads();
+}
+
+// Stages 2-3 for the tile of rows [row0, row0 + n_here) whose x stands in l_x (expert_fill_x, or md_expert_sense's own): obs_out rows,
+// then the MLP; leaves mean | log_std of row r in l_out[r * MD_EXPERT_OUT ...], behind a barrier.
+// l_x [kExpM * kExpXS] (x; later h2 at stride kExpHS), l_h [kExpM * kExpHS] (h1) and l_out are the calling kernel's LDS.
+__device__ __forceinline__ void expert_tile_forward(const float* __restrict__ wts, float* __restrict__ obs_out, float* l_x, float* l_h,
+                                                    float* l_out, int row0, int n_here) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     if (obs_out)
         for (int i = tid; i < n_here * MD_EXPERT_IN; i += 256) {
             const int r = i / MD_EXPERT_IN, k = i - r * MD_EXPERT_IN;
-            obs_out[(size_t)e0 * MD_EXPERT_IN + i] = l_x[r * kExpXS + k];
+            obs_out[(size_t)row0 * MD_EXPERT_IN + i] = l_x[r * kExpXS + k];
         }
     // 2. hidden layers
     expert_hidden(wts + MD_EXPERT_W1, wts + MD_EXPERT_B1, MD_EXPERT_IN_PAD, l_x, kExpXS, l_h, wave, lane);
@@ -3768,6 +3779,24 @@ __device__ __forceinline__ void expert_tile_forward(const MdWorld& w, const MdSt
     __syncthreads();
 }
 
+// The tile's results from l_out: mlp_out rows and the action (mean, or the draw with `noise`) of rows [row0, row0 + n_here).  Rows
+// whose bit in `skip` is set (md_expert_sense: rows that were not sensed) get zeros.
+__device__ __forceinline__ void expert_tile_emit(const float* l_out, const float* __restrict__ noise, float* __restrict__ action_out,
+                                                 float* __restrict__ mlp_out, int row0, int n_here, unsigned skip) {
+    const int tid = threadIdx.x;
+    if (tid < n_here * MD_EXPERT_OUT) {
+        const int r = tid >> 2, q = tid & 3;
+        const size_t e = (size_t)(row0 + r);
+        const bool off = ((skip >> r) & 1u) != 0u;
+        if (mlp_out) mlp_out[e * MD_EXPERT_OUT + q] = off ? 0.0f : l_out[tid];
+        if (q < 2) {
+            const float mean = l_out[r * MD_EXPERT_OUT + q];
+            const float act = noise ? md_expert_sample(mean, l_out[r * MD_EXPERT_OUT + 2 + q], noise[e * 2 + q]) : mean;
+            action_out[e * 2 + q] = off ? 0.0f : act;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void expert_kernel(MdWorld w, MdState g, MdConfig c, const float* __restrict__ wts,
                                                      const float* __restrict__ noise, float* __restrict__ action_out,
                                                      float* __restrict__ mlp_out, float* __restrict__ obs_out) {
@@ -3777,16 +3806,132 @@ __global__ __launch_bounds__(256) void expert_kernel(MdWorld w, MdState g, MdCon
     const int tid = threadIdx.x;
     const int e0 = blockIdx.x * kExpM;
     const int n_here = min(kExpM, c.n_envs - e0);
-    expert_tile_forward(w, g, c, wts, obs_out, l_x, l_h, l_out, e0, n_here);
-    if (tid < n_here * MD_EXPERT_OUT) {
-        const int r = tid >> 2, q = tid & 3;
-        const size_t e = (size_t)(e0 + r);
-        if (mlp_out) mlp_out[e * MD_EXPERT_OUT + q] = l_out[tid];
-        if (q < 2) {
-            const float mean = l_out[r * MD_EXPERT_OUT + q];
-            action_out[e * 2 + q] = noise ? md_expert_sample(mean, l_out[r * MD_EXPERT_OUT + 2 + q], noise[e * 2 + q]) : mean;
+    expert_fill_x(w, g, c, l_x, e0, n_here);
+    expert_tile_forward(wts, obs_out, l_x, l_h, l_out, e0, n_here);
+    expert_tile_emit(l_out, noise, action_out, mlp_out, e0, n_here, 0u);
+}
+
+// md_expert_sense (include/md_expert_sense.h): the expert observes for itself.  Tile of kExpM rows, row i = agent i % A of env i / A.
+//   1. wave w, 16-lane group q: the state dims of row 4 w + q (md_observe_ctx, the six tasks the obs dims read on lanes of the group,
+//      md_observe_state_dims on its lane 0) into the row in LDS;
+//   2. the 16 rows x 4 sectors of the 240-beam cast by LDS ticket: lidar_item against the env's shape table, cloud straight into the
+//      row, the detected set into the row's two LDS words;
+//   3. behind a barrier, one thread per row: md_others_block on the row's own set, md_expert_correct;
+//   4. expert_tile_forward / expert_tile_emit, as expert_kernel.
+// The shape tables are read through L2, not staged: the 16 rows of a single-agent tile belong to 16 envs, and 16 tables of up to 128
+// slots x 32 B (64 KB) cannot stand in LDS beside x and h1; a row's four sectors read the same 4 KB at most, which stays in L2 / the
+// vector cache between them.  Static LDS: x 18.3 KB + h1 16.3 KB + 3 KB of task results + 0.6 KB = 38.3 KB at every capacity.
+// Rows of an env with need_reset != 0 and rows past the last stay zero in LDS and are written out as zeros (expert_tile_emit).
+__global__ __launch_bounds__(256) void expert_sense_kernel(MdWorld w, MdState g, MdConfig c, const float* __restrict__ wts,
+                                                           const float* __restrict__ beam_cs240, const float* __restrict__ noise,
+                                                           float* __restrict__ action_out, float* __restrict__ mlp_out,
+                                                           float* __restrict__ obs_out) {
+    __shared__ __attribute__((aligned(16))) float l_x[kExpM * kExpXS];
+    __shared__ __attribute__((aligned(16))) float l_h[kExpM * kExpHS];
+    __shared__ float l_out[kExpM * MD_EXPERT_OUT];
+    __shared__ float l_task[kExpM * 48];                 // MD_OBS_TASKS * 5 (= 45) task results per row, padded
+    __shared__ unsigned long long l_det[kExpM * 2];      // the rows' detected sets
+    __shared__ int l_env[kExpM];                         // the row's env, -1 = not sensed
+    __shared__ int l_tk;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int A = c.agents_per_env;
+    const int rows = c.n_envs * A;
+    const int row0 = blockIdx.x * kExpM;
+    const int n_here = min(kExpM, rows - row0);
+    // the expert's sensor config (numpy_expert.py:39-46) over the env's
+    c.n_beams = MD_EXPERT_BEAMS;
+    c.lidar_range = MD_EXPERT_RANGE;
+    c.n_side = 0;
+    c.n_lane_line = 0;
+    c.random_agent_model = 0;
+    c.num_others = MD_EXPERT_OTHERS;
+    c.add_others_navi = 0;
+    c.obs_dim = MD_EXPERT_IN;
+    w.beam_cs = beam_cs240;
+    for (int i = tid; i < kExpM * kExpXS; i += 256) l_x[i] = 0.0f;
+    if (tid < kExpM) {
+        int e = -1;
+        if (tid < n_here) {
+            e = (row0 + tid) / A;
+            if (g.need_reset[e] != 0) e = -1;
+        }
+        l_env[tid] = e;
+        l_det[2 * tid] = 0ull;
+        l_det[2 * tid + 1] = 0ull;
+    }
+    if (tid == 0) l_tk = 0;
+    __syncthreads();
+    // the slices of env e that the sensors read (md_env_view without the arrays nothing here touches)
+    auto view_of = [&](int e) {
+        MdState s = g;
+        const size_t b = (size_t)e * (size_t)c.cap;
+        s.shape = g.shape + b;
+        s.dyn = g.dyn + b;
+        s.param = g.param + b;
+        s.nav = g.nav + b;
+        s.action = g.action + 2 * b;
+        s.final_lane = g.final_lane + b;
+        return s;
+    };
+    unsigned skip = 0u;
+#pragma unroll
+    for (int r = 0; r < kExpM; ++r) skip |= (l_env[r] < 0 ? 1u : 0u) << r;
+    // 1. state dims
+    {
+        const int q = lane >> 4, sub = lane & 15;
+        const int r = 4 * wave + q;
+        const int e = l_env[r];
+        float* scratch = l_task + r * 48;
+        MdObsCtx k;
+        MdState s = g;
+        int a = 0;
+        if (e >= 0) {
+            a = row0 + r - e * A;
+            s = view_of(e);
+            const int m = w.env_map[e];
+            md_observe_ctx(w.lanes + w.lane_off[m], w.roads + w.road_off[m], &s, a, &k);
+            if (sub < 5 || sub == 8) {     // the tasks whose results the obs dims read
+                float mine[5];
+                md_observe_task(sub, &k, &s, &c, a, mine);
+#pragma unroll
+                for (int i = 0; i < 5; ++i) scratch[sub * 5 + i] = mine[i];
+            }
+        }
+        wave_lds_sync();
+        // a slot without a driving agent keeps its zeros
+        if (e >= 0 && sub == 0 && k.valid) md_observe_state_dims(&k, &s, &c, a, (const float (*)[5])scratch, l_x + r * kExpXS);
+    }
+    // 2. cloud and detected sets
+    constexpr int kSectors = (MD_EXPERT_BEAMS + 63) / 64;
+    for (int guard = 0; guard < kExpM * kSectors; ++guard) {
+        int it = 0;
+        if (lane == 0) it = atomicAdd(&l_tk, 1);
+        it = __builtin_amdgcn_readfirstlane(it);
+        if (it < 0 || it >= kExpM * kSectors) break;
+        const int r = it / kSectors, sec = it - r * kSectors;
+        const int e = l_env[r];
+        if (e < 0) continue;
+        MdState s = g;
+        s.shape = g.shape + (size_t)e * (size_t)c.cap;
+        lidar_item<true>(w, s, c, row0 + r - e * A, sec, lane, l_x + r * kExpXS + MD_EXPERT_STATE + 4 * MD_EXPERT_OTHERS, l_det + 2 * r);
+    }
+    __syncthreads();
+    // 3. others, correction: row r on lane 0 of its 16-lane group
+    if ((tid & 15) == 0) {
+        const int r = tid >> 4;
+        const int e = l_env[r];
+        if (e >= 0) {
+            const MdState s = view_of(e);
+            const int m = w.env_map[e];
+            float* x = l_x + r * kExpXS;
+            md_others_block(w.lanes + w.lane_off[m], w.roads + w.road_off[m], &s, &c, row0 + r - e * A, l_det[2 * r], l_det[2 * r + 1],
+                            x + MD_EXPERT_STATE);
+            md_expert_correct(x);
         }
     }
+    __syncthreads();
+    expert_tile_forward(wts, obs_out, l_x, l_h, l_out, row0, n_here);
+    expert_tile_emit(l_out, noise, action_out, mlp_out, row0, n_here, skip);
 }
 
 // md_ai_protect: AIProtectPolicy (include/md_ai_protect.h) in one launch.  The expert's draw exactly as expert_kernel computes it (the
@@ -3804,7 +3949,8 @@ __global__ __launch_bounds__(256) void ai_protect_kernel(MdWorld w, MdState g, M
     const int tid = threadIdx.x;
     const int e0 = blockIdx.x * kExpM;
     const int n_here = min(kExpM, c.n_envs - e0);
-    expert_tile_forward(w, g, c, wts, nullptr, l_x, l_h, l_out, e0, n_here);
+    expert_fill_x(w, g, c, l_x, e0, n_here);
+    expert_tile_forward(wts, nullptr, l_x, l_h, l_out, e0, n_here);
     if (tid >= n_here) return;
     const int e = e0 + tid;
     const float* o4 = l_out + tid * MD_EXPERT_OUT;
@@ -3895,7 +4041,8 @@ enum When : unsigned {
     REPLAY = 16, SPAWN_TRAFFIC = 32,                     // check_phase, after traffic_mode is validated
     SCENARIO = 64, ROUTE = 128, OTHERS = 256,            // md_step, each after the config checks of its branch
 };
-constexpr int kLidarEntry = 1 << 9, kDetectorEntry = 1 << 10, kExpertEntry = 1 << 11, kPgWalkEntry = 1 << 12, kProtectEntry = 1 << 13;
+constexpr int kLidarEntry = 1 << 9, kDetectorEntry = 1 << 10, kExpertEntry = 1 << 11, kPgWalkEntry = 1 << 12, kProtectEntry = 1 << 13,
+              kSenseEntry = 1 << 14;
 constexpr int kMapPhases = PH_LOCALIZE | PH_CONTACTS | PH_OBSERVE | PH_IDM | PH_LIFECYCLE;
 constexpr int kTrafficPhases = PH_INTEGRATE | PH_TRAFFIC;
 
@@ -3930,6 +4077,8 @@ const Need kNeeds[] = {
     {kExpertEntry, ALWAYS, {FS(obs), FS(detected), FS(dyn), FS(param), FS(nav), FW(env_map), FW(lanes), FW(lane_off), FW(roads),
                             FW(road_off)}},
     {kProtectEntry, ALWAYS, {FS(shape), FS(need_reset)}},
+    {kSenseEntry, ALWAYS, {FS(dyn), FS(param), FS(nav), FS(action), FS(final_lane), FS(need_reset), FW(env_map), FW(lanes), FW(lane_off),
+                           FW(roads), FW(road_off)}},
     {kPgWalkEntry, ALWAYS, {FS(scene_of), FS(walk_ep), FS(param), FS(route_nodes), FS(route_roads), FS(final_lane), FS(idm_rand)}},
     {kPgWalkEntry, SPAWN_TRAFFIC, {FS(rng), FS(route_nodes0), FS(route_roads0), FS(final_lane0)}},
 };
@@ -4419,6 +4568,32 @@ __attribute__((visibility("default"))) int md_ai_protect(const MdWorld* w, const
     }
     hipLaunchKernelGGL(ai_protect_kernel, dim3((c->n_envs + kExpM - 1) / kExpM), dim3(256), 0, (hipStream_t)stream, *w, *s, *c, weights,
                        noise, actions, save_level, takeover, expert_takeover, applied_out, flags_out, saver_out);
+    return launch_status();
+}
+
+__attribute__((visibility("default"))) int md_expert_sense(const MdWorld* w, const MdState* s, const MdConfig* c, const float* weights,
+                                                          const float* beam_cs240, const float* noise, float* action_out, float* mlp_out,
+                                                          float* obs_out, void* stream) {
+    TRY(check_common(w, s, c));
+    NEED(weights); NEED(beam_cs240); NEED(action_out);
+    TRY(need_fields(kSenseEntry, ALWAYS, w, s, c));
+    if (((uintptr_t)weights & 15) || ((uintptr_t)beam_cs240 & 15)) {
+        snprintf(g_err, sizeof g_err, "md_expert_sense: %s must be 16-byte aligned",
+                 ((uintptr_t)weights & 15) ? "the packed weights" : "the beam table beam_cs240");
+        return MD_EINVAL;
+    }
+    if (c->traffic_mode == 4) {
+        snprintf(g_err, sizeof g_err, "md_expert_sense: not in scenario mode (traffic_mode 4): the expert's observation needs a road "
+                 "network's navigation");
+        return MD_EINVAL;
+    }
+    if (c->is_multi_agent && c->ma_kind == MD_MA_TOLLGATE) {
+        snprintf(g_err, sizeof g_err, "md_expert_sense: not in the tollgate env (ma_kind 1): its observation has no navigation dims");
+        return MD_EINVAL;
+    }
+    const int rows = c->n_envs * c->agents_per_env;
+    hipLaunchKernelGGL(expert_sense_kernel, dim3((rows + kExpM - 1) / kExpM), dim3(256), 0, (hipStream_t)stream, *w, *s, *c, weights,
+                       beam_cs240, noise, action_out, mlp_out, obs_out);
     return launch_status();
 }
 

@@ -318,7 +318,7 @@ class HostScene:
             st["env_steps"] = np.zeros(E, np.int32)
             st["agent_id"] = np.tile(np.arange(cap, dtype=np.int32), E)
             st["next_agent_id"] = np.full(E, cfg["initial_agents"] or A, np.int32)   # names agent0 .. agent{n-1} are taken
-        if self.num_others > 0 or cfg["agent_policy"] in ("ExpertPolicy", "AIProtectPolicy"):
+        if self.num_others > 0 or (cfg["agent_policy"] in ("ExpertPolicy", "AIProtectPolicy") and not cfg.get("expert_own_sensors")):
             # ExpertPolicy / AIProtectPolicy: the expert's own "others" block (num_others=4) is computed by md_expert from these sets; the env's
             # obs keeps its 259 dims (md_step tracks the sets whenever the array is there)
             st["detected"] = np.zeros((E * A, 2), np.uint64)
@@ -448,6 +448,7 @@ class BatchedEngine:
         self._noise_gen = None
         self._expert_gen = None
         self._expert_w = None
+        self._expert_beams = None
         self._track_det = False
         self._rec = None
         self._tracks = None
@@ -769,11 +770,25 @@ class BatchedEngine:
             self._expert_w = self.torch.from_numpy(load_expert_weights(self.cfg.get("expert_weights"))).to(self.device)
         return self._expert_w
 
-    def expert_forward(self, deterministic=False, need_obs=False, action_out=None, mlp_out=None, noise=None):
+    def expert_beams(self):
+        """The expert's 240-beam table on the device (md_expert_sense's beam_cs240): the env's own MdWorld.beam_cs when that is
+        the 240-beam one, else uploaded once per engine."""
+        if self.n_beams == 240:
+            return self.world_dev["beam_cs"]
+        if self._expert_beams is None:
+            self._expert_beams = self._to_dev(beam_table(240))
+        return self._expert_beams
+
+    def expert_forward(self, deterministic=False, need_obs=False, action_out=None, mlp_out=None, noise=None, own_sensors=None):
         """ONE md_expert launch on the current observation -> action [E, 2] (+ the corrected expert obs [E, 275] with
         need_obs).  deterministic=False: action = mean + exp(log_std) * N(0, 1), one [E, 2] draw of the engine's expert
-        generator (seeded with start_seed + env_seed_offset), or `noise` [E, 2] float32 on the device when given."""
+        generator (seeded with start_seed + env_seed_offset), or `noise` [E, 2] float32 on the device when given.
+        own_sensors (None: config["expert_own_sensors"]): ONE md_expert_sense launch on the live state instead -- [E * A, 2]
+        (+ [E * A, 275]), row e * A + a = agent a of env e, one [E * A, 2] draw; rows of an env about to restore itself are zeros."""
         torch = self.torch
+        own = bool(self.cfg.get("expert_own_sensors")) if own_sensors is None else bool(own_sensors)
+        if own:
+            return self._expert_sense(deterministic, need_obs, action_out, mlp_out, noise)
         if self.A != 1:
             raise ValueError("the expert drives single-agent envs")
         self._track_detected()
@@ -792,6 +807,29 @@ class BatchedEngine:
         with self._on_device():
             self._check(self.lib.md_expert(C.byref(self.w), C.byref(self.s), C.byref(self.k), ptr(w), ptr(noise), ptr(action_out),
                                            ptr(mlp_out), ptr(obs), self._stream()), "md_expert")
+        return (action_out, obs) if need_obs else action_out
+
+    def _expert_sense(self, deterministic, need_obs, action_out, mlp_out, noise):
+        torch = self.torch
+        n = self.E * self.A
+        w, beams = self.expert_weights(), self.expert_beams()
+        if deterministic:
+            noise = None
+        elif noise is None:
+            if self._expert_gen is None:
+                self._expert_gen = torch.Generator(device=self.device)
+                self._expert_gen.manual_seed(int(self.cfg["start_seed"]) + int(self.cfg["env_seed_offset"]))
+            noise = torch.randn((n, 2), dtype=torch.float32, device=self.device, generator=self._expert_gen)
+        for name, t, cols in (("noise", noise, 2), ("action_out", action_out, 2), ("mlp_out", mlp_out, 4)):
+            if t is not None and (t.numel() != n * cols or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()):
+                raise ValueError("{} must be a contiguous float32 tensor of {} x {} on the engine's device".format(name, n, cols))
+        if action_out is None:
+            action_out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
+        obs = torch.empty((n, 275), dtype=torch.float32, device=self.device) if need_obs else None
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+        with self._on_device():
+            self._check(self.lib.md_expert_sense(C.byref(self.w), C.byref(self.s), C.byref(self.k), ptr(w), ptr(beams), ptr(noise),
+                                                 ptr(action_out), ptr(mlp_out), ptr(obs), self._stream()), "md_expert_sense")
         return (action_out, obs) if need_obs else action_out
 
     def ai_protect_forward(self, actions, noise=None, saver_out=None):
@@ -841,9 +879,10 @@ class BatchedEngine:
             self.step_raw()
             return
         if self.cfg["agent_policy"] == "ExpertPolicy":
-            if getattr(self, "_expert_action", None) is None or self._expert_action.shape[0] != self.E:
-                self._expert_action = self.torch.empty((self.E, 2), dtype=self.torch.float32, device=self.device)
-            actions = self.expert_forward(deterministic=False, action_out=self._expert_action)
+            rows = self.E * self.A if self.cfg.get("expert_own_sensors") else self.E
+            if getattr(self, "_expert_action", None) is None or self._expert_action.shape[0] != rows:
+                self._expert_action = self.torch.empty((rows, 2), dtype=self.torch.float32, device=self.device)
+            actions = self.expert_forward(deterministic=False, action_out=self._expert_action).view(self.E, -1, 2)
         if self.cfg["agent_policy"] == "AIProtectPolicy":     # the saver looks at the agents' actions on the state the previous step left
             actions = self.ai_protect_forward(actions.reshape(self.E, 2) if actions.dim() == 3 else actions, noise=noise)
         a = actions

@@ -71,7 +71,7 @@ class BatchedMultiAgentRoundaboutEnv(ObjectSpawnMixin, BatchedEnvBase):
 
     def step(self, actions):
         self._require_engine("step")
-        if self.config["agent_policy"] == "IDMPolicy":      # every agent is driven by its own IDMPolicy: `actions` is ignored
+        if self.config["agent_policy"] in ("IDMPolicy", "ExpertPolicy"):      # every agent is driven by its own policy: `actions` is ignored
             self.engine.step(None)
         else:
             self.engine.step(self._coerce_actions(actions, (self.num_envs, self.num_agents), self.config["discrete_action"]))
@@ -98,6 +98,8 @@ class BatchedMultiAgentRoundaboutEnv(ObjectSpawnMixin, BatchedEnvBase):
             "dying": lambda: (sf & (abi.F_ALIVE | abi.F_STATIC)) == (abi.F_ALIVE | abi.F_STATIC),
             "spawned": lambda: ((sf & (abi.F_ALIVE | abi.F_STATIC)) == abi.F_ALIVE) & (e.nav_i[:, :A, 8] == 0),
         }
+        if self.config["agent_policy"] == "ExpertPolicy":     # the applied (sanitised) action of every slot, as the single-agent info has it
+            eager["action"] = e.action[:, :A, :]
         lazy.update(self._flag_info(e.flags[:, :A]))
         return LazyInfo(eager, lazy)
 

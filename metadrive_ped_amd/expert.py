@@ -15,8 +15,15 @@ without importing it.
 
 The expert observes the agent with its own LidarStateObservation (240 beams, 50 m, num_others=4) and, on every call,
 rewrites the vehicle's lidar config to (240, 50, num_others=0) with random_agent_model=False (numpy_expert.py:58-62).
-Only configs where that rewrite changes nothing are accepted (config.expert_config_problem); there the env's own
+By default only configs where that rewrite changes nothing are accepted (config.expert_config_problem); there the env's own
 259-dim observation is the expert's state block and cloud, and only the 16 "others" dims are added, by the kernel.
+
+With config["expert_own_sensors"]=True (or expert(env, own_sensors=True) for one call) the expert observes for itself, as in the
+reference: md_expert_sense (include/md_expert_sense.h) builds the 275-vector of every agent from the live state -- state and
+navigation dims, a 240-beam / 50 m lidar cast with its own detected sets, the four nearest detected vehicles -- in the same launch
+as the MLP.  Any vehicle_config goes, and so do the multi-agent envs (all but tollgate), where the tensors are [E, A, ...].  The
+env's own lidar noise and dropout belong to the env's observation and never touch the expert's.  An env that is about to restore
+itself (its episode just ended) is not sensed: its rows are zeros, and the step ignores its action anyway.
 """
 import importlib.util
 import os
@@ -96,14 +103,21 @@ def _engine_of(env):
     return eng
 
 
-def expert(env, deterministic=False, need_obs=False):
+def expert(env, deterministic=False, need_obs=False, own_sensors=None):
     """The batched metadrive.examples.expert: -> action [E, 2] (and the corrected expert observation [E, 275] with
     need_obs), device tensors on the env's stream, no host synchronisation.  deterministic=False draws
     N(mean, exp(log_std)) from the engine's expert stream (a device generator seeded with start_seed + env_seed_offset;
-    the reference draws from the global numpy stream).  The returned tensors are fresh (not views of engine buffers)."""
+    the reference draws from the global numpy stream).  The returned tensors are fresh (not views of engine buffers).
+    own_sensors: None = config["expert_own_sensors"]; True = the expert observes through its own sensors in this call, on an
+    env built without the key too.  Multi-agent envs (own sensors only): [E, A, 2] and [E, A, 275]."""
     cfg = getattr(env, "config", None) or getattr(env, "cfg")
-    problem = expert_config_problem(cfg)
+    own = bool(cfg.get("expert_own_sensors")) if own_sensors is None else bool(own_sensors)
+    problem = expert_config_problem(cfg, own_sensors=own)
     if problem:
         raise ValueError(problem)
     eng = _engine_of(env)
-    return eng.expert_forward(deterministic=deterministic, need_obs=need_obs)
+    out = eng.expert_forward(deterministic=deterministic, need_obs=need_obs, own_sensors=own)
+    if not own or eng.A == 1:
+        return out
+    shape = lambda t: t.view(eng.E, eng.A, t.shape[-1])
+    return (shape(out[0]), shape(out[1])) if need_obs else shape(out)

@@ -8,8 +8,11 @@ map.  Prints one JSON line per operating point:
     EnvInputPolicy step of the same batch.
 The rocprofv3 figure comes from a separate run under `rocprofv3 --kernel-trace --stats -- python tools/expert_bench.py
 --expert-only` (expert_kernel's row of the stats).
+--sense adds the expert's own sensors (md_expert_sense, include/md_expert_sense.h) on the same batch and state: us per launch beside
+md_expert's, and the ExpertPolicy step with config["expert_own_sensors"] (md_expert_sense + the lean md_step).  --marl ExA measures
+md_expert_sense on E roundabout envs of A agents (72-beam lidar of their own), after 50 ExpertPolicy steps.
 
-    python tools/expert_bench.py [--envs 4096] [--launches 500] [--steps 100] [--maps 4096,1] [--out FILE]
+    python tools/expert_bench.py [--envs 4096] [--launches 500] [--steps 100] [--maps 4096,1] [--sense] [--marl 1024x40] [--out FILE]
 """
 import argparse
 import json
@@ -42,6 +45,35 @@ def time_steps(torch, eng, n, actions):
     return ev_a.elapsed_time(ev_b) * 1e3 / n
 
 
+def time_launches(torch, launch, n):
+    for _ in range(20):
+        launch()
+    torch.cuda.synchronize()
+    ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev_a.record()
+    for _ in range(n):
+        launch()
+    ev_b.record()
+    torch.cuda.synchronize()
+    return ev_a.elapsed_time(ev_b) * 1e3 / n
+
+
+def marl_line(torch, args, E, A):
+    """md_expert_sense on E roundabout envs x A agents: the tiles straddle envs, every env's 16 shape tables are one"""
+    from metadrive_ped_amd.envs.marl_env import BatchedMultiAgentRoundaboutEnv
+    env = BatchedMultiAgentRoundaboutEnv(dict(num_envs=E, num_agents=A, agent_policy="ExpertPolicy", expert_own_sensors=True,
+                                              expert_weights=args.weights))
+    env.reset()
+    eng = env.engine
+    for _ in range(50):
+        eng.step(None)
+    out = torch.empty((E * A, 2), dtype=torch.float32, device=eng.device)
+    us = time_launches(torch, lambda: eng.expert_forward(deterministic=True, action_out=out), args.launches)
+    us_step = time_steps(torch, eng, args.steps, None)
+    return dict(metric="md_expert_sense", env="roundabout", envs=E, agents=A, rows=E * A, env_beams=eng.n_beams, cap=eng.cap,
+                us_per_launch=round(us, 2), rows_per_s=round(E * A / (us * 1e-6)), expert_policy_step_us=round(us_step, 2))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
@@ -49,6 +81,8 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--maps", default="4096,1", help="comma list of num_scenarios")
     ap.add_argument("--expert-only", action="store_true", help="md_expert launches only (the rocprofv3 run)")
+    ap.add_argument("--sense", action="store_true", help="also md_expert_sense (the expert's own sensors) on the same batch")
+    ap.add_argument("--marl", default="", help="ExA: md_expert_sense on E roundabout envs of A agents, e.g. 1024x40")
     ap.add_argument("--weights", default=weights_path())
     ap.add_argument("--out", default="")
     args = ap.parse_args()
@@ -71,22 +105,25 @@ def main():
         for _ in range(50):      # episodes under way: traffic in view, some envs resetting
             eng.step(None)
         out = torch.empty((E, 2), dtype=torch.float32, device=eng.device)
-        for _ in range(20):
-            eng.expert_forward(deterministic=True, action_out=out)
-        torch.cuda.synchronize()
-        ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev_a.record()
-        for _ in range(args.launches):
-            eng.expert_forward(deterministic=True, action_out=out)
-        ev_b.record()
-        torch.cuda.synchronize()
-        us = ev_a.elapsed_time(ev_b) * 1e3 / args.launches
+        us = time_launches(torch, lambda: eng.expert_forward(deterministic=True, action_out=out), args.launches)
         line = dict(metric="md_expert", envs=E, maps=n_maps, beams=240, us_per_launch=round(us, 2),
                     useful_tflops=round(USEFUL * E / (us * 1e-6) / 1e12, 1), padded_tflops=round(PADDED * E / (us * 1e-6) / 1e12, 1),
                     peak_tflops=PEAK_TF, target_us=20.0, met_target=bool(us <= 20.0), host_build_s=round(build_s, 1))
+        if args.sense:      # the same state through the expert's own sensors
+            us_sense = time_launches(torch, lambda: eng.expert_forward(deterministic=True, action_out=out, own_sensors=True), args.launches)
+            line.update(sense_us_per_launch=round(us_sense, 2), cap=eng.cap)
         if not args.expert_only:
             us_expert_step = time_steps(torch, eng, args.steps, None)
             del eng
+            if args.sense:
+                own = BatchedEngine(make_config(dict(num_envs=E, num_scenarios=n_maps, agent_policy="ExpertPolicy", expert_own_sensors=True,
+                                                     expert_weights=args.weights)))
+                own.reset()
+                for _ in range(50):
+                    own.step(None)
+                us_own_step = time_steps(torch, own, args.steps, None)
+                line.update(own_sensors_step_us=round(us_own_step, 2), own_sensors_agent_steps_per_s=round(E / (us_own_step * 1e-6)))
+                del own
             plain = BatchedEngine(make_config(dict(num_envs=E, num_scenarios=n_maps)))
             plain.reset()
             a = torch.zeros((E, 2), dtype=torch.float32, device=plain.device)
@@ -95,6 +132,11 @@ def main():
             del plain
             line.update(expert_policy_step_us=round(us_expert_step, 2), expert_policy_agent_steps_per_s=round(E / (us_expert_step * 1e-6)),
                         env_input_step_us=round(us_plain, 2), env_input_agent_steps_per_s=round(E / (us_plain * 1e-6)))
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    if args.marl:
+        E_m, A_m = (int(x) for x in args.marl.lower().split("x"))
+        line = marl_line(torch, args, E_m, A_m)
         print(json.dumps(line), flush=True)
         lines.append(line)
     if args.out:
