@@ -203,8 +203,10 @@ EXPERT_SENSE_ENTRY_POINTS = {"md_expert_sense": (_i, [_W, _S, _K, P, P, P, P, P,
 AIP_TAKEOVER, AIP_TAKEOVER_START, AIP_TAKEOVER_END = 1, 2, 4      # md_ai_protect's flag byte
 # include/md_curriculum.h
 CURRICULUM_ENTRY_POINTS = {"md_curriculum": (_i, [_S, _S, _K, C.POINTER(MdCurriculum), P, _i, P])}
-# exported by diagnostic (-DMD_STAMP) builds only
-OPTIONAL_ENTRY_POINTS = {"md_debug_set_stamp_buffer": (_i, [P]), "md_debug_set_env_order": (_i, [P])}
+# declared in no header: the hooks of diagnostic (-DMD_STAMP) builds, and md_localize through the lean step's road-first path
+# (the parity tests call it; a -DMD_LOC_ROAD_FIRST=0 build runs the plain walk under that name)
+OPTIONAL_ENTRY_POINTS = {"md_debug_set_stamp_buffer": (_i, [P]), "md_debug_set_env_order": (_i, [P]),
+                         "md_localize_road_first": _PHASE}
 
 
 def check_abi(abi_fn, what):

@@ -26,10 +26,13 @@ def main():
     if os.environ.get("MD_STEP_KERNEL", "wg") != "wg":
         PHASES = WAVE_PHASES     # wave_step_kernel (build with MD_EXTRA_FLAGS=-DMD_WAVE_ENVS=1: one env per workgroup)
     out = os.path.join(ROOT, "gpurun_out", "libmdstep_stamp.so")
+    if os.environ.get("MD_STAMP_LIB"):       # a -DMD_STAMP build made before: used as it is
+        out = os.environ["MD_STAMP_LIB"]
     os.makedirs(os.path.dirname(out), exist_ok=True)
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared",
-                           "-fvisibility=hidden", "-std=c++17", "-DMD_STAMP"] + os.environ.get("MD_EXTRA_FLAGS", "").split() + [ "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "metadrive_ped_amd", "csrc", "mdstep.hip"), "-o", out])
+    if not os.environ.get("MD_STAMP_LIB"):
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared",
+                               "-fvisibility=hidden", "-std=c++17", "-DMD_STAMP"] + os.environ.get("MD_EXTRA_FLAGS", "").split() + ["-I" + os.path.join(ROOT, "include"),
+                               os.path.join(ROOT, "metadrive_ped_amd", "csrc", "mdstep.hip"), "-o", out])
     from metadrive_ped_amd import _lib
     _lib.LIB_PATH = out
     import torch
@@ -68,7 +71,7 @@ def main():
         a[:, 0, 1] = (ob_[:, 3] < 0.35).to(torch.float32) * 0.5
         return a
 
-    for i in range(400 if lane_follow else 80):
+    for i in range(int(os.environ.get("STEPS", "400" if lane_follow else "80"))):
         eng.step(next_action(i))
     buf = torch.zeros(E * 32, dtype=torch.int64, device="cuda")
     eng.lib.md_debug_set_stamp_buffer.argtypes = [C.c_void_p]
@@ -89,11 +92,17 @@ def main():
         print("%-34s mean %8.0f  p50 %8.0f  p99 %8.0f  max %8.0f   share %5.1f%%" %
               (name, x.mean(), np.median(x), np.percentile(x, 99), x.max(), 100.0 * x.sum() / tot.sum()))
     ok = (fine[:, 0] > 0) & (fine[:, 3] > 0)
-    lf = fine[ok]
+    if ok.any():
+        print("localize(agent) stamps 0 -> 3: p50 %.0f  mean %.0f cycles over %d envs" % (
+            np.median(fine[ok, 3] - fine[ok, 0]), (fine[ok, 3] - fine[ok, 0]).mean(), ok.sum()))
+    lf = fine[ok & (fine[:, 2] > 0)]      # the grid walk ran (no road-first hit)
     if len(lf):
       print("localize(agent) fine: grid+cell loads %.0f | items+AABB %.0f | hull tests+frenet %.0f  (p50 cycles); candidates p50 %d, cell items p50 %d" % (
         np.median(lf[:, 1] - lf[:, 0]), np.median(lf[:, 2] - lf[:, 1]), np.median(lf[:, 3] - lf[:, 2]),
         np.median(lf[:, 15] & 0xffffffff), np.median(lf[:, 15] >> 32)))
+    if fine[:, 12].sum():
+        print("localisations of the stamped step: %d, answered by the road-first path: %d (%.1f %%)" % (
+            fine[:, 12].sum(), fine[:, 13].sum(), 100.0 * fine[:, 13].sum() / fine[:, 12].sum()))
     ok = (fine[:, 4] > 0) & (fine[:, 7] > fine[:, 4])
     li = fine[ok]
     if len(li):
