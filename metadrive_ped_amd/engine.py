@@ -19,7 +19,7 @@ from metadrive_ped_amd import abi, hostpool
 from metadrive_ped_amd.mapgen.pg import PGMap
 from metadrive_ped_amd.mapgen.tables import MapTables, WorldTables, beam_table
 from metadrive_ped_amd.obs_layout import ObsLayout
-from metadrive_ped_amd.scene import EnvScene
+from metadrive_ped_amd.scene import EnvScene, HostSceneBase, step_state
 
 STATE_ARRAY_SPECS = None  # filled below
 
@@ -163,157 +163,145 @@ def _build_one(job):
     return mt, EnvScene(s, mt, scene_cfg)
 
 
-class HostScene:
+# what a scene hands to the batch per mover slot: (state array, EnvScene / RoundaboutScene field).  These are also the arrays
+# md_swap_draw copies into an env that takes the next traffic draw or moves on to the next scene of a walk (BatchedEngine.DRAW_ARRAYS).
+DRAW_FIELDS = (("shape0", "shape"), ("dyn0", "dyn"), ("nav0", "nav"), ("pid0", "pid"), ("param", "param"), ("route_nodes", "route_nodes"),
+               ("route_roads", "route_roads"), ("final_lane", "final_lane"), ("idm_rand", "idm_rand"))
+
+
+def _traffic_rng(of_seeds):
+    """MdState.rng of the scenes `of_seeds`: xorshift32 needs a non-zero state; derive it from the scenario seed"""
+    return np.asarray([((s * 2654435761) ^ 0x9E3779B9) & 0xFFFFFFFF or 1 for s in of_seeds], np.uint32)
+
+
+class HostScene(HostSceneBase):
     """Host (numpy) copy of everything: world tables + reset snapshot.  Also what the tests hand to
     the CPU oracle."""
     def __init__(self, cfg):
         self.cfg = cfg
-        E = cfg["num_envs"]
-        cap = cfg["mover_capacity"] or abi.MD_MAX_CAP  # 0 = auto: build with the maximum, trim below
-        A = cfg["num_agents"]
-        self.E, self.cap, self.A = E, cap, A
+        self.E, self.A = cfg["num_envs"], cfg["num_agents"]
         ObsLayout(cfg, scenario=False).export_to(self)     # self.layout, and n_beams / n_side / n_ll / obs_base / ... / obs_dim
-        mc = cfg["map_config"]
-        # the PG walk (walk_scenarios): the scene pool is every seed of the slice, built once whatever the env count; env e starts at
-        # the first scene of its walk (scenario.walk_scene), and md_swap_draw moves it on through the pool on the device
-        walk = bool(cfg.get("walk_scenarios"))
-        self.walk, self.pool, self.walk_params = walk, None, (0, 0, 0, 0, 0)
-        if walk:
-            from metadrive_ped_amd.scenario import walk_params, walk_scene
-            self.walk_params = walk_params(cfg)
-            pool_seeds = [cfg["start_seed"] + p for p in range(cfg["num_scenarios"])]
-            env_scene = [int(p) for p in walk_scene(cfg, np.arange(E), 0)]
-            seeds = [pool_seeds[p] for p in env_scene]
-            self.seeds = pool_seeds       # names the slice, like ScenarioHostScene.seeds of a walk
-            uniq = pool_seeds
-        else:
-            seeds = [cfg["start_seed"] + ((cfg["env_seed_offset"] + e) % cfg["num_scenarios"]) for e in range(E)]
-            self.seeds = seeds
-            uniq = sorted(set(seeds))
-        map_of_seed = {}
-        tables, scenes = [], {}
-        scene_cfg = dict(cap=cap, agents_per_env=A, physics_world_step_size=cfg["physics_world_step_size"],
-                         random_spawn_lane_index=cfg["random_spawn_lane_index"],
-                         spawn_lane_index=cfg["agent_configs"]["default_agent"]["spawn_lane_index"],
-                         agent_vehicle_model=cfg["vehicle_config"]["vehicle_model"],
-                         spawn_longitude=cfg["vehicle_config"]["spawn_longitude"],
-                         spawn_lateral=cfg["vehicle_config"]["spawn_lateral"],
-                         agent_size_mass={k: cfg["vehicle_config"][k] for k in ("width", "length", "height", "mass")},
-                         spawn_velocity=cfg["vehicle_config"]["spawn_velocity"],
-                         spawn_velocity_car_frame=cfg["vehicle_config"]["spawn_velocity_car_frame"],
-                         traffic_density=cfg["traffic_density"], traffic_mode=cfg["traffic_mode"],
-                         accident_prob=cfg["accident_prob"], static_traffic_object=cfg["static_traffic_object"],
-                         need_inverse_traffic=cfg["need_inverse_traffic"], random_lane_width=cfg["random_lane_width"],
-                         random_lane_num=cfg["random_lane_num"], random_agent_model=cfg["random_agent_model"],
-                         random_dynamics=cfg["random_dynamics"], initial_agents=cfg["initial_agents"],
-                         agent_policy=cfg["agent_policy"], spawn_roads=cfg["spawn_roads"],
-                         random_traffic=cfg["random_traffic"], traffic_epoch=cfg.get("traffic_epoch", 0),
-                         destination=cfg["vehicle_config"]["destination"])
+        self.cap = self._build_capacity()
+        seeds, uniq, env_scene = self._assign_seeds()
+        tables, map_of_seed = self._build(uniq, self._scene_config())
+        if not cfg["is_multi_agent"]:
+            self._trim_capacity()
+        self._world_tables(tables, [map_of_seed[s] for s in seeds])
+        self._state(seeds, env_scene)
+        if self.walk:
+            self._walk_pool(uniq)
+        self._md_config(len(tables))
+        self.set_detector_beams()
+
+    def _build_capacity(self):
+        """The slot count the scenes are built with.  Single-agent scenes are always generated with the maximum and cut to size
+        afterwards (_trim_capacity); multi-agent ones with mover_capacity, or (0 = auto) a slot per agent."""
+        cfg, A = self.cfg, self.A
+        if not cfg["is_multi_agent"]:
+            return abi.MD_MAX_CAP
+        if cfg["mover_capacity"]:
+            return cfg["mover_capacity"]
+        if self.tollgate:     # + the toll booths (one on every odd lane of both directions), slots in multiples of 8
+            return min(abi.MD_MAX_CAP, (A + 2 * (cfg["map_config"]["toll_lane_num"] // 2) + 7) // 8 * 8)
+        return A
+
+    def _assign_seeds(self):
+        """-> (the scenario seed of every env, the seeds to build, the pool scene of every env or None).  The PG walk
+        (walk_scenarios): the scene pool is every seed of the slice, built once whatever the env count; env e starts at the first
+        scene of its walk (scenario.walk_scene), and md_swap_draw moves it on through the pool on the device."""
+        cfg, E = self.cfg, self.E
+        self.walk, self.pool, self.walk_params = bool(cfg.get("walk_scenarios")), None, (0, 0, 0, 0, 0)
+        if not self.walk:
+            self.seeds = [cfg["start_seed"] + ((cfg["env_seed_offset"] + e) % cfg["num_scenarios"]) for e in range(E)]
+            return self.seeds, sorted(set(self.seeds)), None
+        from metadrive_ped_amd.scenario import walk_params, walk_scene
+        self.walk_params = walk_params(cfg)
+        self.seeds = [cfg["start_seed"] + p for p in range(cfg["num_scenarios"])]   # names the slice, like ScenarioHostScene.seeds of a walk
+        env_scene = [int(p) for p in walk_scene(cfg, np.arange(E), 0)]
+        return [self.seeds[p] for p in env_scene], self.seeds, env_scene
+
+    def _scene_config(self):
+        """What EnvScene / RoundaboutScene read of the config (picklable: it travels to the build workers with the job)"""
+        cfg, vc = self.cfg, self.cfg["vehicle_config"]
+        scene_cfg = dict(cap=self.cap, agents_per_env=self.A, spawn_lane_index=cfg["agent_configs"]["default_agent"]["spawn_lane_index"],
+                         agent_vehicle_model=vc["vehicle_model"], agent_size_mass={k: vc[k] for k in ("width", "length", "height", "mass")},
+                         traffic_epoch=cfg.get("traffic_epoch", 0))
+        scene_cfg.update({k: vc[k] for k in ("spawn_longitude", "spawn_lateral", "spawn_velocity", "spawn_velocity_car_frame", "destination")})
+        scene_cfg.update({k: cfg[k] for k in (
+            "physics_world_step_size", "random_spawn_lane_index", "traffic_density", "traffic_mode", "accident_prob",
+            "static_traffic_object", "need_inverse_traffic", "random_lane_width", "random_lane_num", "random_agent_model",
+            "random_dynamics", "initial_agents", "agent_policy", "spawn_roads", "random_traffic")})
+        return scene_cfg
+
+    def _build(self, uniq, scene_cfg):
+        """Maps and scenes of the seeds `uniq` -> (the map tables, seed -> its map's index); sets self.scenes / map_tables / spawn.
+        Reset-time host work goes to the persistent build workers (metadrive_ped_amd/hostpool.py): they are started before this
+        process touches the GPU and kept; a process that already has a GPU context and no workers builds serially (it must not
+        fork).  build_workers = 1 forces the serial path."""
+        cfg = self.cfg
         self.spawn = None
-        if not cfg["is_multi_agent"]:
-            scene_cfg["cap"] = abi.MD_MAX_CAP
-        jobs = [(s, dict(mc), cfg["block_dist_config"], scene_cfg) for s in uniq]
-        # reset-time host work goes to the persistent build workers (metadrive_ped_amd/hostpool.py): they are started before
-        # this process touches the GPU and kept; a process that already has a GPU context and no workers builds serially
-        # (it must not fork).  build_workers = 1 forces the serial path.
-        shared_map = cfg["is_multi_agent"] and cfg["marl_map"] != "pg"
-        build_fn = _build_one
-        if cfg["is_multi_agent"] and not cfg["mover_capacity"]:
-            scene_cfg["cap"] = cap = A
-            if self.tollgate:     # + the toll booths (one on every odd lane of both directions), slots in multiples of 8
-                cap = min(abi.MD_MAX_CAP, (A + 2 * (mc["toll_lane_num"] // 2) + 7) // 8 * 8)
-                scene_cfg["cap"] = cap
-            self.cap = cap
-            jobs = [(s, dict(mc), cfg["block_dist_config"], scene_cfg) for s in uniq]
-        if cfg["is_multi_agent"] and not shared_map:
-            build_fn = _build_one_marl_pg
-            self.spawn = dict(n_dest=1)          # per-map spawn tables travel with the map tables
-        if shared_map:
+        if cfg["is_multi_agent"] and cfg["marl_map"] != "pg":      # one shared map, one scene per seed
             mt, marl_scenes, self.spawn = _build_marl(cfg, scene_cfg, uniq)
-            built = [(mt, marl_scenes[s]) for s in uniq]
+            tables, map_of_seed, self.scenes = [mt], {s: 0 for s in uniq}, {s: marl_scenes[s] for s in uniq}
         else:
-            built = hostpool.build_all(build_fn, jobs, workers=int(cfg.get("build_workers", 0)), cache=bool(cfg.get("build_cache", False)), sticky=True)
-        for s, (mt, sc) in zip(uniq, built):
-            if shared_map:
-                map_of_seed[s] = 0
-                if not tables:
-                    tables.append(mt)
-            else:
-                map_of_seed[s] = len(tables)
-                tables.append(mt)
-            scenes[s] = sc
-        if not cfg["is_multi_agent"]:
-            # single-agent scenes are always generated with the maximum slot count and cut to size here (vehicles keep their
-            # low slots, props the top ones: the same arrays as a build at that size), so that one built scene serves every
-            # capacity -- the build memo keys on the job
-            need = max(A + sc.n_traffic + sc.n_props for sc in scenes.values())
-            cap = cfg["mover_capacity"] or min(abi.MD_MAX_CAP, max(8, (need + 7) // 8 * 8))
-            if need > cap:
-                raise ValueError("more than cap={} movers in an env ({}); raise `mover_capacity`".format(cap, need))
-            for sc in scenes.values():
-                sc.trim(cap)
-            self.cap = cap
+            build_fn = _build_one
+            if cfg["is_multi_agent"]:
+                build_fn = _build_one_marl_pg
+                self.spawn = dict(n_dest=1)          # per-map spawn tables travel with the map tables
+            jobs = [(s, dict(cfg["map_config"]), cfg["block_dist_config"], scene_cfg) for s in uniq]
+            built = hostpool.build_all(build_fn, jobs, workers=int(cfg.get("build_workers", 0)), cache=bool(cfg.get("build_cache", False)),
+                                       sticky=True)
+            tables, map_of_seed = [mt for mt, _ in built], {s: i for i, s in enumerate(uniq)}
+            self.scenes = {s: sc for s, (_, sc) in zip(uniq, built)}
         self.map_tables = tables
-        self.scenes = scenes
-        env_map = [map_of_seed[s] for s in seeds]
+        return tables, map_of_seed
+
+    def _trim_capacity(self):
+        """Single-agent scenes are always generated with the maximum slot count and cut to size here (vehicles keep their low
+        slots, props the top ones: the same arrays as a build at that size), so that one built scene serves every capacity -- the
+        build memo keys on the job."""
+        need = max(self.A + sc.n_traffic + sc.n_props for sc in self.scenes.values())
+        cap = self.cfg["mover_capacity"] or min(abi.MD_MAX_CAP, max(8, (need + 7) // 8 * 8))
+        if need > cap:
+            raise ValueError("more than cap={} movers in an env ({}); raise `mover_capacity`".format(cap, need))
+        for sc in self.scenes.values():
+            sc.trim(cap)
+        self.cap = cap
+
+    def _world_tables(self, tables, env_map):
+        cfg = self.cfg
         self.world = WorldTables(tables, env_map, beam_table(self.n_beams))
-        if self.spawn is not None and shared_map:
-            a = self.world.arrays
+        a = self.world.arrays
+        if self.spawn is not None and "spawn_lane" in self.spawn:      # the shared map's spawn tables
             a["spawn_off"] = np.asarray([0, len(self.spawn["spawn_lane"])], np.int32)
             for k in ("spawn_place", "spawn_lane", "spawn_route", "spawn_route_meta"):
                 a[k] = np.ascontiguousarray(self.spawn[k])
-        N = E * cap
-
-        def draw_rows(of_seeds):
-            """The snapshot rows and per-slot constants (BatchedEngine.DRAW_ARRAYS) of the scenes `of_seeds`, cap slots each"""
-            def stack(field):
-                return np.concatenate([getattr(scenes[s], field) for s in of_seeds], axis=0)
-            d = {}
-            d["shape0"] = stack("shape")
-            d["dyn0"] = stack("dyn")
-            d["nav0"] = stack("nav")
-            d["pid0"] = stack("pid")
-            d["param"] = stack("param")
-            d["route_nodes"] = stack("route_nodes")
-            d["route_roads"] = stack("route_roads")
-            d["final_lane"] = stack("final_lane")
-            d["idm_rand"] = stack("idm_rand")
-            # MdNav.road0 / road1: the road ids under the two route cursors, kept beside them (ABI v7) so that the per-step
-            # logic never indexes the route arrays
-            n = len(of_seeds) * cap
-            rows = np.arange(n)
-            rr = d["route_roads"].reshape(n, abi.MD_ROUTE_LEN)
-            d["nav0"]["road0"] = rr[rows, np.clip(d["nav0"]["ck0"], 0, abi.MD_ROUTE_LEN - 1)]
-            d["nav0"]["road1"] = rr[rows, np.clip(d["nav0"]["ck1"], 0, abi.MD_ROUTE_LEN - 1)]
-            return d
-
-        def rng_of(of_seeds):   # xorshift32 needs a non-zero state; derive it from the scenario seed
-            return np.asarray([((s * 2654435761) ^ 0x9E3779B9) & 0xFFFFFFFF or 1 for s in of_seeds], np.uint32)
-
-        st = draw_rows(seeds)
-        st["shape"] = st["shape0"].copy()
-        st["dyn"] = st["dyn0"].copy()
-        st["nav"] = st["nav0"].copy()
-        st["pid"] = st["pid0"].copy()
-        st["action"] = np.zeros((N, 2), np.float32)
-        st["flags"] = np.zeros(N, np.uint32)
-        st["obs"] = np.zeros((E * A, self.obs_dim), np.float32)
-        st["reward"] = np.zeros(E * A, np.float32)
-        st["cost"] = np.zeros(E * A, np.float32)
-        st["step_info"] = np.zeros((E * A, 8), np.float32)
-        st["done_out"] = np.zeros((E * A, 4), np.uint8)          # (terminated, truncated, flag word lo / hi) straight from the kernel
-        st["need_reset"] = np.ones(E, np.int32)
-        self.traffic_respawns = "spawn_off" in self.world.arrays and not cfg["is_multi_agent"]
-        if cfg["is_multi_agent"] or self.traffic_respawns:
-            # respawns (agents in MARL, traffic in the respawn / hybrid modes) rewrite routes and draw random numbers
-            st["route_nodes0"] = st["route_nodes"].copy()
-            st["route_roads0"] = st["route_roads"].copy()
-            st["final_lane0"] = st["final_lane"].copy()
-            st["rng"] = rng_of(seeds)
+        self.traffic_respawns = "spawn_off" in a and not cfg["is_multi_agent"]
         if cfg["is_multi_agent"] and cfg["random_agent_model"]:
             from metadrive_ped_amd.marl import vehicle_class_table
+            a["vclass"] = vehicle_class_table(cfg["physics_world_step_size"])
+
+    def _draw_rows(self, of_seeds):
+        """The snapshot rows and per-slot constants (DRAW_FIELDS) of the scenes `of_seeds`, cap slots each"""
+        d = {k: np.concatenate([getattr(self.scenes[s], field) for s in of_seeds], axis=0) for k, field in DRAW_FIELDS}
+        # MdNav.road0 / road1: the road ids under the two route cursors, kept beside them (ABI v7) so that the per-step
+        # logic never indexes the route arrays
+        n = len(of_seeds) * self.cap
+        rr = d["route_roads"].reshape(n, abi.MD_ROUTE_LEN)
+        for road, ck in (("road0", "ck0"), ("road1", "ck1")):
+            d["nav0"][road] = rr[np.arange(n), np.clip(d["nav0"][ck], 0, abi.MD_ROUTE_LEN - 1)]
+        return d
+
+    def _state(self, seeds, env_scene):
+        cfg, E, A, cap = self.cfg, self.E, self.A, self.cap
+        st = step_state(E, A, cap, self.obs_dim, self._draw_rows(seeds), env_scene)
+        if cfg["is_multi_agent"] or self.traffic_respawns:
+            # respawns (agents in MARL, traffic in the respawn / hybrid modes) rewrite routes and draw random numbers
+            for k in ("route_nodes", "route_roads", "final_lane"):
+                st[k + "0"] = st[k].copy()
+            st["rng"] = _traffic_rng(seeds)
+        if cfg["is_multi_agent"] and cfg["random_agent_model"]:
             st["param0"] = st["param"].copy()
-            self.world.arrays["vclass"] = vehicle_class_table(cfg["physics_world_step_size"])
         if cfg["is_multi_agent"]:
             st["env_steps"] = np.zeros(E, np.int32)
             st["agent_id"] = np.tile(np.arange(cap, dtype=np.int32), E)
@@ -328,45 +316,42 @@ class HostScene:
             st["expert_takeover"] = np.zeros(E, np.uint8)
         if cfg["is_multi_agent"] and cfg["marl_map"] == "racing":
             st["idle_ring"] = np.zeros((E * A, abi.MD_IDLE_WINDOW), np.float32)     # movement_between_steps of every agent
-        if walk:
-            # what md_swap_draw copies into an env that moves on to pool scene p: its rows at p * cap, and the scene's traffic
-            # stream (the reference re-seeds the traffic manager with the scenario seed at every reset)
-            st["scene_of"] = np.asarray(env_scene, np.int32)
-            st["walk_ep"] = np.zeros(E, np.int32)
-            self.pool = draw_rows(pool_seeds)
-            if "rng" in st:
-                self.pool["rng"] = rng_of(pool_seeds)
-            dev_bytes = sum(v.nbytes for v in self.world.arrays.values()) + sum(v.nbytes for v in self.pool.values())
-            if dev_bytes > int(cfg["scenario_pool_max_bytes"]):
-                raise ValueError("walk_scenarios: the pool of num_scenarios={} scenes needs {:.2f} GiB on the device (maps and snapshot "
-                                 "rows, mover capacity {}), more than scenario_pool_max_bytes={:.2f} GiB: walk a smaller slice".format(
-                                     len(pool_seeds), dev_bytes / 2 ** 30, cap, int(cfg["scenario_pool_max_bytes"]) / 2 ** 30))
-            print("walk_scenarios: scene pool of num_scenarios={} scenes (mover capacity {}): {:.1f} MiB on the device".format(
-                len(pool_seeds), cap, dev_bytes / 2 ** 20), flush=True)
         self.state = st
-        self.md_config = make_md_config(cfg, E, A, cap, self.n_beams)
-        self.md_config.n_side, self.md_config.n_lane_line = self.n_side, self.n_ll
-        self.md_config.num_others, self.md_config.add_others_navi = self.num_others, int(self.add_others_navi)
-        self.md_config.random_agent_model = int(bool(cfg["random_agent_model"]))
-        self.md_config.agent_idm = {"IDMPolicy": abi.AGENT_IDM, "LaneChangePolicy": abi.AGENT_LANE_CHANGE}.get(cfg["agent_policy"],
-                                                                                                          abi.AGENT_INPUT)
-        self.md_config.enable_reverse = int(bool(cfg["vehicle_config"]["enable_reverse"]))
-        self.step_kernel = pick_step_kernel(cfg, len(tables))
-        self.md_config.step_kernel = {"wg": 0, "wave": 1}[self.step_kernel]
-        self.md_config.obs_dim = self.obs_dim
-        # detector beam fans start 90 deg off the heading (SideDetector.__init__, distance_detector.py:197)
-        self.side_beams = beam_table(self.n_side, np.pi / 2) if self.n_side else None
-        self.ll_beams = beam_table(self.n_ll, np.pi / 2) if self.n_ll else None
 
-    def clone_state(self):
-        return {k: v.copy() for k, v in self.state.items()}
+    def _walk_pool(self, pool_seeds):
+        """What md_swap_draw copies into an env that moves on to pool scene p: its rows at p * cap, and the scene's traffic
+        stream (the reference re-seeds the traffic manager with the scenario seed at every reset)"""
+        cfg = self.cfg
+        self.pool = self._draw_rows(pool_seeds)
+        if "rng" in self.state:
+            self.pool["rng"] = _traffic_rng(pool_seeds)
+        dev_bytes = sum(v.nbytes for v in self.world.arrays.values()) + sum(v.nbytes for v in self.pool.values())
+        if dev_bytes > int(cfg["scenario_pool_max_bytes"]):
+            raise ValueError("walk_scenarios: the pool of num_scenarios={} scenes needs {:.2f} GiB on the device (maps and snapshot "
+                             "rows, mover capacity {}), more than scenario_pool_max_bytes={:.2f} GiB: walk a smaller slice".format(
+                                 len(pool_seeds), dev_bytes / 2 ** 30, self.cap, int(cfg["scenario_pool_max_bytes"]) / 2 ** 30))
+        print("walk_scenarios: scene pool of num_scenarios={} scenes (mover capacity {}): {:.1f} MiB on the device".format(
+            len(pool_seeds), self.cap, dev_bytes / 2 ** 20), flush=True)
+
+    def _md_config(self, n_maps):
+        cfg = self.cfg
+        k = make_md_config(cfg, self.layout, self.E, self.A, self.cap)
+        k.random_agent_model = int(bool(cfg["random_agent_model"]))
+        k.enable_reverse = int(bool(cfg["vehicle_config"]["enable_reverse"]))
+        self.step_kernel = pick_step_kernel(cfg, n_maps)
+        k.step_kernel = {"wg": 0, "wave": 1}[self.step_kernel]
+        self.md_config = k
 
 
-def make_md_config(cfg, E, A, cap, n_beams):
+def make_md_config(cfg, layout, E, A, cap):
+    """MdConfig of a batch: the sizes, the observation layout's counts (`layout`: the scene's ObsLayout) and what both env
+    families read from the config; a host scene sets its own family's fields afterwards."""
     k = abi.MdConfig()
     k.struct_size = C.sizeof(abi.MdConfig)
     k.n_envs, k.agents_per_env, k.cap = E, A, cap
-    k.n_beams, k.obs_dim = n_beams, 19 + n_beams
+    k.n_beams, k.n_side, k.n_lane_line, k.obs_dim = layout.n_beams, layout.n_side, layout.n_ll, layout.obs_dim
+    k.num_others, k.add_others_navi = layout.num_others, int(layout.add_others_navi)
+    k.agent_idm = {"IDMPolicy": abi.AGENT_IDM, "LaneChangePolicy": abi.AGENT_LANE_CHANGE}.get(cfg["agent_policy"], abi.AGENT_INPUT)
     k.substeps = int(cfg["decision_repeat"])
     k.horizon = int(cfg["horizon"]) if cfg["horizon"] else 0
     k.dt = float(cfg["physics_world_step_size"])
@@ -406,6 +391,8 @@ def make_md_config(cfg, E, A, cap, n_beams):
 
 
 def make_structs(world_arrays, state_arrays, md_config, n_maps, n_envs, ptr_of):
+    """(MdWorld, MdState, MdConfig) over the arrays wherever they live (ptr_of(array) -> address); `world_arrays` also holds the
+    host scene's world_scalars()."""
     w = abi.MdWorld()
     w.n_maps, w.n_envs = n_maps, n_envs
     abi.fill_struct(w, abi.WORLD_FIELDS, world_arrays, ptr_of)
@@ -431,6 +418,11 @@ class _NullCtx:
 _NULL_CTX = _NullCtx()
 
 
+def _ptr(t):
+    """A tensor's address as a C-ABI pointer argument; None -> NULL"""
+    return C.c_void_p(t.data_ptr() if t is not None else None)
+
+
 class BatchedEngine:
     def __init__(self, cfg, host=None):
         import torch
@@ -450,6 +442,7 @@ class BatchedEngine:
         self._expert_w = None
         self._expert_beams = None
         self._track_det = False
+        self._clear_buffers()
         self._rec = None
         self._tracks = None
         if self.device.index is None:
@@ -457,12 +450,19 @@ class BatchedEngine:
             self._dev_index = self.device.index
         self.build()
 
+    def _clear_buffers(self):
+        """Per-engine buffers made on first use; a build() drops them with the batch they were sized for."""
+        self._expert_action = None      # step(): the expert's action, ExpertPolicy
+        self._protect_action = None     # ai_protect_forward: the applied action ...
+        self.protect_flags = None       # ... and its flag bytes; None before the first protected step
+        self._difficulty_dev = None     # BatchedScenarioEnv: the pool's difficulty scores on the device
+
     # -- upload helpers ---------------------------------------------------------------------------
     def _to_dev(self, arr):
         t = self.torch.from_numpy(np.ascontiguousarray(arr).view(np.uint8).reshape(-1))
         return t.to(self.device)
 
-    DRAW_ARRAYS = ("shape0", "dyn0", "nav0", "pid0", "param", "route_nodes", "route_roads", "final_lane", "idm_rand")
+    DRAW_ARRAYS = tuple(k for k, _ in DRAW_FIELDS)
     DRAW_EPOCH_STRIDE = 4099          # traffic_epoch of draw k = the env's epoch + k * stride
 
     def n_traffic_draws(self):
@@ -488,6 +488,7 @@ class BatchedEngine:
     def build(self):
         """(Re)generate maps + scenes on the host and upload.  BaseEnv.reset's map/agent/traffic managers."""
         torch = self.torch
+        self._clear_buffers()
         K = self.n_traffic_draws()
         draws = None
         if self.host is None:
@@ -511,10 +512,7 @@ class BatchedEngine:
         self.state_dev = {k: self._to_dev(v) for k, v in h.state.items()}
         self._pack_step_outputs()
         ptr = lambda t: t.data_ptr()
-        wd = dict(self.world_dev)
-        wd["lane_off_host"], wd["road_off_host"] = h.world.arrays["lane_off"], h.world.arrays["road_off"]
-        wd["n_dest_host"] = h.spawn["n_dest"] if h.spawn is not None else (1 if h.traffic_respawns else 0)
-        wd["n_vclass_host"] = len(h.world.arrays["vclass"]) if "vclass" in h.world.arrays else 0
+        wd = dict(self.world_dev, **h.world_scalars())
         self._side_beams = self._to_dev(h.side_beams) if h.side_beams is not None else None
         self._ll_beams = self._to_dev(h.ll_beams) if h.ll_beams is not None else None
         # scenario mode: md_step runs the side / lane-line detectors itself (MdWorld.side_beam_cs / ll_beam_cs) on waves that
@@ -604,6 +602,11 @@ class BatchedEngine:
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _launch(self, name, *args):
+        """One C-ABI launch on the engine's batch: md_<name>(&world, &state, &config, *args, stream), checked.  The caller is
+        inside _on_device()."""
+        self._check(getattr(self.lib, name)(C.byref(self.w), C.byref(self.s), C.byref(self.k), *args, self._stream()), name)
+
     def _on_device(self):
         """Context in which HIP's current device is the engine's (config["device"]): a no-op object when it already is
         (the usual one-process-per-GPU case), torch.cuda.device(...) otherwise -- a launch must not land on another
@@ -642,7 +645,7 @@ class BatchedEngine:
             self._step_raw()
 
     def _step_raw(self):
-        self._check(self.lib.md_step(C.byref(self.w), C.byref(self.s), C.byref(self.k), self._stream()), "md_step")
+        self._launch("md_step")
         L = self.host.layout
         vc = self.cfg["vehicle_config"]
         obs = self.state_dev["obs"]
@@ -650,13 +653,10 @@ class BatchedEngine:
             pass
         elif L.n_side and L.n_ll and L.n_side + L.n_ll <= 255:
             # both detector clouds in ONE launch and one pass over the line pieces (md_line_detectors)
-            self._check(self.lib.md_line_detectors(
-                C.byref(self.w), C.byref(self.s), C.byref(self.k),
-                C.c_void_p(self._side_beams.data_ptr()), L.n_side, C.c_float(float(vc["side_detector"]["distance"])),
-                C.c_uint32(self.SIDE_MASK), L.side_off,
-                C.c_void_p(self._ll_beams.data_ptr()), L.n_ll, C.c_float(float(vc["lane_line_detector"]["distance"])),
-                C.c_uint32(self.LANE_LINE_MASK), L.ll_off,
-                C.c_void_p(obs.data_ptr()), L.obs_dim, self._stream()), "md_line_detectors")
+            self._launch("md_line_detectors",
+                         _ptr(self._side_beams), L.n_side, C.c_float(float(vc["side_detector"]["distance"])), C.c_uint32(self.SIDE_MASK), L.side_off,
+                         _ptr(self._ll_beams), L.n_ll, C.c_float(float(vc["lane_line_detector"]["distance"])), C.c_uint32(self.LANE_LINE_MASK),
+                         L.ll_off, _ptr(obs), L.obs_dim)
         else:
             if L.n_side:     # SideDetector cloud replaces obs[0:2] (obs/state_obs.py:77-86)
                 self.line_detector(self._side_beams, L.n_side, float(vc["side_detector"]["distance"]), self.SIDE_MASK, obs, L.obs_dim, L.side_off)
@@ -730,8 +730,7 @@ class BatchedEngine:
             if (g <= 0.0 and p <= 0.0) or n <= 0:
                 continue
             if self._noise_gen is None:
-                self._noise_gen = torch.Generator(device=self.device)
-                self._noise_gen.manual_seed(int(self.cfg["start_seed"]) + int(self.cfg["env_seed_offset"]))
+                self._noise_gen = self._seeded_generator()
             cloud = self.obs[..., off:off + n]
             if g > 0.0:
                 noise = torch.empty_like(cloud).normal_(0.0, g, generator=self._noise_gen)
@@ -742,9 +741,7 @@ class BatchedEngine:
                 cloud.masked_fill_(drop, 0.0)
 
     def line_detector(self, beams, n, dist, mask, out, stride, offset):
-        self._check(self.lib.md_line_detector(C.byref(self.w), C.byref(self.s), C.byref(self.k), C.c_void_p(beams.data_ptr()),
-                                              n, C.c_float(dist), C.c_uint32(mask), C.c_void_p(out.data_ptr()), stride, offset,
-                                              self._stream()), "md_line_detector")
+        self._launch("md_line_detector", _ptr(beams), n, C.c_float(dist), C.c_uint32(mask), _ptr(out), stride, offset)
 
     # -- the PPO expert (metadrive_ped_amd/expert.py, md_expert) -----------------------------------------------------------
     def _track_detected(self):
@@ -759,9 +756,7 @@ class BatchedEngine:
         self.s.detected = self.state_dev["detected"].data_ptr()
         scratch = self.torch.empty((self.E * self.A, self.n_beams), dtype=self.torch.float32, device=self.device)
         with self._on_device():
-            self._check(self.lib.md_lidar_detect(C.byref(self.w), C.byref(self.s), C.byref(self.k), C.c_void_p(scratch.data_ptr()),
-                                                 self.n_beams, 0, C.c_void_p(self.state_dev["detected"].data_ptr()), self._stream()),
-                        "md_lidar_detect")
+            self._launch("md_lidar_detect", _ptr(scratch), self.n_beams, 0, _ptr(self.state_dev["detected"]))
 
     def expert_weights(self):
         """The packed expert weights on the device (uploaded once per engine)."""
@@ -779,6 +774,25 @@ class BatchedEngine:
             self._expert_beams = self._to_dev(beam_table(240))
         return self._expert_beams
 
+    def _seeded_generator(self):
+        """A device generator seeded with start_seed + env_seed_offset (reproducible, shard-dependent): the lidar noise and the
+        expert's draws each have one of their own."""
+        g = self.torch.Generator(device=self.device)
+        g.manual_seed(int(self.cfg["start_seed"]) + int(self.cfg["env_seed_offset"]))
+        return g
+
+    def _expert_noise(self, rows):
+        """One [rows, 2] N(0, 1) draw of the engine's expert generator"""
+        if self._expert_gen is None:
+            self._expert_gen = self._seeded_generator()
+        return self.torch.randn((rows, 2), dtype=self.torch.float32, device=self.device, generator=self._expert_gen)
+
+    def _check_f32(self, name, t, rows, cols):
+        """A caller's tensor that a kernel reads or writes as rows x cols floats (leading dims may be split: [E, A, cols])"""
+        if (t.numel() != rows * cols or t.shape[-1] != cols or t.dtype != self.torch.float32 or t.device != self.device
+                or not t.is_contiguous()):
+            raise ValueError("{} must be a contiguous float32 [{}, {}] tensor on the engine's device".format(name, rows, cols))
+
     def expert_forward(self, deterministic=False, need_obs=False, action_out=None, mlp_out=None, noise=None, own_sensors=None):
         """ONE md_expert launch on the current observation -> action [E, 2] (+ the corrected expert obs [E, 275] with
         need_obs).  deterministic=False: action = mean + exp(log_std) * N(0, 1), one [E, 2] draw of the engine's expert
@@ -787,49 +801,25 @@ class BatchedEngine:
         (+ [E * A, 275]), row e * A + a = agent a of env e, one [E * A, 2] draw; rows of an env about to restore itself are zeros."""
         torch = self.torch
         own = bool(self.cfg.get("expert_own_sensors")) if own_sensors is None else bool(own_sensors)
-        if own:
-            return self._expert_sense(deterministic, need_obs, action_out, mlp_out, noise)
-        if self.A != 1:
-            raise ValueError("the expert drives single-agent envs")
-        self._track_detected()
-        w = self.expert_weights()
+        if own:      # md_expert_sense reads the live state through the expert's own beam table
+            rows, name, extra = self.E * self.A, "md_expert_sense", (_ptr(self.expert_beams()), )
+        else:        # md_expert reads the env's observation row and the lidar's detected sets
+            if self.A != 1:
+                raise ValueError("the expert drives single-agent envs")
+            self._track_detected()
+            rows, name, extra = self.E, "md_expert", ()
         if deterministic:
             noise = None
-        elif noise is None:
-            if self._expert_gen is None:
-                self._expert_gen = torch.Generator(device=self.device)
-                self._expert_gen.manual_seed(int(self.cfg["start_seed"]) + int(self.cfg["env_seed_offset"]))
-            noise = torch.randn((self.E, 2), dtype=torch.float32, device=self.device, generator=self._expert_gen)
+        for what, t, cols in (("noise", noise, 2), ("action_out", action_out, 2), ("mlp_out", mlp_out, 4)):
+            if t is not None:
+                self._check_f32(what, t, rows, cols)
+        if noise is None and not deterministic:
+            noise = self._expert_noise(rows)
         if action_out is None:
-            action_out = torch.empty((self.E, 2), dtype=torch.float32, device=self.device)
-        obs = torch.empty((self.E, 275), dtype=torch.float32, device=self.device) if need_obs else None
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+            action_out = torch.empty((rows, 2), dtype=torch.float32, device=self.device)
+        obs = torch.empty((rows, 275), dtype=torch.float32, device=self.device) if need_obs else None
         with self._on_device():
-            self._check(self.lib.md_expert(C.byref(self.w), C.byref(self.s), C.byref(self.k), ptr(w), ptr(noise), ptr(action_out),
-                                           ptr(mlp_out), ptr(obs), self._stream()), "md_expert")
-        return (action_out, obs) if need_obs else action_out
-
-    def _expert_sense(self, deterministic, need_obs, action_out, mlp_out, noise):
-        torch = self.torch
-        n = self.E * self.A
-        w, beams = self.expert_weights(), self.expert_beams()
-        if deterministic:
-            noise = None
-        elif noise is None:
-            if self._expert_gen is None:
-                self._expert_gen = torch.Generator(device=self.device)
-                self._expert_gen.manual_seed(int(self.cfg["start_seed"]) + int(self.cfg["env_seed_offset"]))
-            noise = torch.randn((n, 2), dtype=torch.float32, device=self.device, generator=self._expert_gen)
-        for name, t, cols in (("noise", noise, 2), ("action_out", action_out, 2), ("mlp_out", mlp_out, 4)):
-            if t is not None and (t.numel() != n * cols or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()):
-                raise ValueError("{} must be a contiguous float32 tensor of {} x {} on the engine's device".format(name, n, cols))
-        if action_out is None:
-            action_out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
-        obs = torch.empty((n, 275), dtype=torch.float32, device=self.device) if need_obs else None
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
-        with self._on_device():
-            self._check(self.lib.md_expert_sense(C.byref(self.w), C.byref(self.s), C.byref(self.k), ptr(w), ptr(beams), ptr(noise),
-                                                 ptr(action_out), ptr(mlp_out), ptr(obs), self._stream()), "md_expert_sense")
+            self._launch(name, _ptr(self.expert_weights()), *extra, _ptr(noise), _ptr(action_out), _ptr(mlp_out), _ptr(obs))
         return (action_out, obs) if need_obs else action_out
 
     def ai_protect_forward(self, actions, noise=None, saver_out=None):
@@ -840,28 +830,21 @@ class BatchedEngine:
         torch = self.torch
         if "takeover" not in self.state_dev:
             raise ValueError("ai_protect_forward needs agent_policy='AIProtectPolicy'")
-        w = self.expert_weights()
         if noise is None:
-            if self._expert_gen is None:
-                self._expert_gen = torch.Generator(device=self.device)
-                self._expert_gen.manual_seed(int(self.cfg["start_seed"]) + int(self.cfg["env_seed_offset"]))
-            noise = torch.randn((self.E, 2), dtype=torch.float32, device=self.device, generator=self._expert_gen)
+            noise = self._expert_noise(self.E)
         a = actions
         if tuple(a.shape) != (self.E, 2):
             raise ValueError("actions must have shape [{}, 2], got {}".format(self.E, tuple(a.shape)))
         if a.dtype != torch.float32 or a.device != self.device or not a.is_contiguous():
             a = a.to(self.device, torch.float32).contiguous()
-        if tuple(noise.shape) != (self.E, 2) or noise.dtype != torch.float32 or noise.device != self.device or not noise.is_contiguous():
-            raise ValueError("noise must be a contiguous float32 [{}, 2] tensor on the engine's device".format(self.E))
-        if getattr(self, "_protect_action", None) is None or self._protect_action.shape[0] != self.E:
+        self._check_f32("noise", noise, self.E, 2)
+        if self._protect_action is None:
             self._protect_action = torch.empty((self.E, 2), dtype=torch.float32, device=self.device)
             self.protect_flags = torch.zeros(self.E, dtype=torch.uint8, device=self.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
         with self._on_device():
-            self._check(self.lib.md_ai_protect(C.byref(self.w), C.byref(self.s), C.byref(self.k), ptr(w), ptr(noise), ptr(a),
-                                               C.c_float(float(self.cfg["save_level"])), ptr(self.state_dev["takeover"]),
-                                               ptr(self.state_dev["expert_takeover"]), ptr(self._protect_action), ptr(self.protect_flags),
-                                               ptr(saver_out), self._stream()), "md_ai_protect")
+            self._launch("md_ai_protect", _ptr(self.expert_weights()), _ptr(noise), _ptr(a), C.c_float(float(self.cfg["save_level"])),
+                         _ptr(self.state_dev["takeover"]), _ptr(self.state_dev["expert_takeover"]), _ptr(self._protect_action),
+                         _ptr(self.protect_flags), _ptr(saver_out))
         return self._protect_action
 
     def step(self, actions, noise=None):
@@ -880,7 +863,7 @@ class BatchedEngine:
             return
         if self.cfg["agent_policy"] == "ExpertPolicy":
             rows = self.E * self.A if self.cfg.get("expert_own_sensors") else self.E
-            if getattr(self, "_expert_action", None) is None or self._expert_action.shape[0] != rows:
+            if self._expert_action is None:
                 self._expert_action = self.torch.empty((rows, 2), dtype=self.torch.float32, device=self.device)
             actions = self.expert_forward(deterministic=False, action_out=self._expert_action).view(self.E, -1, 2)
         if self.cfg["agent_policy"] == "AIProtectPolicy":     # the saver looks at the agents' actions on the state the previous step left
@@ -904,17 +887,15 @@ class BatchedEngine:
 
     def call(self, name):
         """Single-phase entry points (parity tests): md_integrate, md_localize, ..."""
-        fn = getattr(self.lib, name)
         with self._on_device():
-            self._check(fn(C.byref(self.w), C.byref(self.s), C.byref(self.k), self._stream()), name)
+            self._launch(name)
 
     def lidar(self, out, stride, offset):
         with self._on_device():
             self._lidar(out, stride, offset)
 
     def _lidar(self, out, stride, offset):
-        self._check(self.lib.md_lidar(C.byref(self.w), C.byref(self.s), C.byref(self.k), C.c_void_p(out.data_ptr()),
-                                      stride, offset, self._stream()), "md_lidar")
+        self._launch("md_lidar", _ptr(out), stride, offset)
 
     # -- user-spawned traffic participants (engine.spawn_object(Pedestrian, ...) + set_velocity of the reference,
     #    tests/test_functionality/test_pedestrian.py:38-55); see participants.py ---------------------------------

@@ -124,7 +124,7 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
         if self.config["agent_policy"] == "AIProtectPolicy":     # BaseVehicle.reset (base_vehicle.py:361,367)
             self.engine.state_dev["takeover"].zero_()
             self.engine.state_dev["expert_takeover"].zero_()
-            if getattr(self.engine, "protect_flags", None) is not None:
+            if self.engine.protect_flags is not None:
                 self.engine.protect_flags.zero_()
         return self._obs(), self._info()
 
@@ -260,7 +260,7 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
 
     def _protect_flags(self):
         e = self.engine
-        fl = getattr(e, "protect_flags", None)      # None before the first step: nothing reported yet
+        fl = e.protect_flags      # None before the first step: nothing reported yet
         return fl if fl is not None else e.torch.zeros(self.num_envs, dtype=e.torch.uint8, device=e.device)
 
     def _scenario_index(self):

@@ -129,7 +129,7 @@ class BatchedScenarioEnv(BatchedEnvBase):
 
     def _difficulty(self):
         e = self.engine
-        if getattr(e, "_difficulty_dev", None) is None:
+        if e._difficulty_dev is None:
             e._difficulty_dev = e.torch.as_tensor(e.host.difficulty, device=e.device)
         return e._difficulty_dev
 

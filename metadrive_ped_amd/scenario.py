@@ -25,6 +25,7 @@ import numpy as np
 from metadrive_ped_amd import abi
 from metadrive_ped_amd.mapgen.tables import beam_table
 from metadrive_ped_amd.obs_layout import ObsLayout
+from metadrive_ped_amd.scene import HostSceneBase, step_state
 
 # ScenarioEnv's own defaults (envs/scenario_env.py:21-95); keys not listed keep BaseEnv's
 SCENARIO_DEFAULT_CONFIG = dict(
@@ -618,87 +619,102 @@ def _poly_balls(poly_off, segs):
     return out, off.astype(np.int32)
 
 
-class ScenarioHostScene:
+def curriculum_state(E, n_scenes, eval_):
+    """The curriculum's per-env arrays (include/md_curriculum.h MdCurriculum, keys cur_*) of a batch before its first reset:
+    every env at level 0, no seed yet, empty queues of `eval_` entries, nothing of the `n_scenes` scenes covered."""
+    return dict(cur_level=np.zeros(E, np.int32), cur_seed=np.full(E, -1, np.int32), cur_q_len=np.zeros(E, np.int32),
+                cur_q_key=np.full((E, eval_), -1, np.int32), cur_q_success=np.zeros((E, eval_), np.int32),
+                cur_q_route=np.zeros((E, eval_), np.float32), cur_cover=np.zeros((E, (n_scenes + 31) // 32), np.uint32),
+                cur_cover_n=np.zeros(E, np.int32), cur_rep_i=np.zeros((E, 2), np.int32), cur_rep_f=np.zeros((E, 3), np.float64))
+
+
+class ScenarioHostScene(HostSceneBase):
     """The HostScene of scenario mode: one scenario description per env (`scenarios[e]` -> env e), or -- with walk_scenarios --
     the scene pool of the dataset slice (`scenarios[p]` = scenario start_scenario_index + p), every scene built once, that the
     envs walk through (walk_scene; the device moves an env on in md_swap_draw)."""
     def __init__(self, cfg, scenarios):
-        from metadrive_ped_amd.engine import make_md_config
         self.cfg = cfg
-        E = cfg["num_envs"]
-        walk = bool(cfg.get("walk_scenarios"))
+        self.E, self.A, self.walk = cfg["num_envs"], 1, bool(cfg.get("walk_scenarios"))
+        self.spawn, self.traffic_respawns, self.scenes = None, False, {}
+        ObsLayout(cfg, scenario=True).export_to(self)      # self.layout, and n_beams / n_side / n_ll / ... / obs_dim
+        scenarios, order = self._assign_scenes(scenarios)
+        self._sizes(scenarios)
+        built = self._build(scenarios, order)
+        self._world_tables(built)
+        self._state(built)
+        self._md_config()
+        if self.walk:
+            dev_bytes = sum(v.nbytes for d in (self.world.arrays, self.pool) for v in d.values()) + self.tracks["shape"].nbytes \
+                + self.tracks["dyn"].nbytes
+            print("walk_scenarios: scene pool of num_scenarios={} scenes (T={}, mover capacity {}): {:.1f} MiB on the device".format(
+                len(scenarios), self.T, self.cap, dev_bytes / 2 ** 20))
+        self.set_detector_beams()
+
+    def _assign_scenes(self, scenarios):
+        """-> (the scenarios in pool order, their order in the slice or None); sets env_scene (the scene of every env: its own, or
+        the first of its walk), curriculum and difficulty."""
+        cfg, E = self.cfg, self.E
         self.curriculum, self.difficulty = None, None
-        order = None
-        if walk:
-            P = int(cfg["num_scenarios"])
-            if len(scenarios) != P:
-                raise ValueError("walk_scenarios: need the num_scenarios={} scenarios of the slice, got {}".format(P, len(scenarios)))
-            env_scene = [int(p) for p in walk_scene(cfg, np.arange(E), 0)]     # every env at the first scene of its walk
-            # the curriculum: the slice sorted by difficulty before the pool is built (ScenarioDataManager.sort_scenarios runs
-            # with more than one level only; scenario_difficulty is 0 otherwise)
-            self.curriculum = curriculum_params(cfg)
-            if self.curriculum[0] > 1:
-                scenarios, diff, order = sort_by_difficulty(scenarios)
-                self.difficulty = np.asarray(diff, np.float64)
-            else:
-                self.difficulty = np.zeros(P, np.float64)
-        else:
+        if not self.walk:
             if len(scenarios) != E:
                 raise ValueError("need one scenario per env: got {} for {} envs".format(len(scenarios), E))
-            env_scene = list(range(E))
-        S = len(scenarios)
+            self.env_scene = list(range(E))
+            return scenarios, None
+        P = int(cfg["num_scenarios"])
+        if len(scenarios) != P:
+            raise ValueError("walk_scenarios: need the num_scenarios={} scenarios of the slice, got {}".format(P, len(scenarios)))
+        self.env_scene = [int(p) for p in walk_scene(cfg, np.arange(E), 0)]     # every env at the first scene of its walk
+        # the curriculum: the slice sorted by difficulty before the pool is built (ScenarioDataManager.sort_scenarios runs
+        # with more than one level only; scenario_difficulty is 0 otherwise)
+        self.curriculum = curriculum_params(cfg)
+        if self.curriculum[0] > 1:
+            scenarios, diff, order = sort_by_difficulty(scenarios)
+            self.difficulty = np.asarray(diff, np.float64)
+            return scenarios, order
+        self.difficulty = np.zeros(P, np.float64)
+        return scenarios, None
+
+    def _sizes(self, scenarios):
+        """T, cap and the identity of the scenes (seeds, scenario_ids)"""
+        cfg, S = self.cfg, len(scenarios)
         T = max(int(sc["length"]) for sc in scenarios)   # frames of the batch; a shorter scene is over (all invalid) after its own
         n_tracks = max(len(sc["tracks"]) for sc in scenarios)
         cap = cfg["mover_capacity"] or min(abi.MD_MAX_CAP, max(8, (n_tracks + 7) // 8 * 8))
         if n_tracks > cap:
             raise ValueError("a scenario holds {} objects, the mover capacity is {}".format(n_tracks, cap))
-        if walk:
+        if self.walk:
             # the recorded frames dominate the pool: T x scenes x cap x (MdShape + heading, speed)
             frames = T * S * cap * (abi.SHAPE_DT.itemsize + 8)
             if frames > int(cfg["scenario_pool_max_bytes"]):
                 raise ValueError("walk_scenarios: the pool of num_scenarios={} scenes needs {:.2f} GiB of recorded frames alone "
                                  "(T={}, mover capacity {}), more than scenario_pool_max_bytes={:.2f} GiB: walk a smaller slice".format(
                                      S, frames / 2 ** 30, T, cap, int(cfg["scenario_pool_max_bytes"]) / 2 ** 30))
-        A = 1
-        self.E, self.cap, self.A, self.T = E, cap, A, T
-        ObsLayout(cfg, scenario=True).export_to(self)      # self.layout, and n_beams / n_side / n_ll / ... / obs_dim
+        self.cap, self.T = cap, T
         # scene e <-> dataset index start_scenario_index + (env_seed_offset + e) % num_scenarios (scenario_data.scenario_indices):
         # the identity checkpoints and track sets are checked against, and the fallback parameter seed of a description that
         # carries none -- tied to WHICH scenario it is, not to where it sits in the batch.  A walk's pool: the slice itself.
         from metadrive_ped_amd.scenario_data import scenario_indices
-        self.seeds = [int(cfg["start_scenario_index"]) + p for p in range(S)] if walk else scenario_indices(cfg, E)
+        self.seeds = [int(cfg["start_scenario_index"]) + p for p in range(S)] if self.walk else scenario_indices(cfg, self.E)
         self.scenario_ids = [str(sc.get("id", sc.get("metadata", {}).get("scenario_id", i))) for sc, i in zip(scenarios, self.seeds)]
-        self.walk = walk
-        self.env_scene = env_scene
-        self.spawn = None
-        self.traffic_respawns = False
-        self.scenes, self.map_tables = {}, []
-        N = E * cap
-        dt = cfg["physics_world_step_size"]
 
-        # vehicle parameters are sampled from a stream seeded by the scenario's OWN seed where it carries one, so that a
-        # scene behaves the same in whatever batch (slot, shard) it is loaded
-        fallback = self.seeds if order is None else [int(cfg["start_scenario_index"]) + i for i in order]   # the dataset index
-        jobs = [(p, scenarios[p], cap, T, int(scenarios[p]["metadata"].get("seed", fallback[p])), dt, bool(cfg["no_traffic"]),
-                 float(cfg["map_region_size"])) for p in range(S)]
+    def _build(self, scenarios, order):
+        """Every scene once, through the build workers.  Vehicle parameters are sampled from a stream seeded by the scenario's OWN
+        seed where it carries one, so that a scene behaves the same in whatever batch (slot, shard) it is loaded."""
         from metadrive_ped_amd import hostpool
+        cfg = self.cfg
+        fallback = self.seeds if order is None else [int(cfg["start_scenario_index"]) + i for i in order]   # the dataset index
+        jobs = [(p, sc, self.cap, self.T, int(sc["metadata"].get("seed", fallback[p])), cfg["physics_world_step_size"],
+                 bool(cfg["no_traffic"]), float(cfg["map_region_size"])) for p, sc in enumerate(scenarios)]
         built = hostpool.build_all(_build_scene, jobs, workers=int(cfg.get("build_workers", 0)))
-        shape0 = np.concatenate([built[p]["shape0"] for p in env_scene])
-        dyn0 = np.concatenate([built[p]["dyn0"] for p in env_scene])
-        param = np.concatenate([built[p]["param"] for p in env_scene])
-        nav0 = np.zeros(N, dtype=abi.NAV_DT)
-        nav0["lane"], nav0["target_lane"], nav0["road0"], nav0["road1"] = -1, -1, -1, -1
-        pid0 = np.zeros(N, dtype=abi.PID_DT)
-        pid0["target_speed"] = 40.0
-        self.pool = None
-        if walk:   # the snapshot rows of every scene, at p * cap: what md_swap_draw copies into an env that moves on to scene p
-            self.pool = dict(shape0=np.concatenate([b_["shape0"] for b_ in built]), dyn0=np.concatenate([b_["dyn0"] for b_ in built]),
-                             nav0=np.resize(nav0[:cap], S * cap), pid0=np.resize(pid0[:cap], S * cap),
-                             param=np.concatenate([b_["param"] for b_ in built]))
-        fshape = np.concatenate([b_["fshape"] for b_ in built], axis=1)
-        fdyn = np.concatenate([b_["fdyn"] for b_ in built], axis=1)
-        meta = np.concatenate([b_["meta"] for b_ in built])
         self.track_ids = [b_["order"] for b_ in built]
+        self.tracks = dict(shape=np.concatenate([b_["fshape"] for b_ in built], axis=1),
+                           dyn=np.concatenate([b_["fdyn"] for b_ in built], axis=1), seeds=list(self.seeds), cap=self.cap)
+        return built
+
+    def _world_tables(self, built):
+        """Static bodies: one map per scene (its road lines + their grid); the lane / road / node tables are placeholders.  On
+        top of them the scenes' polylines, outlines, checkpoints, track records and runs, each with its offset table."""
+        from metadrive_ped_amd.mapgen.tables import WorldTables
         segs, poly_off, verts, polyv_off, ckpts, ckpt_off = [], [0], [], [0], [], [0]
         for b_ in built:
             for r in b_["segs"]:
@@ -709,10 +725,8 @@ class ScenarioHostScene:
                 polyv_off.append(polyv_off[-1] + len(v))
             ckpts.append(b_["ckpt"])
             ckpt_off.append(ckpt_off[-1] + len(b_["ckpt"]))
-        # static bodies: one map per scene (its road lines + their grid); the lane / road / node tables are placeholders
-        from metadrive_ped_amd.mapgen.tables import WorldTables
         self.map_tables = [b_["static"] for b_ in built]
-        self.world = WorldTables(self.map_tables, list(env_scene), beam_table(self.n_beams))
+        self.world = WorldTables(self.map_tables, list(self.env_scene), beam_table(self.n_beams))
         a = self.world.arrays
         a["poly_off"] = np.asarray(poly_off, np.int32)
         a["segs"] = np.concatenate(segs) if sum(len(x) for x in segs) else np.zeros(1, dtype=abi.SEG_DT)
@@ -721,7 +735,7 @@ class ScenarioHostScene:
         a["polyv"] = np.ascontiguousarray(vv, dtype=np.float32)
         a["ckpt_off"] = np.asarray(ckpt_off, np.int32)
         a["ckpt_xy"] = np.ascontiguousarray(np.concatenate(ckpts), dtype=np.float32)
-        a["track_meta"] = meta
+        a["track_meta"] = np.concatenate([b_["meta"] for b_ in built])
         run_off, run_list = [0], []
         for b_ in built:
             for r in b_["runs"]:
@@ -729,57 +743,44 @@ class ScenarioHostScene:
                 run_off.append(run_off[-1] + len(r))
         a["run_off"] = np.asarray(run_off, np.int32)
         a["runs"] = np.asarray(run_list if run_list else [(0, 0)], np.int32).reshape(-1, 2)
+        a["poly_aux"] = _poly_aux(a["poly_off"], a["segs"], a["polyv_off"], a["polyv"])
+        a["poly_ball"], a["poly_ball_off"] = _poly_balls(a["poly_off"], a["segs"])
         # buffers for routes cut at a later spawn frame (MdState.route_*): at most one piece per frame of the longest run, the
         # outline two vertices per metre of its path + the end caps
         self.route_seg_cap = int(max(b_["cut_frames"] for b_ in built))
         self.route_vert_cap = 2 * (int(math.ceil(max(b_["cut_metres"] for b_ in built))) + 3) + 4
-        a["poly_aux"] = _poly_aux(a["poly_off"], a["segs"], a["polyv_off"], a["polyv"])
-        a["poly_ball"], a["poly_ball_off"] = _poly_balls(a["poly_off"], a["segs"])
-        st = {}
-        st["shape0"], st["dyn0"], st["nav0"], st["pid0"], st["param"] = shape0, dyn0, nav0, pid0, param
-        st["route_nodes"] = np.full((N, abi.MD_ROUTE_LEN), -1, np.int32)
-        st["route_roads"] = np.full((N, abi.MD_ROUTE_LEN), -1, np.int32)
-        st["final_lane"] = np.zeros(N, np.int32)
-        st["idm_rand"] = np.zeros((N, abi.MD_IDM_RAND), np.int32)
-        for k in ("shape", "dyn", "nav", "pid"):
-            st[k] = st[k + "0"].copy()
-        st["action"] = np.zeros((N, 2), np.float32)
-        st["flags"] = np.zeros(N, np.uint32)
-        st["obs"] = np.zeros((E * A, self.obs_dim), np.float32)
-        st["reward"] = np.zeros(E * A, np.float32)
-        st["cost"] = np.zeros(E * A, np.float32)
-        st["step_info"] = np.zeros((E * A, 8), np.float32)
-        st["done_out"] = np.zeros((E * A, 4), np.uint8)
-        st["need_reset"] = np.ones(E, np.int32)
+
+    def _state(self, built):
+        cfg, E, cap, S = self.cfg, self.E, self.cap, len(built)
+        N = E * cap
+        nav0 = np.zeros(N, dtype=abi.NAV_DT)
+        nav0["lane"], nav0["target_lane"], nav0["road0"], nav0["road1"] = -1, -1, -1, -1
+        pid0 = np.zeros(N, dtype=abi.PID_DT)
+        pid0["target_speed"] = 40.0
+        rows = {k: np.concatenate([built[p][k] for p in self.env_scene]) for k in ("shape0", "dyn0", "param")}
+        rows.update(nav0=nav0, pid0=pid0, route_nodes=np.full((N, abi.MD_ROUTE_LEN), -1, np.int32),
+                    route_roads=np.full((N, abi.MD_ROUTE_LEN), -1, np.int32), final_lane=np.zeros(N, np.int32),
+                    idm_rand=np.zeros((N, abi.MD_IDM_RAND), np.int32))
+        st = step_state(E, self.A, cap, self.obs_dim, rows, self.env_scene if self.walk else None)
         st["next_agent_id"] = np.zeros(E, np.int32)     # ScenarioTrafficManager.idm_policy_count
-        if walk:
-            st["scene_of"] = np.asarray(env_scene, np.int32)
-            st["walk_ep"] = np.zeros(E, np.int32)
-            # the curriculum's per-env state (include/md_curriculum.h MdCurriculum); every env starts at level 0, no seed yet
-            Q, CW = self.curriculum[2], (S + 31) // 32
-            st["cur_level"] = np.zeros(E, np.int32)
-            st["cur_seed"] = np.full(E, -1, np.int32)
-            st["cur_q_len"] = np.zeros(E, np.int32)
-            st["cur_q_key"] = np.full((E, Q), -1, np.int32)
-            st["cur_q_success"] = np.zeros((E, Q), np.int32)
-            st["cur_q_route"] = np.zeros((E, Q), np.float32)
-            st["cur_cover"] = np.zeros((E, CW), np.uint32)
-            st["cur_cover_n"] = np.zeros(E, np.int32)
-            st["cur_rep_i"] = np.zeros((E, 2), np.int32)
-            st["cur_rep_f"] = np.zeros((E, 3), np.float64)
+        self.pool = None
+        if self.walk:   # the snapshot rows of every scene, at p * cap: what md_swap_draw copies into an env that moves on to scene p
+            self.pool = {k: np.concatenate([b_[k] for b_ in built]) for k in ("shape0", "dyn0", "param")}
+            self.pool.update(nav0=np.resize(nav0[:cap], S * cap), pid0=np.resize(pid0[:cap], S * cap))
+            st.update(curriculum_state(E, S, self.curriculum[2]))
         if cfg["reactive_traffic"]:
             st["route_n"] = np.zeros((N, 4), np.int32)
             st["route_segs"] = np.zeros((N, self.route_seg_cap), dtype=abi.SEG_DT)
             st["route_verts"] = np.zeros((N, self.route_vert_cap, 2), np.float32)
             st["route_aux"] = np.zeros((N, 8), np.float32)
         self.state = st
-        self.tracks = dict(shape=fshape, dyn=fdyn, seeds=list(self.seeds), cap=cap)
-        k = make_md_config(dict(cfg, traffic_mode="trigger"), E, A, cap, self.n_beams)
+
+    def _md_config(self):
+        from metadrive_ped_amd.engine import make_md_config
+        cfg = self.cfg
+        k = make_md_config(dict(cfg, traffic_mode="trigger"), self.layout, self.E, self.A, self.cap)
         k.traffic_mode = 4
-        k.n_side, k.n_lane_line = self.n_side, self.n_ll
-        k.obs_dim = self.obs_dim
-        k.track_len = T
-        k.scenario_length = T
+        k.track_len = k.scenario_length = self.T
         for name in ("on_lane_line_penalty", "crash_human_penalty", "steering_range_penalty", "heading_penalty",
                      "lateral_penalty", "max_lateral_dist", "crash_human_cost"):
             setattr(k, name, float(cfg[name]))
@@ -791,15 +792,6 @@ class ScenarioHostScene:
         k.ego_replay = int(cfg["agent_policy"] == "ReplayEgoCarPolicy")
         self.walk_params = walk_params(cfg)      # MdState.walk (all 0 without the walk)
         self.md_config = k
-        if walk:
-            dev_bytes = sum(v.nbytes for v in a.values()) + fshape.nbytes + fdyn.nbytes + sum(v.nbytes for v in self.pool.values())
-            print("walk_scenarios: scene pool of num_scenarios={} scenes (T={}, mover capacity {}): {:.1f} MiB on the device".format(
-                S, T, cap, dev_bytes / 2 ** 20))
-        self.side_beams = beam_table(self.n_side, np.pi / 2) if self.n_side else None
-        self.ll_beams = beam_table(self.n_ll, np.pi / 2) if self.n_ll else None
-
-    def clone_state(self):
-        return {k: v.copy() for k, v in self.state.items()}
 
 
 # --------------------------------------------------------------------------------------------------

@@ -27,7 +27,7 @@ import numpy as np
 from metadrive_ped_amd import abi
 from metadrive_ped_amd.mapgen.lanes import wrap_to_pi
 from metadrive_ped_amd.mapgen.pg import FirstBlock
-from metadrive_ped_amd.mapgen.tables import destination_for, respawn_lanes
+from metadrive_ped_amd.mapgen.tables import beam_table, destination_for, respawn_lanes
 from metadrive_ped_amd.pg_space import VEHICLE_TYPES, sample_parameters
 from metadrive_ped_amd.rng import Randomizable, get_np_random
 
@@ -421,3 +421,49 @@ class EnvScene:
         nv["route_len"] = len(ckpts)
         nv["target_lane"] = -1
         self.pid[slot]["target_speed"] = 30.0
+
+
+# -- what the two host scenes (engine.HostScene, scenario.ScenarioHostScene) share -----------------------------------------------
+def step_state(E, A, cap, obs_dim, rows, env_scene=None):
+    """The state dict of a batch before its first reset: `rows` (the snapshot rows shape0 | dyn0 | nav0 | pid0 and the per-slot
+    constants, E * cap slots each), the live copies of the snapshot and the per-step arrays md_step writes.  `env_scene`: the
+    scene each env of a walk starts at (MdState.scene_of, with walk_ep = 0)."""
+    N = E * cap
+    st = dict(rows)
+    for k in ("shape", "dyn", "nav", "pid"):
+        st[k] = st[k + "0"].copy()
+    st["action"] = np.zeros((N, 2), np.float32)
+    st["flags"] = np.zeros(N, np.uint32)
+    st["obs"] = np.zeros((E * A, obs_dim), np.float32)
+    st["reward"] = np.zeros(E * A, np.float32)
+    st["cost"] = np.zeros(E * A, np.float32)
+    st["step_info"] = np.zeros((E * A, 8), np.float32)
+    st["done_out"] = np.zeros((E * A, 4), np.uint8)          # (terminated, truncated, flag word lo / hi) straight from the kernel
+    st["need_reset"] = np.ones(E, np.int32)
+    if env_scene is not None:
+        st["scene_of"] = np.asarray(env_scene, np.int32)
+        st["walk_ep"] = np.zeros(E, np.int32)
+    return st
+
+
+class HostSceneBase:
+    """The small parts both host scenes have: a copy of the state for an oracle, the detector beam tables, and the MdWorld
+    scalars that are no device arrays."""
+    spawn = None
+    traffic_respawns = False
+
+    def clone_state(self):
+        return {k: v.copy() for k, v in self.state.items()}
+
+    def set_detector_beams(self):
+        """detector beam fans start 90 deg off the heading (SideDetector.__init__, distance_detector.py:197)"""
+        self.side_beams = beam_table(self.n_side, np.pi / 2) if self.n_side else None
+        self.ll_beams = beam_table(self.n_ll, np.pi / 2) if self.n_ll else None
+
+    def world_scalars(self):
+        """What engine.make_structs needs beside the world arrays, wherever those live: the host copies of the two offset tables
+        (MdWorld.max_lanes / max_roads come from them) and MdWorld.n_dest / n_vclass."""
+        a = self.world.arrays
+        return dict(lane_off_host=a["lane_off"], road_off_host=a["road_off"],
+                    n_dest_host=self.spawn["n_dest"] if self.spawn is not None else int(self.traffic_respawns),
+                    n_vclass_host=len(a["vclass"]) if "vclass" in a else 0)

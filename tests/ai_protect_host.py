@@ -1,11 +1,12 @@
 """ctypes binding of tests/ai_protect_host.c, the host build of include/md_ai_protect.h (compiled on first use into a temporary
-directory with gcc -O2 -ffp-contract=off).  TEST INFRASTRUCTURE."""
+directory by tests/hostlib.py).  TEST INFRASTRUCTURE."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
+
+import hostlib
+from hostlib import ptr as _p
 
 from metadrive_ped_amd import abi
 
@@ -14,29 +15,19 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "ai_protect.npz")
 # MdProtectIn
 IN_DT = np.dtype([(k, np.float32) for k in ("obs0", "obs1", "heading_diff", "speed_kmh", "max_speed_kmh", "lat_min", "lon_min")])
 TAKEOVER, TAKEOVER_START, TAKEOVER_END = abi.AIP_TAKEOVER, abi.AIP_TAKEOVER_START, abi.AIP_TAKEOVER_END
-_LIB = []
 
 
-def lib():
-    if _LIB:
-        return _LIB[0]
-    out = os.path.join(tempfile.mkdtemp(prefix="md_ai_protect_host_"), "libaiprotecthost.so")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-std=c11", "-fPIC", "-shared", "-fvisibility=hidden",
-                           "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "ai_protect_host.c"), "-o", out, "-lm"])
-    L = C.CDLL(out)
+def _declare(L):
     P = C.c_void_p
     L.hx_heading_diff.argtypes = [P, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float]
     L.hx_heading_diff.restype = C.c_float
     L.hx_windows.argtypes = [P, C.c_int, P, P]
     L.hx_act.argtypes = [C.c_int] + [P] * 8
     L.hx_batch.argtypes = [P] * 9 + [C.POINTER(abi.MdConfig), P, P, C.c_float] + [P] * 5
-    _LIB.append(L)
-    return L
 
 
-def _p(a):
-    assert a.flags["C_CONTIGUOUS"]
-    return a.ctypes.data
+def lib():
+    return hostlib.build("ai_protect_host", _declare)
 
 
 def lane_record(kind, **f):

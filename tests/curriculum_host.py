@@ -2,40 +2,25 @@
 directory) and the host model of md_curriculum on an oracle: CurriculumOracle steps the walk's oracle and runs the same state
 machine after every step, moving the envs itself when there is more than one level.  TEST INFRASTRUCTURE."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import hostlib
 import walk_host as wh
+from metadrive_ped_amd.scenario import curriculum_state as new_state      # noqa: F401  (the per-env arrays cur_* of a batch before its first reset)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = ("level", "seed", "q_len", "q_key", "q_success", "q_route", "cover", "cover_n", "rep_i", "rep_f")
-_LIB = []
 
 
-def lib():
-    if _LIB:
-        return _LIB[0]
-    out = os.path.join(tempfile.mkdtemp(prefix="md_cur_host_"), "libcurhost.so")
-    subprocess.check_call(["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall", "-ffp-contract=off",
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "curriculum_host.c"), "-o", out, "-lm"])
-    L = C.CDLL(out)
+def _declare(L):
     P = C.c_void_p
     L.hx_cur_after_step.argtypes = [P, P, C.c_double, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int]
     L.hx_cur_restart.argtypes = [P, P, C.c_double, C.c_int, C.c_int]
     L.hx_cur_next.argtypes = [P, C.c_int, P, C.c_int, C.c_int, P]
-    _LIB.append(L)
-    return L
 
 
-def new_state(E, n_scenes, eval_):
-    """the per-env arrays of a batch before its first reset (as ScenarioHostScene makes them, keys cur_*)"""
-    return dict(cur_level=np.zeros(E, np.int32), cur_seed=np.full(E, -1, np.int32), cur_q_len=np.zeros(E, np.int32),
-                cur_q_key=np.full((E, eval_), -1, np.int32), cur_q_success=np.zeros((E, eval_), np.int32),
-                cur_q_route=np.zeros((E, eval_), np.float32), cur_cover=np.zeros((E, (n_scenes + 31) // 32), np.uint32),
-                cur_cover_n=np.zeros(E, np.int32), cur_rep_i=np.zeros((E, 2), np.int32), cur_rep_f=np.zeros((E, 3), np.float64))
+def lib():
+    return hostlib.build("curriculum_host", _declare)
 
 
 class Curriculum:

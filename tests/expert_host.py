@@ -1,25 +1,19 @@
 """ctypes binding of tests/expert_host.c, the host build of include/md_expert.h (compiled on first use into a temporary
-directory with gcc -O2 -ffp-contract=off).  TEST INFRASTRUCTURE."""
+directory by tests/hostlib.py).  TEST INFRASTRUCTURE."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
+
+import hostlib
+from hostlib import lane_index, ptr as _p
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 WEIGHTS = os.path.join(GOLDEN, "expert_weights.npz")
-_LIB = []
 
 
-def lib():
-    if _LIB:
-        return _LIB[0]
-    out = os.path.join(tempfile.mkdtemp(prefix="md_expert_host_"), "libexperthost.so")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-std=c11", "-fPIC", "-shared", "-fvisibility=hidden",
-                           "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "expert_host.c"), "-o", out, "-lm"])
-    L = C.CDLL(out)
+def _declare(L):
     P = C.c_void_p
     L.hx_expert.argtypes = [P, P, C.c_int, P, P]
     L.hx_mlp.argtypes = [P, P, C.c_int, P]
@@ -28,13 +22,10 @@ def lib():
     L.hx_exp.argtypes = [P, C.c_int, P]
     L.hx_widx.argtypes = [C.c_int, C.c_int, C.c_int]
     L.hx_widx.restype = C.c_int
-    _LIB.append(L)
-    return L
 
 
-def _p(a):
-    assert a.flags["C_CONTIGUOUS"]
-    return a.ctypes.data
+def lib():
+    return hostlib.build("expert_host", _declare)
 
 
 def packed_weights(path=WEIGHTS):
@@ -91,16 +82,6 @@ def perf_config(name, lane, **extra):
     cfg.update(PERF_CONFIGS[name])
     cfg.update(extra)
     return make_config(cfg)
-
-
-def lane_index(host, state):
-    """lane_index[-1] of the agent (its lane's index inside the road), -1 off every lane."""
-    lane = int(state["nav"]["lane"][0])
-    if lane < 0:
-        return -1
-    a = host.world.arrays
-    m = int(a["env_map"][0])
-    return int(a["lanes"][int(a["lane_off"][m]) + lane]["idx"])
 
 
 def oracle_episode(w, name, lane, max_steps=3000, record=None):

@@ -1,26 +1,17 @@
 """ctypes binding of tests/lane_change_host.c, the host build of include/md_lane_change.h (compiled on first use into a
-temporary directory with gcc -O2 -ffp-contract=off), and the CPU oracle driven by it: LaneChangePolicy's reference run
+temporary directory by tests/hostlib.py), and the CPU oracle driven by it: LaneChangePolicy's reference run
 without a GPU.  TEST INFRASTRUCTURE."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = []
+import hostlib
+from hostlib import lane_index, ptr as _p      # noqa: F401  (lane_index: the tests read it from here)
+
 PID_ERRS = ("hp", "hi", "hd", "lp", "li", "ld")     # the lane-change PIDs' state in an MdPid row
 
 
-def lib():
-    if _LIB:
-        return _LIB[0]
-    out = os.path.join(tempfile.mkdtemp(prefix="md_lane_change_host_"), "liblanechangehost.so")
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-std=c11", "-fPIC", "-shared", "-fvisibility=hidden",
-                           "-Wall", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "lane_change_host.c"), "-o", out,
-                           "-lm"])
-    L = C.CDLL(out)
+def _declare(L):
     P, i, f = C.c_void_p, C.c_int, C.c_float
     L.hx_target.argtypes = [P, P, i, i, i]
     L.hx_target.restype = i
@@ -28,13 +19,10 @@ def lib():
     L.hx_steer.restype = f
     L.hx_lane_change_batch.argtypes = [P] * 13 + [i, i, i, i]
     L.hx_lane_change_batch.restype = None
-    _LIB.append(L)
-    return L
 
 
-def _p(a):
-    assert a.flags["C_CONTIGUOUS"]
-    return a.ctypes.data
+def lib():
+    return hostlib.build("lane_change_host", _declare)
 
 
 def target(lanes, roads, cur, road0, direction):
@@ -92,17 +80,6 @@ class LaneChangeOracle:
         """slot indices of the agents in the global [E * cap] arrays"""
         h = self.host
         return (np.arange(h.E)[:, None] * h.cap + np.arange(h.A)[None, :]).reshape(-1)
-
-
-def lane_index(host, state, e=0, a=0):
-    """current_lane.index[-1] of agent a of env e (MdLane.idx of MdNav.lane), -1 without a lane"""
-    j = e * host.cap + a
-    lane = int(state["nav"]["lane"][j])
-    if lane < 0:
-        return -1
-    arr = host.world.arrays
-    m = int(arr["env_map"][e])
-    return int(arr["lanes"][int(arr["lane_off"][m]) + lane]["idx"])
 
 
 # the reference's known answer (tests/test_policy/test_lane_change_policy.py::test_lane_change)

@@ -3,6 +3,7 @@
 md_walk_scene of include/md_scenario.h through tests/walk_host.c.  TEST INFRASTRUCTURE."""
 import numpy as np
 
+import hostlib
 import lane_change_host as lh
 import oracle_binding as ob
 import walk_host as wh
@@ -67,7 +68,7 @@ class PgWalkLaneChangeOracle(lh.LaneChangeOracle):
         h, st = self.host, self.o.state
         a = h.world.arrays
         act = np.ascontiguousarray(np.asarray(decoded, np.float32).reshape(h.E, h.A, 2)).copy()
-        P = lh._p
+        P = hostlib.ptr
         lh.lib().hx_lane_change_batch(P(a["lanes"]), P(a["lane_off"]), P(a["roads"]), P(a["road_off"]), P(self.o.env_map),
                                       P(st["shape"]), P(st["dyn"]), P(st["nav"]), P(st["flags"]), P(st["need_reset"]), P(self.pid),
                                       P(st["pid0"]), P(act), h.E, h.cap, h.A, 0)

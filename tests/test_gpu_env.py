@@ -182,6 +182,34 @@ def test_discrete_actions_and_lidar_noise():
     assert np.array_equal(od[:, rest], oc[:, rest])                      # nothing else is touched (lidar noise is off)
 
 
+def test_lidar_noise_stream_is_pinned():
+    """The noise of the clouds, bit for bit: the noise-free observation of a twin engine, then per cloud normal_ and uniform_
+    drawn from a device generator seeded start_seed + env_seed_offset -- the reset observation takes the stream's first draws,
+    each step the next ones."""
+    import torch
+    from metadrive_ped_amd.config import make_config
+    from metadrive_ped_amd.engine import BatchedEngine
+    E, B, g, p = 4, 16, 0.05, 0.1
+    base = dict(num_envs=E, num_scenarios=E, start_seed=5, env_seed_offset=2, build_workers=1)
+    clean = BatchedEngine(make_config(dict(base, vehicle_config=dict(lidar=dict(num_lasers=B, distance=50)))))
+    noisy = BatchedEngine(make_config(dict(base, vehicle_config=dict(lidar=dict(num_lasers=B, distance=50, gaussian_noise=g,
+                                                                                    dropout_prob=p)))))
+    gen = torch.Generator(device=clean.device)
+    gen.manual_seed(5 + 2)
+    off = clean.host.layout.lidar_off
+    actions = torch.from_numpy(scripted_actions(E, 1, 0)).to(clean.device)
+    for step in (False, True):
+        for eng in (clean, noisy):
+            eng.step(actions) if step else eng.reset()
+        want = clean.obs.clone()
+        cloud = want[..., off:off + B]
+        noise = torch.empty_like(cloud).normal_(0.0, g, generator=gen)
+        cloud.copy_((cloud + noise).clamp_(0.0, 1.0))
+        cloud.masked_fill_(torch.empty_like(cloud).uniform_(0.0, 1.0, generator=gen) < p, 0.0)
+        assert torch.equal(noisy.obs, want), "step" if step else "reset"
+    assert not torch.equal(noisy.obs, clean.obs)
+
+
 def test_record_then_replay_traffic():
     """env.start_recording / stop_recording / load_tracks + traffic_mode='replay': replaying a recorded rollout with
     the same agent actions gives the same observations bit for bit; the replay path equals the oracle's."""

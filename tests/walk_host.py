@@ -1,31 +1,23 @@
-"""ctypes binding of tests/walk_host.c (md_walk_scene of include/md_scenario.h, compiled on first use into a temporary directory)
+"""ctypes binding of tests/walk_host.c (md_walk_scene of include/md_scenario.h, compiled by tests/hostlib.py)
 and the host-side form of md_swap_draw's scenario walk, applied to an oracle's arrays.  TEST INFRASTRUCTURE."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import hostlib
 import oracle_binding as ob
 from metadrive_ped_amd import abi
 from metadrive_ped_amd.scenario import walk_params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = []
+
+
+def _declare(L):
+    P = C.c_void_p
+    L.hx_walk_scene.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, P, P, C.c_int, P]
 
 
 def lib():
-    if _LIB:
-        return _LIB[0]
-    out = os.path.join(tempfile.mkdtemp(prefix="md_walk_host_"), "libwalkhost.so")
-    subprocess.check_call(["gcc", "-O2", "-std=c11", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall",
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "walk_host.c"), "-o", out, "-lm"])
-    L = C.CDLL(out)
-    P = C.c_void_p
-    L.hx_walk_scene.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, P, P, C.c_int, P]
-    _LIB.append(L)
-    return L
+    return hostlib.build("walk_host", _declare)
 
 
 def walk_scene(n_scenes, walk, stride, offset, seed, e, ep):
