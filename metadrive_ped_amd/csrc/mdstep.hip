@@ -61,7 +61,8 @@ thread_local char g_err[256] = "ok";
 __device__ unsigned long long* g_stamp_buf = nullptr;
 __device__ const int* g_env_order = nullptr;
 // slots 0..11: shader-cycle stamps; 12 / 13: s_memrealtime (100 MHz, one time base for the whole chip) at the first / last
-// stamp; 14: HW_ID | XCC_ID << 32 (which CU the workgroup ran on) -- tools/timeline_probe.py rebuilds the occupancy timeline
+// stamp; 14: HW_ID | XCC_ID << 32 (which CU the workgroup ran on) -- tools/timeline_probe.py rebuilds the occupancy timeline;
+// 15 (fine slot -1) / fine slot 14: start / end of the trigger's search (trigger_search_wave)
 #define MD_STAMP_AT(i)                                                                         \
     do {                                                                                       \
         if (threadIdx.x == 0 && g_stamp_buf) {                                                 \
@@ -1669,10 +1670,21 @@ __device__ __forceinline__ void observe_agent_wave(const MdLane* lanes, const Md
 }
 
 // ------------------------------------------------------------------------------------------------
-// Traffic trigger (wave 0) -- PGTrafficManager.before_step, manager/traffic_manager.py:80-88
+// Traffic trigger (one wave) -- PGTrafficManager.before_step, manager/traffic_manager.py:80-88
+// In two halves: the lean kernel runs the search beside the integration and only the fire in its traffic stage.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void trigger_env(const MdLane* lanes, const MdState& s, const MdConfig& c, int lane_id) {
+// A/B builds: -DMD_TRIGGER_EARLY=0 compiles the lean kernel with both halves in its traffic stage (trigger_env)
+#ifndef MD_TRIGGER_EARLY
+#define MD_TRIGGER_EARLY 1
+#endif
+// The search: the lowest pending trigger_order of the env and the trigger road of its block (0x7fffffff: nothing is pending).
+// Reads only the PENDING / ALIVE bits and trigger_order / trigger_road of slots that do not drive: nothing a step computes.
+constexpr int kNoTrigger = 0x7fffffff;
+__device__ __forceinline__ void trigger_search_wave(const MdState& s, const MdConfig& c, int lane_id, int* min_order_out, int* trig_road_out) {
     const int base = 0;  // env-local view
+    MD_FINE_STAMP(lane_id == 0, -1);
+    *min_order_out = kNoTrigger;
+    *trig_road_out = -1;
     int my_min = 0x7fffffff;
     for (int j = lane_id; j < c.cap; j += 64) {
         const int f = s.shape[base + j].flags;
@@ -1691,7 +1703,15 @@ __device__ __forceinline__ void trigger_env(const MdLane* lanes, const MdState& 
             my_slot = j < my_slot ? j : my_slot;
     }
     const int first_slot = wave_min_i(my_slot, my_slot != 0x7fffffff, 0x7fffffff);
-    const int trig_road = s.nav[base + first_slot].trigger_road;
+    *min_order_out = min_order;
+    *trig_road_out = s.nav[base + first_slot].trigger_road;
+    MD_FINE_STAMP(lane_id == 0, 14);
+}
+
+// The fire: an agent on the trigger road wakes the block's vehicles (clears their PENDING bits)
+__device__ __forceinline__ void trigger_fire_wave(const MdLane* lanes, const MdState& s, const MdConfig& c, int lane_id, int min_order, int trig_road) {
+    const int base = 0;  // env-local view
+    if (min_order == kNoTrigger) return;
     bool fire = false;
     for (int a = lane_id; a < c.agents_per_env; a += 64) {
         if (!md_drives(s.shape[base + a].flags)) continue;
@@ -1704,6 +1724,12 @@ __device__ __forceinline__ void trigger_env(const MdLane* lanes, const MdState& 
         if ((f & MD_F_PENDING) && (f & MD_F_ALIVE) && s.nav[base + j].trigger_order == min_order)
             s.shape[base + j].flags = f & ~MD_F_PENDING;
     }
+}
+
+__device__ __forceinline__ void trigger_env(const MdLane* lanes, const MdState& s, const MdConfig& c, int lane_id) {
+    int min_order, trig_road;
+    trigger_search_wave(s, c, lane_id, &min_order, &trig_road);
+    trigger_fire_wave(lanes, s, c, lane_id, min_order, trig_road);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2169,6 +2195,23 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     if ((MULTI || PH == PH_ALL) && tid == 0) l_tk[0] = l_tk[1] = l_tk[2] = 0;
     __syncthreads();
     MD_STAMP_AT(1);
+    // Lean kernel: the search half of the next step's trigger runs here, on the last wave, which owns no slot of the integrate
+    // stage below.  It reads PENDING / ALIVE and trigger_order / trigger_road of waiting slots only, which no stage before the
+    // traffic stage writes (the reset step's too: the snapshot is staged by now).  The same wave fires, behind the locate
+    // stage's barrier; nothing stays in registers in between.
+    constexpr bool kTriggerEarly = MD_TRIGGER_EARLY && PH == PH_ALL && kIdmKeys && kWaves > 1;
+    // its two words (min order, trigger road): words 46 / 47 of the last wave's own scratch (env_lds: 48 per wave), which the observe
+    // tasks (45 floats) never touch and the wave's IDM (ints 0 .. 35) uses only after the fire has read them
+    constexpr int kTrigWord = (kWaves - 1) * 48 + 46;
+    if (kTriggerEarly && wave == kWaves - 1) {
+        int min_order, trig_road;
+        trigger_search_wave(s, c, lane, &min_order, &trig_road);
+        if (lane == 0) {
+            int* l_trig = reinterpret_cast<int*>(smem + L.scratch) + kTrigWord;
+            l_trig[0] = min_order;
+            l_trig[1] = trig_road;
+        }
+    }
 
     if ((PH & PH_LIFECYCLE) && MULTI && !just_reset) {
         lifecycle_block(w, s, c, w.env_map[e], tid, kBlock, reinterpret_cast<int*>(l_onlane));
@@ -2288,7 +2331,12 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         }
         // next step's trigger: reads the agents' final lanes and the PENDING slots, which the removal above
         // (slots that drove in this step only) does not touch
-        if (plan_ahead && wave == kWaves - 1) trigger_env(lanes, s, c, lane);
+        if (plan_ahead && wave == kWaves - 1) {
+            if (kTriggerEarly) {   // searched beside the integration
+                const int* l_trig = reinterpret_cast<const int*>(smem + L.scratch) + kTrigWord;
+                trigger_fire_wave(lanes, s, c, lane, __builtin_amdgcn_readfirstlane(l_trig[0]), __builtin_amdgcn_readfirstlane(l_trig[1]));
+            } else trigger_env(lanes, s, c, lane);
+        }
         __syncthreads();
         if (RESPAWN) {  // respawn / hybrid: the removed vehicle re-enters on a respawn lane (rare; serial)
             if (tid == 0) md_traffic_respawn_env(&w, lanes, &s, &c, w.env_map[e]);

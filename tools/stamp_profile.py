@@ -113,6 +113,22 @@ def main():
     if len(lo):
         print("observe(agent) fine: context %.0f | nine tasks %.0f | combine + stores %.0f (p50 cycles)" % (
             np.median(lo[:, 9] - lo[:, 8]), np.median(lo[:, 10] - lo[:, 9]), np.median(lo[:, 11] - lo[:, 10])))
+    # the trigger's search (trigger_search_wave): stamp slot 15 at its start, fine slot 14 at its end.  Beside the integration it
+    # starts at stamp 1 and must end before stamp 4 (the integrate stage's end); in a -DMD_TRIGGER_EARLY=0 build it starts at stamp 6
+    # and is part of the traffic stage.
+    ts0, ts1 = raw[:, 15].astype(np.int64), fine[:, 14]
+    ok = (ts0 > 0) & (ts1 > ts0)
+    if ok.any():
+        dur, beside = (ts1 - ts0)[ok], ts0[ok] < st[ok, 4]
+        print("trigger search over %d envs: %.0f p50  %.0f p99 cycles; beside the integration in %d envs" % (
+            ok.sum(), np.median(dur), np.percentile(dur, 99), beside.sum()))
+        if beside.any():
+            integ, slack = (st[:, 4] - st[:, 1])[ok][beside], (st[:, 4] - ts1)[ok][beside]
+            print("  stamps 1 -> 4 (integrate) p50 %.0f  p99 %.0f; the search ends %.0f (p50) / %.0f (p1) cycles before stamp 4, after it in %d envs" % (
+                np.median(integ), np.percentile(integ, 99), np.median(slack), np.percentile(slack, 1), (slack < 0).sum()))
+        else:
+            print("  it starts %.0f (p50) cycles after stamp 6 and ends %.0f (p50) before stamp 7" % (
+                np.median((ts0 - st[:, 6])[ok]), np.median((st[:, 7] - ts1)[ok])))
     flags = eng.shape_f.view(torch.int32)[..., 6]
     drv = (((flags & 0x10) != 0) & ((flags & 0x40) == 0) & ((flags & 0xF) == 1)).sum(dim=1).cpu().numpy()
     print("driving vehicles/env: mean %.2f max %d" % (drv.mean(), drv.max()))
