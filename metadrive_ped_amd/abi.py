@@ -110,6 +110,26 @@ class MdCurriculum(C.Structure):
 
 CURRICULUM_FIELDS = [f for f, t in MdCurriculum._fields_ if t is P]
 
+# include/md_topdown.h: the limits, and md_topdown's argument block
+MD_TD_MAX_RES, MD_TD_MAX_RING = 128, 64
+
+
+class MdTopDown(C.Structure):
+    """include/md_topdown.h: the top-down observation's sizes, output and engine-owned history arrays"""
+    _fields_ = [("struct_size", C.c_int32), ("resolution", C.c_int32), ("distance", C.c_float), ("frame_stack", C.c_int32),
+                ("frame_skip", C.c_int32), ("post_stack", C.c_int32), ("norm_pixel", C.c_int32), ("reserved", C.c_int32),
+                ("out", P), ("ring_traffic", P), ("ring_pos", P), ("cursor", P)]
+
+
+def td_row_words(R):
+    """MD_TD_ROW_WORDS: 32-bit words per row of a 1-bit frame"""
+    return (R + 31) >> 5
+
+
+def td_ring_len(stack, skip):
+    """md_td_ring_len: the length of stack_traffic_flow / stack_past_pos"""
+    return (stack - 1) * skip + 1
+
 
 class MdState(C.Structure):
     _fields_ = [
@@ -203,6 +223,8 @@ EXPERT_SENSE_ENTRY_POINTS = {"md_expert_sense": (_i, [_W, _S, _K, P, P, P, P, P,
 AIP_TAKEOVER, AIP_TAKEOVER_START, AIP_TAKEOVER_END = 1, 2, 4      # md_ai_protect's flag byte
 # include/md_curriculum.h
 CURRICULUM_ENTRY_POINTS = {"md_curriculum": (_i, [_S, _S, _K, C.POINTER(MdCurriculum), P, _i, P])}
+# include/md_topdown.h: (w, s, c, td, stream)
+TOPDOWN_ENTRY_POINTS = {"md_topdown": (_i, [_W, _S, _K, C.POINTER(MdTopDown), P])}
 # declared in no header: the hooks of diagnostic (-DMD_STAMP) builds, and md_localize through the lean step's road-first path
 # (the parity tests call it; a -DMD_LOC_ROAD_FIRST=0 build runs the plain walk under that name)
 OPTIONAL_ENTRY_POINTS = {"md_debug_set_stamp_buffer": (_i, [P]), "md_debug_set_env_order": (_i, [P]),

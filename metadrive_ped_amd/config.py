@@ -139,6 +139,12 @@ BATCH_DEFAULT_CONFIG = dict(
                             # env's own obs row (md_expert), which only the 259-dim default vehicle config allows
 )
 
+# The top-down observation envs' own keys (envs/top_down_env.py:12-21,54-61 of the reference): they exist for BatchedTopDownMetaDrive /
+# BatchedTopDownMetaDriveEnvV2 only (make_config(top_down=True)); any other class given one raises KeyError, as the reference's would.
+# norm_pixel is on the cosmetic list below for every other class; for these two it decides the image's dtype.
+TOP_DOWN_DEFAULT_CONFIG = dict(frame_skip=5, frame_stack=3, post_stack=5, norm_pixel=True, resolution_size=84, distance=30)
+TOP_DOWN_MAX_RES, TOP_DOWN_MAX_RING = 128, 64      # MD_TD_MAX_RES / MD_TD_MAX_RING (include/md_topdown.h)
+
 # Keys of the reference's BASE_DEFAULT_CONFIG (envs/base_env.py:32-266) that only concern rendering, cameras, the GUI,
 # debugging displays or asset handling: nothing on this path reads them, so any value is accepted and kept.
 COSMETIC_DEFAULT_CONFIG = dict(
@@ -234,11 +240,33 @@ def _obs_row_expert_problem(cfg, why):
     return None
 
 
-def make_config(user=None):
+def _check_top_down(cfg):
+    """The top-down keys' types and the limits of include/md_topdown.h, refused by name"""
+    for k in ("frame_skip", "frame_stack", "post_stack", "resolution_size"):
+        if isinstance(cfg[k], bool) or not isinstance(cfg[k], int) or cfg[k] < 1:
+            raise ValueError("config['{}']={!r}: an int >= 1".format(k, cfg[k]))
+    if not isinstance(cfg["norm_pixel"], bool):
+        raise TypeError("Attempting to update 'norm_pixel' with type {}, expected bool".format(type(cfg["norm_pixel"]).__name__))
+    if isinstance(cfg["distance"], bool) or not cfg["distance"] > 0:
+        raise ValueError("config['distance']={!r}: a positive number of metres".format(cfg["distance"]))
+    if cfg["resolution_size"] > TOP_DOWN_MAX_RES:
+        raise ValueError("config['resolution_size']={} is beyond the top-down kernel's limit {}".format(cfg["resolution_size"], TOP_DOWN_MAX_RES))
+    for k in ("frame_stack", "post_stack"):
+        if (cfg[k] - 1) * cfg["frame_skip"] + 1 > TOP_DOWN_MAX_RING:
+            raise ValueError("({0} - 1) * frame_skip + 1 = {1} is beyond the top-down kernel's ring limit {2}".format(
+                k, (cfg[k] - 1) * cfg["frame_skip"] + 1, TOP_DOWN_MAX_RING))
+    if cfg["is_multi_agent"] or cfg["num_agents"] != 1:
+        raise NotImplementedError("Don't support multi-agent top-down observation yet! (top_down_obs_multi_channel.py:151)")
+
+
+def make_config(user=None, top_down=False):
+    """top_down: the config of a top-down observation env (TOP_DOWN_DEFAULT_CONFIG's keys exist)"""
     cfg = copy.deepcopy(BASE_DEFAULT_CONFIG)
     cfg.update(copy.deepcopy(METADRIVE_DEFAULT_CONFIG))
     cfg.update(copy.deepcopy(BATCH_DEFAULT_CONFIG))
     cfg.update(copy.deepcopy(COSMETIC_DEFAULT_CONFIG))
+    if top_down:
+        cfg.update(copy.deepcopy(TOP_DOWN_DEFAULT_CONFIG))
     cfg["vehicle_config"].update(copy.deepcopy(COSMETIC_VEHICLE_CONFIG))
     for k, off in _OFF_ONLY.items():
         cfg.setdefault(k, off)
@@ -248,6 +276,8 @@ def make_config(user=None):
     if isinstance(user.get("sensors"), dict) and not user["sensors"]:
         user["sensors"] = None                                  # an empty sensor table is the default
     _merge(cfg, user)
+    if top_down:
+        _check_top_down(cfg)
     # agent_policy: the reference takes a policy CLASS; here its name (or a class of that name)
     pol = cfg["agent_policy"]
     pol = pol if isinstance(pol, str) else getattr(pol, "__name__", repr(pol))

@@ -575,10 +575,47 @@ class BatchedEngine:
         self.dyn_f = sd["dyn"].view(torch.float32).view(self.E, self.cap, 8)
         self.nav_i = sd["nav"].view(torch.int32).view(self.E, self.cap, 16)
         self.agent_id = sd["agent_id"].view(torch.int32).view(self.E, self.cap) if "agent_id" in sd else None
+        self._topdown_setup()
         if getattr(h, "tracks", None) is not None:     # scenario mode: the scenes' recorded frames come with the host scene
             tr = h.tracks
             self.set_tracks(dict(shape=torch.from_numpy(np.ascontiguousarray(tr["shape"]).view(np.uint8).reshape(tr["shape"].shape[0], -1)),
                                  dyn=torch.from_numpy(np.ascontiguousarray(tr["dyn"])), seeds=tr["seeds"], cap=tr["cap"]))
+
+    def _topdown_setup(self):
+        """The top-down observation envs (config keys resolution_size ...; include/md_topdown.h): the image tensor
+        [E, R, R, 2 + frame_stack] and the engine-owned history -- the 1-bit traffic frames, the past positions and the cursors --
+        md_topdown's arguments, not MdState's.  self.topdown is None for every other env."""
+        torch, cfg = self.torch, self.cfg
+        self._td = self.topdown = self.topdown_dev = None
+        if "resolution_size" not in cfg:
+            return
+        if cfg.get("scenario_mode") or self.A != 1:
+            raise NotImplementedError("the top-down observation is built for the single-agent PG envs")
+        R, stack, skip = int(cfg["resolution_size"]), int(cfg["frame_stack"]), int(cfg["frame_skip"])
+        norm = bool(cfg["norm_pixel"])
+        Lt, Lp = abi.td_ring_len(stack, skip), abi.td_ring_len(int(cfg["post_stack"]), skip)
+        self.topdown = torch.zeros((self.E, R, R, 2 + stack), dtype=torch.float32 if norm else torch.uint8, device=self.device)
+        self.topdown_dev = dict(ring_traffic=torch.zeros((self.E, Lt, R, abi.td_row_words(R)), dtype=torch.int32, device=self.device),
+                                ring_pos=torch.zeros((self.E, Lp, 2), dtype=torch.float32, device=self.device),
+                                cursor=torch.zeros((self.E, 4), dtype=torch.int32, device=self.device))
+        td = abi.MdTopDown()
+        td.struct_size, td.resolution, td.distance = C.sizeof(abi.MdTopDown), R, float(cfg["distance"])
+        td.frame_stack, td.frame_skip, td.post_stack, td.norm_pixel = stack, skip, int(cfg["post_stack"]), int(norm)
+        td.out = self.topdown.data_ptr()
+        for k, t in self.topdown_dev.items():
+            setattr(td, k, t.data_ptr())
+        self._td = td
+
+    def topdown_history(self):
+        """The top-down history arrays as host numpy copies: ring_traffic, ring_pos, cursor (the tests compare them; the top-down
+        envs' get_state() carries them and set_state() puts them back through upload_topdown_history)"""
+        return {k: t.cpu().numpy().copy() for k, t in self.topdown_dev.items()}
+
+    def upload_topdown_history(self, arrays):
+        """The arrays of topdown_history(), back onto the device (env.set_state)"""
+        for k, v in arrays.items():
+            t = self.topdown_dev[k]
+            t.copy_(self.torch.from_numpy(np.ascontiguousarray(v)).to(t.dtype).view_as(t))
 
     def _pack_step_outputs(self):
         """obs | reward | done_out (terminated, truncated, step flags) of this rank in ONE allocation, in that order, each part
@@ -664,6 +701,8 @@ class BatchedEngine:
                 self.line_detector(self._ll_beams, L.n_ll, float(vc["lane_line_detector"]["distance"]), self.LANE_LINE_MASK, obs, L.obs_dim,
                                    L.ll_off)
         self._lidar_noise()
+        if self._td is not None:         # the top-down image of the state this step left, on the map of the episode it belongs to
+            self._launch("md_topdown", C.byref(self._td))
         # Only now, with the step's observation complete, do the envs whose episode just ended move on: the swap of a walk rewrites
         # MdWorld.env_map, and the detector launches above trace the map of the episode that ended
         if self._cur is not None:        # the scenario walk: the curriculum's step, and the envs whose episode just ended move on

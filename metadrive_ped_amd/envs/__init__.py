@@ -4,3 +4,5 @@ from metadrive_ped_amd.envs.marl_env import (BatchedMultiAgentBidirectionEnv, Ba
                                             BatchedMultiAgentTinyInter, BatchedMultiAgentRacingEnv,
                                              BatchedMultiAgentMetaDrive, BatchedMultiAgentParkingLotEnv,
                                              BatchedMultiAgentRoundaboutEnv, BatchedMultiAgentTollgateEnv)
+from metadrive_ped_amd.envs.top_down_env import (BatchedTopDownMetaDrive, BatchedTopDownMetaDriveEnvV2,  # noqa: F401
+                                                 BatchedTopDownSingleFrameMetaDriveEnv)

@@ -81,16 +81,19 @@ def discrete_to_continuous(torch, cfg, actions, lead_shape, device):
 class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
     metadata = {"render_modes": []}
     DEFAULTS = {}         # a subclass's own defaults, under the user's config (top-level keys)
+    TOP_DOWN = False      # the top-down observation envs: their own config keys exist (config.TOP_DOWN_DEFAULT_CONFIG)
     FLAG_INFO = SINGLE_AGENT_FLAG_INFO + (("on_lane", abi.FL_ON_LANE), ("on_broken_line", abi.FL_ON_BROKEN))
     RENDER_MESSAGE = BatchedEnvBase.RENDER_MESSAGE + (": export_scenarios() gives the episode in the reference's scenario format "
-                                                      "for its own top-down renderer")
+                                                      "for its own top-down renderer; "
+                                                      "BatchedTopDownMetaDrive / BatchedTopDownMetaDriveEnvV2 return the bird's-eye "
+                                                      "observation as an image tensor")
 
     @classmethod
     def default_config(cls):
-        return make_config(copy.deepcopy(cls.DEFAULTS))
+        return make_config(copy.deepcopy(cls.DEFAULTS), top_down=cls.TOP_DOWN)
 
     def __init__(self, config=None):
-        super().__init__(make_config(dict(copy.deepcopy(self.DEFAULTS), **(config or {}))))
+        super().__init__(make_config(dict(copy.deepcopy(self.DEFAULTS), **(config or {})), top_down=self.TOP_DOWN))
         if self.config["num_agents"] != 1 or self.config["is_multi_agent"]:
             raise NotImplementedError("BatchedMetaDriveEnv is the single-agent env; multi-agent envs are separate classes")
         if self.config["random_traffic"] and self.config["auto_reset"] and int(self.config.get("traffic_draws", 1)) <= 1:
