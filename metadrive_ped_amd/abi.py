@@ -130,6 +130,17 @@ def td_ring_len(stack, skip):
     """md_td_ring_len: the length of stack_traffic_flow / stack_past_pos"""
     return (stack - 1) * skip + 1
 
+# include/md_render.h: the limits, and md_render's argument block
+MD_RD_MAX_SIZE, MD_RD_MAX_STACK, MD_RD_TILE = 1024, 32, 64
+
+
+class MdRender(C.Structure):
+    """include/md_render.h: the top-down renderer's window, options, rendered envs, output and engine-owned history arrays"""
+    _fields_ = [("struct_size", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("scaling", C.c_float),
+                ("num_stack", C.c_int32), ("history_smooth", C.c_int32), ("track_agent", C.c_int32), ("heading_up", C.c_int32),
+                ("draw_contour", C.c_int32), ("fixed_camera", C.c_int32), ("cam_x", C.c_float), ("cam_y", C.c_float),
+                ("n_render", C.c_int32), ("reserved", C.c_int32), ("env_ids", P), ("out", P), ("ring", P), ("cursor", P)]
+
 
 class MdState(C.Structure):
     _fields_ = [
@@ -225,6 +236,8 @@ AIP_TAKEOVER, AIP_TAKEOVER_START, AIP_TAKEOVER_END = 1, 2, 4      # md_ai_protec
 CURRICULUM_ENTRY_POINTS = {"md_curriculum": (_i, [_S, _S, _K, C.POINTER(MdCurriculum), P, _i, P])}
 # include/md_topdown.h: (w, s, c, td, stream)
 TOPDOWN_ENTRY_POINTS = {"md_topdown": (_i, [_W, _S, _K, C.POINTER(MdTopDown), P])}
+# include/md_render.h: (w, s, c, r, stream)
+RENDER_ENTRY_POINTS = {"md_render": (_i, [_W, _S, _K, C.POINTER(MdRender), P])}
 # declared in no header: the hooks of diagnostic (-DMD_STAMP) builds, and md_localize through the lean step's road-first path
 # (the parity tests call it; a -DMD_LOC_ROAD_FIRST=0 build runs the plain walk under that name)
 OPTIONAL_ENTRY_POINTS = {"md_debug_set_stamp_buffer": (_i, [P]), "md_debug_set_env_order": (_i, [P]),

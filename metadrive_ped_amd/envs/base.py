@@ -27,6 +27,7 @@ class BatchedEnvBase:
         self.num_envs = config["num_envs"]
         self.observation_space = Box(-0.0, 1.0, (ObsLayout(self.config, scenario=scenario).obs_dim, ), np.float32)
         self.engine = None
+        self.top_down_renderer = None      # the BatchedTopDownRenderer of render(mode="topdown"), None before the first call
 
     # -- lifecycle ----------------------------------------------------------------------------
     def _build_host(self):
@@ -41,12 +42,47 @@ class BatchedEnvBase:
 
     def close(self):
         self.engine = None
+        self.top_down_renderer = None
 
     def seed(self, seed=None):
         """BaseEnv.seed: scenario seeds are set through reset(seed=...); kept as a no-op like the gymnasium API."""
 
-    def render(self, *args, **kwargs):
-        raise NotImplementedError(self.RENDER_MESSAGE)
+    def render(self, text=None, mode=None, envs=None, screen_size=(512, 512), scaling=5, num_stack=15, history_smooth=0, camera_position=None,
+               target_vehicle_heading_up=False, draw_contour=True, track_agent=0, screen_record=False, window=False, film_size=None, **refused):
+        """BaseEnv.render (envs/base_env.py:482-492) for the modes "top_down" | "topdown" | "bev" | "birdview": the reference's
+        TopDownRenderer, rasterised on the device (include/md_render.h) -> uint8 device tensor [len(envs), H, W, 3], RGB, of the envs
+        `envs` (None: env 0); screen_size is (width, height), `scaling` pixels per metre.  The tensor is rewritten by the next call.
+        The first call after reset() fixes the options, as the reference's first call of an episode does; a later call with other
+        options raises ValueError, and reset() drops the renderer (env.top_down_renderer) with its history.  The history of an env
+        that auto-resets empties itself; a caller that renders less often than every step can miss a reset, and in a walking batch
+        the one frame between an episode's end and its reset step is drawn on the next scene's map (the swap happens inside step()).
+        `film_size` is accepted and has nothing to act on: there is no film canvas, the window is sampled from the geometry itself.
+        Not built, refused by name: window=True, a non-empty `text`, semantic_map, draw_target_vehicle_trajectory, show_agent_name.
+        Every other mode: NotImplementedError(RENDER_MESSAGE)."""
+        from metadrive_ped_amd import render as rd
+        if mode not in rd.TOPDOWN_MODES:
+            raise NotImplementedError(self.RENDER_MESSAGE)
+        if window:
+            raise NotImplementedError("render(window=True): there is no on-screen window; the frames are device tensors")
+        if text:
+            raise NotImplementedError("render(text=...): the text overlay is not built")
+        for k, v in refused.items():
+            if k not in rd.REFUSED_OPTIONS:
+                raise TypeError("render() got an unexpected keyword argument {!r}".format(k))
+            if v:
+                raise NotImplementedError("render({}=True) is not built".format(k))
+        options = rd.check_options(self.num_envs, int(self.config["num_agents"]), envs=envs, screen_size=screen_size, scaling=scaling,
+                                   num_stack=num_stack, history_smooth=history_smooth, camera_position=camera_position,
+                                   target_vehicle_heading_up=target_vehicle_heading_up, draw_contour=draw_contour, track_agent=track_agent,
+                                   screen_record=screen_record)
+        self._require_engine("render")
+        if self.top_down_renderer is None:
+            self.top_down_renderer = rd.BatchedTopDownRenderer(self.engine, options)
+        elif self.top_down_renderer.options != options:
+            changed = sorted(k for k, v in options.items() if self.top_down_renderer.options[k] != v)
+            raise ValueError("render: the first call after reset() fixed the renderer's options; {} changed (reset() drops the "
+                             "renderer)".format(", ".join(changed)))
+        return self.top_down_renderer.render()
 
     def _require_engine(self, what):
         if self.engine is None:

@@ -65,6 +65,7 @@ class BatchedMultiAgentRoundaboutEnv(ObjectSpawnMixin, BatchedEnvBase):
             self.config["start_seed"] = int(seed)
             if self.engine is not None:
                 self.engine.rebuild(self.config)
+        self.top_down_renderer = None      # BaseEnv.reset clears the top-down renderer (base_env.py:526-528)
         self.lazy_init()
         self.engine.reset()
         return self.engine.obs, self._info()

@@ -122,6 +122,7 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
             # reset); episodes that auto-reset in between restart from the latest draw
             self.config["traffic_epoch"] = int(self.config.get("traffic_epoch", 0)) + 1
             self.engine.rebuild(self.config)
+        self.top_down_renderer = None      # BaseEnv.reset clears the top-down renderer (base_env.py:526-528)
         self.lazy_init()
         self.engine.reset()        # a walk: every env back to episode 0 of its walk
         if self.config["agent_policy"] == "AIProtectPolicy":     # BaseVehicle.reset (base_vehicle.py:361,367)

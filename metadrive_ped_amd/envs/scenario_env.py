@@ -75,6 +75,7 @@ class BatchedScenarioEnv(BatchedEnvBase):
         self.host = self.engine.host
 
     def reset(self, seed=None):
+        self.top_down_renderer = None      # BaseEnv.reset clears the top-down renderer (base_env.py:526-528)
         self.lazy_init()
         self.engine.reset()
         return self.engine.obs[:, 0, :], self._info()
