@@ -1982,6 +1982,31 @@ __device__ __forceinline__ int popc(SlotMask m) { return __popcll(m.lo) + __popc
 #ifndef MD_ENV_WAVES_EU
 #define MD_ENV_WAVES_EU 7
 #endif
+// ---- what a lean launch pins ----
+// The lean kernels of md_step -- env_kernel<PH_ALL, *, false, false> and wave_step_kernel<false> -- are launched only while every
+// field listed here has its pinned value: variant<PH_ALL>() (the launch predicate) asks lean_pins_hold(), and the kernels overwrite
+// their by-value copies of the arguments with the same list (lean_pins_fold; all but the staged-map env_kernel, see there), so the
+// branches on these fields fold away instead of riding along in SGPRs.  ONE list for both sides: a field taken out of the predicate
+// is no longer folded.  Only fields the predicate itself tests belong here; a field that merely happens to be unused in these
+// configs does not.
+//   zero(int32 MdConfig field): the field is 0;  null(MdState pointer): the pointer is null
+template <class Config, class State, class Zero, class Null>
+__host__ __device__ inline void lean_pins(Config& c, State& s, Zero zero, Null null) {
+    zero(c.is_multi_agent);   // the multi-agent envs have their own variant (MULTI)
+    zero(c.traffic_mode);     // trigger mode; respawn / hybrid / replay: the RESPAWN variant (scenario mode: its own kernel)
+    zero(c.agent_idm);        // the caller's actions; IDMPolicy / LaneChangePolicy agents: the RESPAWN variant
+    zero(c.num_others);       // the `others` block needs the detected sets
+    null(s.detected);         // tracked by the RESPAWN / MULTI variants only
+}
+__host__ __device__ inline bool lean_pins_hold(const MdState& s, const MdConfig& c) {
+    bool ok = true;
+    lean_pins(c, s, [&ok](const int32_t& v) { ok = ok && v == 0; }, [&ok](const void* p) { ok = ok && p == nullptr; });
+    return ok;
+}
+__host__ __device__ inline void lean_pins_fold(MdState& s, MdConfig& c) {
+    lean_pins(c, s, [](int32_t& v) { v = 0; }, [](auto*& p) { p = nullptr; });
+}
+
 // MULTI: multi-agent envs (lifecycle phase, reference order of the IDM); single-agent envs plan the traffic ahead.
 // Register budget: the single-agent fused step is compiled for 7 waves per SIMD (72 VGPRs / 96 SGPRs): measured
 // 123 us against 133 us at the compiler's own choice (6 waves) and 131 us at 8 (64 VGPRs, more spills) --
@@ -2031,6 +2056,9 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     constexpr bool kIdmKeys = !STAGE_MAP && !RESPAWN && !MULTI;
     // the road-first localisation: the lean kernel's one- and two-vehicles-per-wave forms (and the test entry point md_localize_road_first)
     constexpr bool kLocRoadFirst = PH == PH_ALL ? kIdmKeys : PH == PH_LOCALIZE_ROAD_FIRST;
+    // The lean launch: variant<PH_ALL>() guarantees the pins.  Not in the staged-map kernel: folded, its scratch grows from 16 to
+    // 80 B per lane (EXPERIMENTS.md, "Lean kernels fold what their launch pins"), so it keeps reading the fields.
+    if constexpr (PH == PH_ALL && !RESPAWN && !MULTI && !STAGE_MAP) lean_pins_fold(g, c);
     if ((int)blockIdx.x >= c.n_envs) return;
 #ifdef MD_STAMP
     const int e = g_env_order ? g_env_order[blockIdx.x] : (int)blockIdx.x;   // diagnostic: launch-order experiments
@@ -2496,6 +2524,7 @@ static_assert((sizeof(MdShape) + sizeof(MdDyn) + sizeof(MdPid) + sizeof(MdParam)
 template <bool RESPAWN>
 __global__ __launch_bounds__(64 * kWaveEnvs) void wave_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
                                                                   int lidar_stride, int lidar_offset) {
+    if constexpr (!RESPAWN) lean_pins_fold(g, c);   // the lean launch: variant<PH_ALL>() guarantees them
     const int lane = threadIdx.x & 63;
     const int e = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);   // blockDim.x / 64 envs per workgroup (<= kWaveEnvs)
     if (e >= c.n_envs) return;   // whole wave
@@ -5013,8 +5042,10 @@ Variant variant(const MdWorld* w, const MdState* s, const MdConfig* c) {
     v.stage = w->max_lanes <= kStageMaxLanes;
     v.multi = (PH & (PH_LIFECYCLE | PH_RESET)) && c->is_multi_agent;
     // agent_idm != 0: IDMPolicy and LaneChangePolicy agents are driven by code that only this variant (and MULTI) carries
+    // md_step (PH_ALL): whatever breaks one of the lean pins (lean_pins: the list the lean kernels fold) -- so does num_others > 0,
+    // which md_step accepts with the detected sets only.  The phase entry points track no detected sets.
     v.respawn = !v.multi && (PH & (PH_TRAFFIC | PH_RESET | PH_INTEGRATE)) &&
-                (c->traffic_mode != 0 || c->agent_idm != 0 || (PH == PH_ALL && s->detected != nullptr));
+                (PH == PH_ALL ? !lean_pins_hold(*s, *c) : (c->traffic_mode != 0 || c->agent_idm != 0));
     // Multi-agent md_step: eight waves per env while every workgroup of the batch is resident at once at that size (the MULTI
     // kernel's 92 VGPRs allow 5 waves per SIMD = 640 eight-wave workgroups on the 256 CUs); larger batches keep four, which
     // then fill the chip by themselves.  Measured: 512 tollgate envs x 40 agents, 1024 roundabout envs (profiles/r03_*).
