@@ -19,6 +19,8 @@
 #ifndef MD_ENTITY_H
 #define MD_ENTITY_H
 
+#include <stddef.h>
+
 #include "md_geom.h"
 #include "md_lane_change.h"
 
@@ -270,6 +272,228 @@ MD_HD void md_observe_task(int task, const MdObsCtx* k, const MdState* s, const 
         out5[0] = md_clip(beta / 0.1f, 0.0f, 1.0f); /* obs[7] yaw rate */
         out5[1] = md_step_energy(md_fabs(d->speed) * 3.6f, md_norm(d->last_x - x, d->last_y - y));
     }
+}
+
+/* The nine tasks in LOCK-STEP (the lean step kernel's form; md_observe_task above stays the specification and what the
+ * oracle runs).  A wave runs divergent bodies one after the other, so nine lanes on four different bodies cost the sum of
+ * the bodies, each with its own copies of the expensive primitives: the correctly rounded square root and the IEEE
+ * quotient, a dozen dependent instructions apiece.  Here every lane walks ONE straight-line sequence of three square-root
+ * slots and three quotient slots,
+ *     S1  S2  Q1  Q2  [md_atan, wraps]  S3  [md_asin, md_exp]  Q3
+ * with per-lane operands; a lane whose evaluation has no use for a slot feeds it (1, 0) or 0 / 1 and drops the result.
+ * Between the slots sit only the cheap operand selections; md_atan's polynomial with the phase wraps, md_asin's
+ * polynomial and md_exp occur in one evaluation each and stay private to their lanes.
+ *
+ * Sixteen lanes, so that no evaluation needs a fourth quotient: the two results of the yaw / energy task and the five
+ * of a checkpoint projection do not depend on each other and sit on lanes of their own.
+ *     lane 0, 2, 5, 6, 7   Frenet transform of task `lane`            -> r[lane][0], r[lane][1]
+ *     lane 1               heading difference                         -> r[1][0]
+ *     lane 3, 4 | 10, 11   checkpoint projection, forward | left dim  -> r[3 | 4][0] | r[3 | 4][1]
+ *     lane 12, 13          checkpoint bend radius and direction       -> r[3 | 4][2], r[3 | 4][3]
+ *     lane 14, 15          checkpoint bend angle                      -> r[3 | 4][4]
+ *     lane 8 | 9           yaw rate | step energy                     -> r[8][0] | r[8][1]
+ * Bit-exactness: every primitive receives exactly the operands md_observe_task gives it and every float operation in
+ * between is the same operation in the same order (tests/test_observe_lockstep.py compares the 45 words); the one
+ * rewriting is md_atan's -(1 / x), taken as -1 / x.
+ *
+ * r45 = the MD_OBS_TASKS x 5 results, ZEROED by the caller: a lane writes its one or two words, nothing when !k->valid.
+ * A wave calls it with ALL its lanes (no execution mask to keep around the call): lanes from MD_OBS_LANES up walk the
+ * sequence on harmless operands and write nothing. */
+#define MD_OBS_LANES 16
+/* Which evaluation a lane runs depends on nothing but its number.  On the device `lane` IS the calling thread's lane in its
+ * wave (md_observe_lane's precondition there), so "lane is one of these" is a literal execution mask that costs no compare
+ * and no register to keep; the host tests the bit.  The mask is made anew at every use (one scalar move, which the volatile
+ * keeps in place): as a plain constant the compiler hoists the two dozen masks out of the kernel's loop over agents and
+ * holds them in scalar registers through the whole stage, which spills others (EXPERIMENTS.md, "Observation tasks in
+ * lock-step": the lean kernel's spilled SGPRs by form). */
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MD_LANE_IN(lane, mask) __extension__({ unsigned long long m_; __asm__ volatile("s_mov_b64 %0, %1" : "=s"(m_) : "i"(mask)); __builtin_amdgcn_inverse_ballot_w64(m_); })
+#else
+#define MD_LANE_IN(lane, mask) ((((mask) >> (lane)) & 1ull) != 0)
+#endif
+#define MD_LANE_F(m) ((int)(offsetof(MdLane, m) / sizeof(float)))
+
+/* md_atan(q) after its argument reduction: xr = the reduced argument, y0 = the octant's offset */
+MD_HD float md_atan_reduced(float xr, float y0, int neg) {
+    float z = xr * xr;
+    y0 += (((8.05374449538e-2f * z - 1.38776856032e-1f) * z + 1.99777106478e-1f) * z - 3.33329491539e-1f) * z * xr + xr;
+    return neg ? -y0 : y0;
+}
+
+/* md_asin(x) for 0 <= x <= 0.5, where it takes neither the sign flip nor the square-root branch */
+MD_HD float md_asin_small(float x) {
+    float z = x * x;
+    return ((((4.2163199048e-2f * z + 2.4181311049e-2f) * z + 4.5470025998e-2f) * z + 7.4953002686e-2f) * z
+            + 1.6666752422e-1f) * z * x + x;
+}
+
+MD_HD void md_observe_lane(int lane, const MdObsCtx* k, const MdState* s, const MdConfig* c, int n, float* r45) {
+    if (!k->valid) return;
+    const MdShape* sh = &s->shape[n];
+    const MdDyn* d = &s->dyn[n];
+    /* everything a lane may select from is loaded by all of them: a load under a condition is a branch */
+    const float x = sh->cx, y = sh->cy, hc = sh->c, hs = sh->s;
+    const float last_x = d->last_x, last_y = d->last_y, last_c = d->last_c, last_s = d->last_s, speed = d->speed;
+    const int task = (lane < 9) ? lane : ((lane == 9) ? 8 : 3 + (lane & 1));
+/* the sets of lanes by evaluation, and v = e on the lanes of a set (the sets of one selection are disjoint) */
+#define MD_LF 0x00E5ull
+#define MD_LN 0x0C18ull
+#define MD_LH 0x0002ull
+#define MD_LY 0x0100ull
+#define MD_LE 0x0200ull
+#define MD_LB 0x3000ull
+#define MD_LA 0xC000ull
+#define MD_PICK(m, v, e) do { const int p_ = MD_LANE_IN(lane, m); v = p_ ? (e) : v; } while (0)
+#define MD_PICK2(m, v, e, w, f) do { const int p_ = MD_LANE_IN(lane, m); v = p_ ? (e) : v; w = p_ ? (f) : w; } while (0)
+    /* ---- the lane's record, loaded once: eight words whose meaning depends on the evaluation ----
+     *      g0  g1  g2     g3   g4           g5         g6       g7
+     *   F  ax  ay  bx     by   end_phase_w  end_phase  dirsign  length
+     *   N  ex  ey  elx    ely
+     *   H  ax  ay  ex     ey   sx           sy         dirsign
+     *   B          bx                                  dirsign
+     *   A          angle                                                                        */
+    const char* const ref0 = (const char*)k->ref0;   /* the record by its distance from ref0: one word to select, not a pointer */
+    int o_rec = 0;                                   /* tasks 0, 3 and 8: ref0 */
+    MD_PICK(0x0002ull, o_rec, (int)((const char*)k->ref_last - ref0));   /* task 1 */
+    MD_PICK(0x0004ull, o_rec, (int)((const char*)k->lane - ref0));       /* task 2 */
+    MD_PICK(0xA810ull, o_rec, (int)((const char*)k->next0 - ref0));      /* task 4: lanes 4, 11, 13, 15 */
+    MD_PICK(0x0020ull, o_rec, (int)((const char*)k->fin - ref0));        /* task 5 */
+    MD_PICK(0x00C0ull, o_rec, (int)((const char*)k->rl - ref0));         /* tasks 6, 7 */
+    const MdLane* L = (const MdLane*)(ref0 + o_rec);
+    const float* lf = (const float*)L;
+    int i0 = MD_LANE_F(ax), i1 = MD_LANE_F(ay), i2 = MD_LANE_F(bx), i3 = MD_LANE_F(by);
+    int i4 = MD_LANE_F(end_phase_w), i5 = MD_LANE_F(end_phase);
+    MD_PICK2(MD_LN, i0, MD_LANE_F(ex), i1, MD_LANE_F(ey));
+    MD_PICK2(MD_LN, i2, MD_LANE_F(elx), i3, MD_LANE_F(ely));
+    MD_PICK2(MD_LH, i2, MD_LANE_F(ex), i3, MD_LANE_F(ey));
+    MD_PICK2(MD_LH, i4, MD_LANE_F(sx), i5, MD_LANE_F(sy));
+    MD_PICK(MD_LA, i2, MD_LANE_F(angle));
+    const float g0 = lf[i0], g1 = lf[i1], g2 = lf[i2], g3 = lf[i3], g4 = lf[i4], g5 = lf[i5];
+    const float g6 = L->dirsign, g7 = L->length;
+    const int type = L->type;
+
+    /* ---- the lane's vector (a, b) ----
+     * F: point - lane origin; N: checkpoint - position; H: the lane's chord (straight) or its lateral at the position
+     * (circular); Y: the heading; E: the step's displacement */
+    float px = x, py = y;
+    MD_PICK2(0x0040ull, px, last_x, py, last_y);   /* task 6: where the vehicle was */
+    const float later_middle = (k->cur_n / 2.0f - 0.5f) * k->cur_w;
+    const float fa = px - g0, fb = py - g1;
+    const int h_straight = (int)MD_LANE_IN(lane, MD_LH) & (type == 0);
+    float a = 1.0f, b = 0.0f;
+    MD_PICK2(MD_LF, a, fa, b, fb);
+    MD_PICK2(MD_LN, a, (g0 + later_middle * g2) - x, b, (g1 + later_middle * g3) - y);
+    MD_PICK2(MD_LH, a, h_straight ? g2 - g4 : ((g6 > 0.0f) ? fa : g0 - x), b, h_straight ? g3 - g5 : ((g6 > 0.0f) ? fb : g1 - y));
+    MD_PICK2(MD_LY, a, hc, b, hs);
+    MD_PICK2(MD_LE, a, last_x - x, b, last_y - y);
+
+    /* S1: F |point - origin|, N dn, H |chord| or ln, Y |heading|, E the step's distance */
+    const float n1 = md_norm(a, b);
+    /* S2: Y |last heading|, H fn */
+    float a2 = 1.0f, b2 = 0.0f;
+    MD_PICK2(MD_LY, a2, last_c, b2, last_s);
+    MD_PICK2(MD_LH, a2, hc, b2, hs);
+    const float n2 = md_norm(a2, b2);
+
+    /* Q1: F dy / dx (md_atan2), N dx / dn, H vy / n, Y cosb, E dist / 1000, B bend, A angle in degrees / angle_max */
+    const int curved = type == 1;
+    float num1 = 0.0f, den1 = 1.0f;
+    MD_PICK2(MD_LF, num1, fb, den1, fa);
+    MD_PICK2(MD_LN, num1, a, den1, n1);
+    MD_PICK2(MD_LH, num1, b, den1, n1);
+    MD_PICK2(MD_LY, num1, hc * last_c + hs * last_s, den1, n1 * n2);
+    MD_PICK2(MD_LE, num1, n1, den1, 1000.0f);
+    MD_PICK2(MD_LB, num1, g2, den1, c->curve_radius_max + k->cur_n * k->cur_w);
+    MD_PICK2(MD_LA, num1, (curved ? g2 : 0.0f) * 57.29577951308232f, den1, c->curve_angle_max);
+    float out1 = ((curved ? -g6 : 0.0f) + 1.0f) / 2.0f;   /* B: the bend's direction */
+    const float q1 = num1 / den1;
+    /* B, A: done but for the clips */
+    float out0 = (q1 + 1.0f) / 2.0f;
+    MD_PICK(MD_LB, out0, (type == 1) ? q1 : 0.0f);
+
+    /* Q2: F md_atan's argument reduction, N dy / dn, H -vx / n.  The reduction in one quotient whichever octant: -(1 / x) as
+     * -1 / x (the same bits: the sign of a quotient is the exclusive or of its operands' signs), (x - 1) / (x + 1), or x / 1 = x */
+    const int at_neg = q1 < 0.0f;
+    const float at_x = at_neg ? -q1 : q1;
+    const int at_big = at_x > 2.414213562373095f, at_mid = !at_big && at_x > 0.4142135623730950f;
+    const float at_y0 = at_big ? MD_HALF_PI_F : (at_mid ? MD_QUARTER_PI_F : 0.0f);
+    float num2 = 0.0f, den2 = 1.0f;
+    MD_PICK2(MD_LF, num2, at_big ? -1.0f : (at_mid ? at_x - 1.0f : at_x), den2, at_big ? at_x : (at_mid ? at_x + 1.0f : 1.0f));
+    MD_PICK2(MD_LN, num2, b, den2, n1);
+    MD_PICK2(MD_LH, num2, -a, den2, n1);
+    const float q2 = num2 / den2;
+
+    /* F: md_lane_local; its md_atan2(fb, fa) from q1 and q2.  One level of branch: the choices inside are selects (nested
+     * branches cost a saved execution mask each), the straight lane's two dot products are computed by all F lanes */
+    if (MD_LANE_IN(lane, MD_LF)) {
+        out0 = fa * g2 + fb * g3;
+        out1 = fa * g3 - fb * g2;
+        if (type != 0) {
+            float abs_phase = md_atan_reduced(q2, at_y0, q1 < 0.0f);
+            abs_phase = (fa < 0.0f) ? ((fb < 0.0f) ? abs_phase - MD_PI_F : abs_phase + MD_PI_F) : abs_phase;
+            abs_phase = (fb == 0.0f) ? ((fa > 0.0f) ? 0.0f : MD_PI_F) : abs_phase;
+            abs_phase = (fa == 0.0f) ? ((fb > 0.0f) ? MD_HALF_PI_F : ((fb < 0.0f) ? -MD_HALF_PI_F : 0.0f)) : abs_phase;
+            const float radius = g2, start_phase = g3;
+            const float d_start = md_fabs(md_wrap_to_pi(abs_phase - start_phase));
+            const float d_end = md_fabs(md_wrap_to_pi(abs_phase - g4));
+            const int clockwise = g6 < 0.0f, from_end = d_start > d_end;
+            const float phase0 = from_end ? g5 : start_phase;
+            const float along = md_wrap_to_pi(clockwise ? (phase0 - abs_phase) : (abs_phase - phase0)) * radius;
+            out0 = from_end ? along + g7 : along;
+            out1 = g6 * (n1 - radius);
+        }
+    }
+
+    /* N: the checkpoint direction, cut at NAVI_POINT_DIST, in the vehicle's frame; H: the lateral (lx, ly) */
+    const float NAVI_POINT_DIST = 50.0f;
+    const int cut = (int)MD_LANE_IN(lane, MD_LN) & (n1 > NAVI_POINT_DIST);
+    const int h_quot = (int)MD_LANE_IN(lane, MD_LH) & (type == 0);   /* h_straight, tested again: a mask kept is a register kept */
+    const float vx = cut ? q1 * NAVI_POINT_DIST : (h_quot ? q1 : a);
+    const float vy = cut ? q2 * NAVI_POINT_DIST : (h_quot ? q2 : b);
+
+    /* S3: H ln (straight lane: of the two quotients), Y md_acos's square root (0 <= cosb <= 1) */
+    const float cosb = md_clip(q1, 0.0f, 1.0f);
+    const int ac_hi = (int)MD_LANE_IN(lane, MD_LY) & (cosb > 0.5f);
+    const float n3 = md_sqrt(h_quot ? vx * vx + vy * vy : (ac_hi ? 0.5f * (1.0f - cosb) : 1.0f));
+    const float ln = h_quot ? n3 : n1;
+
+    /* Q3: N fwd (lanes 3, 4) or left (lanes 10, 11) / 50, H cosv, Y beta / 0.1, E md_step_energy's t / 100 */
+    float num3 = vx * hc + vy * hs, den3 = NAVI_POINT_DIST;
+    MD_PICK(0x0C00ull, num3, vy * hc - vx * hs);
+    MD_PICK2(MD_LH, num3, hc * vx + hs * vy, den3, ln * n2);
+    if (MD_LANE_IN(lane, MD_LY)) {
+        num3 = ac_hi ? 2.0f * md_asin_small(n3) : MD_HALF_PI_F - md_asin_small(cosb);
+        den3 = 0.1f;
+    }
+    if (MD_LANE_IN(lane, MD_LE)) {
+        float t = 3.25f * md_exp(0.01f * (md_fabs(speed) * 3.6f));
+        num3 = t * q1;
+        den3 = 100.0f;
+    }
+    const float q3 = num3 / den3;
+
+    int w0 = task * 5;
+    MD_PICK2(MD_LN, out0, (q3 + 1.0f) / 2.0f, w0, w0 + (lane >= 10));
+    MD_PICK(MD_LH, out0, (!(ln * n2 != 0.0f)) ? 0.0f : md_clip(q3, -1.0f, 1.0f) / 2.0f + 0.5f);
+    MD_PICK(MD_LY, out0, q3);
+    MD_PICK2(MD_LE, out0, q3 * 1000.0f, w0, w0 + 1);
+    MD_PICK(MD_LB, w0, w0 + 2);
+    MD_PICK(MD_LA, w0, w0 + 4);
+
+    /* ---- the lane's one or two words; clipped to [0, 1] but for the Frenet coordinates, the heading difference (clipped
+     * above) and the energy ---- */
+    MD_PICK(0xFD18ull, out0, md_clip(out0, 0.0f, 1.0f));   /* N, Y, B, A */
+    if (MD_LANE_IN(lane, 0xFFFFull)) r45[w0] = out0;
+    if (MD_LANE_IN(lane, MD_LF | MD_LB)) r45[w0 + 1] = (lane >= 12) ? md_clip(out1, 0.0f, 1.0f) : out1;
+#undef MD_PICK
+#undef MD_PICK2
+#undef MD_LF
+#undef MD_LN
+#undef MD_LH
+#undef MD_LY
+#undef MD_LE
+#undef MD_LB
+#undef MD_LA
 }
 
 /* dist to left/right of the route (base_vehicle.py:491-499) from the lateral on the current road's first lane */

@@ -1627,14 +1627,25 @@ __device__ __forceinline__ void idm_group_wave(const MdWorld& w, const MdLane* l
 // Observation / reward / done of one agent by one wave: the nine independent geometric evaluations
 // (md_observe_task) run on lanes 0..8 at once, lane 0 gathers them with v_readlane and combines.
 // ------------------------------------------------------------------------------------------------
+// A/B builds: -DMD_OBS_LOCKSTEP=0 compiles the lean kernel with the serial tasks (md_observe_task) like every other kernel
+#ifndef MD_OBS_LOCKSTEP
+#define MD_OBS_LOCKSTEP 1
+#endif
 // One agent per wave (`a` wave-uniform: its context lives in scalar registers) -- the single-agent envs' form.
+// kLockstep (the lean kernel): the tasks as md_observe_lane, sixteen lanes on one straight-line sequence of three square
+// roots and three quotients instead of nine lanes on four bodies run one after the other; same 45 words in the scratch.
+template <bool kLockstep = false>
 __device__ __forceinline__ void observe_agent_wave1(const MdLane* lanes, const MdRoad* roads, const MdState& s, const MdConfig& c, int a,
                                     int just_reset, int lane_id, float* wave_scratch /* LDS, MD_OBS_TASKS*5 floats */) {
     MdObsCtx k;
     MD_FINE_STAMP(a == 0 && lane_id == 0, 8);
     md_observe_ctx(lanes, roads, &s, a, &k);
     MD_FINE_STAMP(a == 0 && lane_id == 0, 9);
-    if (lane_id < MD_OBS_TASKS) {
+    if constexpr (kLockstep) {
+        // the lanes write one or two words each: the rest of the 45 are zeros (an LDS unit runs a wave's writes in order)
+        if (lane_id < MD_OBS_TASKS * 5) wave_scratch[lane_id] = 0.0f;
+        md_observe_lane(lane_id, &k, &s, &c, a, wave_scratch);   // lanes 0 .. MD_OBS_LANES - 1 write
+    } else if (lane_id < MD_OBS_TASKS) {
         float mine[5];
         md_observe_task(lane_id, &k, &s, &c, a, mine);
 #pragma unroll
@@ -2056,6 +2067,8 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     constexpr bool kIdmKeys = !STAGE_MAP && !RESPAWN && !MULTI;
     // the road-first localisation: the lean kernel's one- and two-vehicles-per-wave forms (and the test entry point md_localize_road_first)
     constexpr bool kLocRoadFirst = PH == PH_ALL ? kIdmKeys : PH == PH_LOCALIZE_ROAD_FIRST;
+    // the agent's observation tasks in lock-step (md_observe_lane): the lean kernel only
+    constexpr bool kObsLockstep = MD_OBS_LOCKSTEP && PH == PH_ALL && kIdmKeys;
     // The lean launch: variant<PH_ALL>() guarantees the pins.  Not in the staged-map kernel: folded, its scratch grows from 16 to
     // 80 B per lane (EXPERIMENTS.md, "Lean kernels fold what their launch pins"), so it keeps reading the fields.
     if constexpr (PH == PH_ALL && !RESPAWN && !MULTI && !STAGE_MAP) lean_pins_fold(g, c);
@@ -2382,7 +2395,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         // disjoint from what observe writes -- obs, reward, the agent's flags / steps / energy).
         if (wave == 0) {
             if (!(MD_ENV_SKIP & 16))
-                for (int a = 0; a < c.agents_per_env; ++a) observe_agent_wave1(lanes, roads, s, c, a, just_reset, lane, l_scratch);
+                for (int a = 0; a < c.agents_per_env; ++a) observe_agent_wave1<kObsLockstep>(lanes, roads, s, c, a, just_reset, lane, l_scratch);
         } else if (!(MD_ENV_SKIP & 2)) {
             // the driving traffic vehicles by RANK, not by slot: dealt by slot (j = A + wave - 1, + kWaves - 1, ...) two of an env's
             // two or three vehicles meet on one wave in every third env while another wave idles

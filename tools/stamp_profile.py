@@ -113,6 +113,8 @@ def main():
     if len(lo):
         print("observe(agent) fine: context %.0f | nine tasks %.0f | combine + stores %.0f (p50 cycles)" % (
             np.median(lo[:, 9] - lo[:, 8]), np.median(lo[:, 10] - lo[:, 9]), np.median(lo[:, 11] - lo[:, 10])))
+        print("observe(agent) fine, p99: context %.0f | nine tasks %.0f | combine + stores %.0f" % (
+            np.percentile(lo[:, 9] - lo[:, 8], 99), np.percentile(lo[:, 10] - lo[:, 9], 99), np.percentile(lo[:, 11] - lo[:, 10], 99)))
     # the trigger's search (trigger_search_wave): stamp slot 15 at its start, fine slot 14 at its end.  Beside the integration it
     # starts at stamp 1 and must end before stamp 4 (the integrate stage's end); in a -DMD_TRIGGER_EARLY=0 build it starts at stamp 6
     # and is part of the traffic stage.
