@@ -142,6 +142,22 @@ class MdRender(C.Structure):
                 ("n_render", C.c_int32), ("reserved", C.c_int32), ("env_ids", P), ("out", P), ("ring", P), ("cursor", P)]
 
 
+# include/md_branch.h: the extras table's size, and md_branch's argument block
+MD_BR_MAX_EXTRAS = 12
+
+
+class MdBranchExtra(C.Structure):
+    _fields_ = [("dst", P), ("src", P), ("row_bytes", C.c_int64)]
+
+
+class MdBranch(C.Structure):
+    """include/md_branch.h: the (source row, destination row) pairs of one md_branch launch, the row counts of the two states and
+    the engine-owned per-env arrays outside MdState"""
+    _fields_ = [("struct_size", C.c_int32), ("n_pairs", C.c_int32), ("src_n_envs", C.c_int32), ("dst_n_envs", C.c_int32),
+                ("n_extras", C.c_int32), ("reserved", C.c_int32), ("src_row", P), ("dst_row", P),
+                ("extra", MdBranchExtra * MD_BR_MAX_EXTRAS)]
+
+
 class MdState(C.Structure):
     _fields_ = [
         ("shape", P), ("dyn", P), ("param", P), ("nav", P), ("pid", P), ("action", P), ("route_nodes", P),
@@ -238,6 +254,8 @@ CURRICULUM_ENTRY_POINTS = {"md_curriculum": (_i, [_S, _S, _K, C.POINTER(MdCurric
 TOPDOWN_ENTRY_POINTS = {"md_topdown": (_i, [_W, _S, _K, C.POINTER(MdTopDown), P])}
 # include/md_render.h: (w, s, c, r, stream)
 RENDER_ENTRY_POINTS = {"md_render": (_i, [_W, _S, _K, C.POINTER(MdRender), P])}
+# include/md_branch.h: (dst, src, c, b, stream)
+BRANCH_ENTRY_POINTS = {"md_branch": (_i, [_S, _S, _K, C.POINTER(MdBranch), P])}
 # declared in no header: the hooks of diagnostic (-DMD_STAMP) builds, and md_localize through the lean step's road-first path
 # (the parity tests call it; a -DMD_LOC_ROAD_FIRST=0 build runs the plain walk under that name)
 OPTIONAL_ENTRY_POINTS = {"md_debug_set_stamp_buffer": (_i, [P]), "md_debug_set_env_order": (_i, [P]),

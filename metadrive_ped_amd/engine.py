@@ -444,6 +444,7 @@ class BatchedEngine:
         self._track_det = False
         self._clear_buffers()
         self._rec = None
+        self._branch_owner = object()    # names this engine in the env snapshots it makes (branch.py), across rebuilds
         self._tracks = None
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -489,6 +490,8 @@ class BatchedEngine:
         """(Re)generate maps + scenes on the host and upload.  BaseEnv.reset's map/agent/traffic managers."""
         torch = self.torch
         self._clear_buffers()
+        self._branch_token = object()    # env snapshots (branch.py) belong to one build of the batch
+        self._branch_idx = OrderedDict() # their latest index lists, on the device
         K = self.n_traffic_draws()
         draws = None
         if self.host is None:
@@ -877,14 +880,18 @@ class BatchedEngine:
         if a.dtype != torch.float32 or a.device != self.device or not a.is_contiguous():
             a = a.to(self.device, torch.float32).contiguous()
         self._check_f32("noise", noise, self.E, 2)
-        if self._protect_action is None:
-            self._protect_action = torch.empty((self.E, 2), dtype=torch.float32, device=self.device)
-            self.protect_flags = torch.zeros(self.E, dtype=torch.uint8, device=self.device)
+        self._protect_buffers()
         with self._on_device():
             self._launch("md_ai_protect", _ptr(self.expert_weights()), _ptr(noise), _ptr(a), C.c_float(float(self.cfg["save_level"])),
                          _ptr(self.state_dev["takeover"]), _ptr(self.state_dev["expert_takeover"]), _ptr(self._protect_action),
                          _ptr(self.protect_flags), _ptr(saver_out))
         return self._protect_action
+
+    def _protect_buffers(self):
+        """ai_protect_forward's applied action and flag bytes, made on first use"""
+        if self._protect_action is None:
+            self._protect_action = self.torch.empty((self.E, 2), dtype=self.torch.float32, device=self.device)
+            self.protect_flags = self.torch.zeros(self.E, dtype=self.torch.uint8, device=self.device)
 
     def step(self, actions, noise=None):
         """actions: tensor [E, A, 2] (or [E, 2] when A == 1), float32, on the engine's device.  With agent_policy =
@@ -969,6 +976,73 @@ class BatchedEngine:
         for k, v in self.host.state.items():
             out[k] = self.state_dev[k].cpu().numpy().view(v.dtype).reshape(v.shape).copy()
         return out
+
+    # -- device-side env snapshots (include/md_branch.h, metadrive_ped_amd/branch.py) ----------------------------------------
+    def branch_fields(self):
+        """{MdState field: bytes per env} of the per-env arrays this batch has, in the header table's order; each is checked against
+        the array's real size, so a table that drifted from the state builder fails here and not in the kernel."""
+        from metadrive_ped_amd import branch
+        rows = branch.field_rows(self.cap, self.A, self.obs_dim, int(self.k.route_seg_cap), int(self.k.route_vert_cap))
+        out = OrderedDict()
+        for name, rb in rows.items():
+            t = self.state_dev.get(name)
+            if t is None or not getattr(self.s, name):
+                continue
+            if t.numel() != self.E * rb:
+                raise RuntimeError("md_branch: MdState.{} holds {} bytes, the table of per-env extents says {} x {}".format(
+                    name, t.numel(), self.E, rb))
+            out[name] = rb
+        return out
+
+    def branch_extras(self):
+        """[(name, tensor, bytes per env)]: the per-env arrays the engine owns outside MdState -- MdWorld.env_map, the top-down
+        history and image, the AIProtect bytes, the staged-draw index of random_traffic"""
+        ex = [("env_map", self.world_dev["env_map"])]
+        if self.topdown_dev is not None:
+            ex += [(k, self.topdown_dev[k]) for k in ("ring_traffic", "ring_pos", "cursor")] + [("topdown", self.topdown)]
+        if "takeover" in self.state_dev:
+            self._protect_buffers()
+            ex += [("takeover", self.state_dev["takeover"]), ("expert_takeover", self.state_dev["expert_takeover"]),
+                   ("protect_flags", self.protect_flags)]
+        if self._staged is not None and not self._walk:
+            ex.append(("draw_idx", self.draw_idx))
+        out = []
+        for name, t in ex:
+            nbytes = t.numel() * t.element_size()
+            assert t.is_contiguous() and nbytes % self.E == 0, name
+            out.append((name, t, nbytes // self.E))
+        return out
+
+    def _branch_indices(self, src, dst):
+        """The pair lists on the device, [2, n] int32 (a pinned host copy and an asynchronous upload: no sync); the latest few
+        lists are kept, so a rollout loop that branches the same envs again uploads nothing."""
+        torch = self.torch
+        host = np.stack([src, dst]).astype(np.int32)
+        key = host.tobytes()
+        t = self._branch_idx.get(key)
+        if t is None:
+            t = torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
+            self._branch_idx[key] = t
+            while len(self._branch_idx) > 8:
+                self._branch_idx.popitem(last=False)
+        else:
+            self._branch_idx.move_to_end(key)
+        return t
+
+    def branch_rows(self, dst_state, src_state, src, dst, src_n, dst_n, extras):
+        """ONE md_branch launch on torch's current stream: row src[i] of every per-env array of `src_state` (an abi.MdState: this
+        engine's self.s or a snapshot's) -> row dst[i] of `dst_state`; extras = [(dst address, src address, bytes per env)].
+        src / dst: host integer arrays, already checked by the caller (ranges, no destination twice, no overlap); the kernel
+        itself only guards the rows against the two row counts."""
+        from metadrive_ped_amd import branch
+        src, dst = np.asarray(src, dtype=np.int64).reshape(-1), np.asarray(dst, dtype=np.int64).reshape(-1)
+        if src.size != dst.size or src.size == 0:
+            raise ValueError("md_branch: {} source rows for {} destination rows".format(src.size, dst.size))
+        idx = self._branch_indices(src, dst)
+        n = len(src)
+        b = branch.fill_branch(idx.data_ptr(), idx.data_ptr() + 4 * n, n, src_n, dst_n, extras)
+        with self._on_device():
+            self._check(self.lib.md_branch(C.byref(dst_state), C.byref(src_state), C.byref(self.k), C.byref(b), self._stream()), "md_branch")
 
     def upload_state(self, arrays):
         for k, v in arrays.items():

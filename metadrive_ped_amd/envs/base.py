@@ -119,6 +119,127 @@ class BatchedEnvBase:
         """The lazy info entries that test bits of the flag words `fl`: this family's FLAG_INFO."""
         return {k: (lambda m=m: (fl & m) != 0) for k, m in self.FLAG_INFO}
 
+    # -- device-side snapshots (metadrive_ped_amd/branch.py, include/md_branch.h) ---------------
+    def _branch_plan(self):
+        """(batch signature, {MdState field: bytes per env}, the engine's extras) of the batch as it is now"""
+        from metadrive_ped_amd import branch
+        e, c = self.engine, self.config
+        key = (e._branch_token, len(e.state_dev), e.protect_flags is None)
+        if getattr(self, "_branch_cache", (None, ))[0] != key:
+            fields, extras = e.branch_fields(), e.branch_extras()
+            td = None
+            if e.topdown_dev is not None:
+                td = tuple(int(c[k]) for k in ("resolution_size", "frame_stack", "frame_skip", "post_stack", "norm_pixel"))
+            family = "marl:{}".format(c["marl_map"]) if c["is_multi_agent"] else "pg"
+            sig = branch.batch_signature(family, e.cap, e.A, e.obs_dim, td, tuple(fields) + tuple(n for n, _, _ in extras))
+            self._branch_cache = (key, sig, fields, extras)
+        return self._branch_cache[1:]
+
+    def _checked_pairs(self, what, a, b, check, keep=None):
+        """check() -> the checked (a, b) index arrays, remembered under the arguments' cheap names (branch.pair_key) for the
+        latest few calls.  `keep`: an object the memo entry belongs to (a snapshot, named by id in `what`): held weakly, and the
+        entry is only used while it is that very object."""
+        import weakref
+        from metadrive_ped_amd import branch
+        ka, kb = branch.pair_key(a), branch.pair_key(b)
+        if ka is None or kb is None:
+            return check()
+        memo = self.__dict__.setdefault("_pair_memo", {})
+        key = what + (ka, kb, self.num_envs)
+        hit = memo.get(key)
+        if hit is not None and (hit[1] is None or hit[1]() is keep):
+            return hit[0]
+        out = check()
+        if len(memo) >= 8:
+            memo.pop(next(iter(memo)))
+        memo[key] = (out, None if keep is None else weakref.ref(keep))
+        return out
+
+    def _seeds_np(self):
+        """The host scene's seed list as an int64 array, kept beside it (the list is only ever rewritten here and by a build)"""
+        seeds = self.engine.host.seeds
+        m = getattr(self, "_seeds_mirror", None)
+        if m is None or m[0] is not seeds:
+            m = self._seeds_mirror = (seeds, np.asarray(seeds, dtype=np.int64))
+        return m[1]
+
+    def _seeds_moved(self, seeds, dst):
+        """The scenario seeds follow the rows: env dst[i] now plays seeds[i].  Host-side, from the host-side indices: no sync."""
+        arr = self._seeds_np()
+        if np.array_equal(arr[dst], seeds):      # the usual case of a rollout loop: nothing to rewrite
+            return
+        arr[dst] = seeds
+        self.engine.host.seeds[:] = arr.tolist()
+        self._seed_cache = (None, None)
+
+    def snapshot(self, envs=None):
+        """-> EnvSnapshot: a device-resident copy of the envs `envs` (host integers; None: all), made by ONE md_branch launch on
+        torch's current stream, no host sync.  It holds everything that makes an env's next step() bit-identical: every per-env
+        row of every state array (live, reset snapshot rows, step outputs, RNG), the env's map, the top-down history and image,
+        the AIProtect takeover bytes and the scenario seed.  It does NOT hold the lidar-noise and expert-noise generators (one
+        stream per batch), the viewer's render history or a recording buffer.  Valid across step() and a plain reset(); not
+        across reset(seed=...), a rebuild of the engine or close()."""
+        from metadrive_ped_amd import abi as _abi, branch
+        branch.check_scope(self.config, "snapshot", self.engine)
+        if envs is None:
+            envs = np.arange(self.num_envs, dtype=np.int64)
+        else:
+            envs = branch.as_indices(envs, "envs")
+            if envs.size == 0:
+                raise ValueError("snapshot: envs names no env")
+            branch.check_range(envs, self.num_envs, "snapshot: envs")
+            branch.check_distinct(envs, self.num_envs, "snapshot: envs")
+        self._require_engine("snapshot")
+        e, n = self.engine, int(envs.size)
+        sig, fields, extras = self._branch_plan()
+        st_off, ex_off, total = branch.layout(fields, [(name, rb) for name, _, rb in extras], n)
+        storage = e.torch.empty(total, dtype=e.torch.uint8, device=e.device)
+        base = storage.data_ptr()
+        s = _abi.MdState()
+        for name, (off, _) in st_off.items():
+            setattr(s, name, base + off)
+        e.branch_rows(s, e.s, envs, np.arange(n, dtype=np.int64), e.E, n, [(base + ex_off[name][0], t.data_ptr(), rb) for name, t, rb in extras])
+        return branch.EnvSnapshot(envs, self._seeds_np()[envs], sig, e._branch_token, storage, s,
+                                  {name: (base + off, rb) for name, (off, rb) in ex_off.items()}, total, owner=e._branch_owner)
+
+    def restore(self, snap, envs=None, rows=None):
+        """Snapshot row rows[i] -> env envs[i], ONE md_branch launch on torch's current stream, no host sync.  Defaults: every row,
+        to the env it came from; a one-row snapshot goes to every env named.  The envs' scenario seeds follow (current_seeds,
+        info["env_seed"], get_state()["__seeds__"]), so a set_state() of a checkpoint from before is refused as another
+        assignment.  What a snapshot does not hold (the noise generators, render history, recordings) is not touched.
+        ValueError: an index out of range or an env named twice (names the env), a snapshot of another kind of batch, or one
+        invalidated by reset(seed=...) / a rebuild / close()."""
+        from metadrive_ped_amd import branch
+        branch.check_scope(self.config, "restore", self.engine)
+        if not isinstance(snap, branch.EnvSnapshot):
+            raise TypeError("restore: expected an EnvSnapshot from env.snapshot(), got {!r}".format(type(snap).__name__))
+        rows, envs = self._checked_pairs(("restore", id(snap)), rows, envs,
+                                         lambda: branch.check_restore_pairs(snap, envs, rows, self.num_envs), keep=snap)
+        branch.check_staged_draws(self.config, (snap._source[rows], envs), "restore")
+        if self.engine is None:
+            raise ValueError("restore: the snapshot is no longer valid: this env has no engine (close() came after it, or reset() "
+                             "was never called)")
+        e = self.engine
+        sig, _, extras = self._branch_plan()
+        branch.check_snapshot(snap, sig, e._branch_token, owner=e._branch_owner)
+        e.branch_rows(e.s, snap._state, rows, envs, snap.num_envs, e.E, [(t.data_ptr(), snap._extras[name][0], rb) for name, t, rb in extras])
+        self._seeds_moved(snap._seeds[rows], envs)
+
+    def branch(self, src, dst):
+        """Live env -> live env(s) in ONE md_branch launch on torch's current stream, no host sync: `src` one env or as many as
+        `dst`.  Everything a snapshot holds travels (see snapshot()); reset() without a new seed keeps the branched assignment,
+        since the reset snapshot rows travel too.  ValueError names an env that is out of range, twice in dst, or both a source
+        and a destination (the pairs are copied concurrently)."""
+        from metadrive_ped_amd import branch
+        branch.check_scope(self.config, "branch", self.engine)
+        src, dst = self._checked_pairs(("branch", ), src, dst, lambda: branch.check_branch_pairs(src, dst, self.num_envs))
+        branch.check_staged_draws(self.config, (src, dst), "branch")
+        self._require_engine("branch")
+        e = self.engine
+        _, _, extras = self._branch_plan()
+        e.branch_rows(e.s, e.s, src, dst, e.E, e.E, [(t.data_ptr(), t.data_ptr(), rb) for _, t, rb in extras])
+        self._seeds_moved(self._seeds_np()[src], dst)
+
     # -- checkpoints --------------------------------------------------------------------------
     def _check_checkpoint(self, state):
         """-> the arrays of `state` (its "__...__" keys dropped), once the checkpoint is known to fit this batch: taken with the
