@@ -158,6 +158,24 @@ class MdBranch(C.Structure):
                 ("extra", MdBranchExtra * MD_BR_MAX_EXTRAS)]
 
 
+# include/md_ped.h: the phases (MdNav.toll_state of a policy-driven pedestrian), and md_ped's argument block
+PED_OFF, PED_WAIT_A, PED_CROSS_AB, PED_WAIT_B, PED_CROSS_BA = range(5)
+
+
+class MdPed(C.Structure):
+    """include/md_ped.h: the constants of the crossing rule that all pedestrians share (config pedestrian_config)"""
+    _fields_ = [("struct_size", C.c_int32), ("wait_min_steps", C.c_int32), ("clear_dist", C.c_float), ("margin", C.c_float),
+                ("time_margin", C.c_float), ("yield_ahead", C.c_float), ("yield_time", C.c_float), ("reserved", C.c_int32)]
+
+
+def make_md_ped(pedestrian_config):
+    p = MdPed()
+    p.struct_size, p.wait_min_steps = C.sizeof(MdPed), int(pedestrian_config["wait_min_steps"])
+    for k in ("clear_dist", "margin", "time_margin", "yield_ahead", "yield_time"):
+        setattr(p, k, float(pedestrian_config[k]))
+    return p
+
+
 class MdState(C.Structure):
     _fields_ = [
         ("shape", P), ("dyn", P), ("param", P), ("nav", P), ("pid", P), ("action", P), ("route_nodes", P),
@@ -256,6 +274,8 @@ TOPDOWN_ENTRY_POINTS = {"md_topdown": (_i, [_W, _S, _K, C.POINTER(MdTopDown), P]
 RENDER_ENTRY_POINTS = {"md_render": (_i, [_W, _S, _K, C.POINTER(MdRender), P])}
 # include/md_branch.h: (dst, src, c, b, stream)
 BRANCH_ENTRY_POINTS = {"md_branch": (_i, [_S, _S, _K, C.POINTER(MdBranch), P])}
+# include/md_ped.h: (s, c, p, stream)
+PED_ENTRY_POINTS = {"md_ped": (_i, [_S, _K, C.POINTER(MdPed), P])}
 # declared in no header: the hooks of diagnostic (-DMD_STAMP) builds, and md_localize through the lean step's road-first path
 # (the parity tests call it; a -DMD_LOC_ROAD_FIRST=0 build runs the plain walk under that name)
 OPTIONAL_ENTRY_POINTS = {"md_debug_set_stamp_buffer": (_i, [P]), "md_debug_set_env_order": (_i, [P]),

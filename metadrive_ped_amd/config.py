@@ -137,6 +137,20 @@ BATCH_DEFAULT_CONFIG = dict(
                             # detectors: numpy_expert.py:39-62) from the live state (md_expert_sense), so agent_policy="ExpertPolicy"
                             # and expert() take any vehicle_config and the multi-agent envs (all but tollgate); False: from the
                             # env's own obs row (md_expert), which only the 259-dim default vehicle config allows
+    # crossing pedestrians driven on the device (include/md_ped.h; no key of the reference's, the numbers are a design choice):
+    # placed per scenario seed at scene build, restored by the env's own reset, one md_ped launch before every md_step
+    num_pedestrians=0,      # per env; a map with fewer straight roads than that holds fewer (env.pedestrian_state() reports them)
+    pedestrian_config=dict(
+        speed=1.2,              # m/s (Pedestrian.SPEED_LIST[1])
+        wait_min_steps=10,      # a wait at the kerb lasts this + a draw of randint(0, 25) steps
+        clear_dist=1.0,         # m: a vehicle this close to the crossing line (beyond its half length) occupies it
+        margin=1.0,             # m: the strip a waiting pedestrian watches reaches this far beyond both kerbs
+        time_margin=1.0,        # s: a gap is taken if no vehicle arrives within the crossing time + this
+        yield_ahead=3.0,        # m: a crossing pedestrian looks this far ahead along its walk ...
+        yield_time=1.5,         # s: ... and stops for a vehicle that arrives there within this
+        kerb_offset=1.0,        # m: the end points lie this far outside the outermost lanes' edges
+        min_road_length=20.0,   # m: shorter roads hold no crossing
+        spawn_clearance=15.0),  # m: no crossing closer than this to the agent's spawn position
 )
 
 # The top-down observation envs' own keys (envs/top_down_env.py:12-21,54-61 of the reference): they exist for BatchedTopDownMetaDrive /
@@ -371,6 +385,26 @@ def make_config(user=None, top_down=False):
             raise ValueError("walk_scenarios=True needs auto_reset=True: an env moves on when it resets itself")
         if cfg["walk_stride"] is not None and int(cfg["walk_stride"]) < 1:
             raise ValueError("walk_stride must be >= 1 (the env count over all shards), got {!r}".format(cfg["walk_stride"]))
+    if cfg["num_pedestrians"]:
+        # crossing pedestrians: built for the single-agent PG envs; everything else is refused by name
+        n, pc = cfg["num_pedestrians"], cfg["pedestrian_config"]
+        if isinstance(n, bool) or n < 0:
+            raise ValueError("num_pedestrians={!r}: an int >= 0".format(n))
+        if cfg["is_multi_agent"]:
+            raise NotImplementedError("num_pedestrians > 0 in a multi-agent env is not built: crossing pedestrians are placed by the "
+                                      "single-agent PG scene builder")
+        if cfg["traffic_mode"] == "replay":
+            raise NotImplementedError("num_pedestrians > 0 with traffic_mode='replay' is not built: replayed slots take their poses from "
+                                      "the recorded frames")
+        for k in ("speed", "min_road_length"):
+            if not pc[k] > 0:
+                raise ValueError("pedestrian_config['{}']={!r}: a positive number".format(k, pc[k]))
+        for k in ("wait_min_steps", "clear_dist", "margin", "time_margin", "yield_ahead", "yield_time", "kerb_offset", "spawn_clearance"):
+            if pc[k] < 0:
+                raise ValueError("pedestrian_config['{}']={!r} must not be negative".format(k, pc[k]))
+        if pc["min_road_length"] < 10:
+            raise ValueError("pedestrian_config['min_road_length']={!r}: at least 10 m (a crossing keeps 5 m from both road ends)".format(
+                pc["min_road_length"]))
     if cfg["step_kernel"] not in ("auto", "wg", "wave"):
         raise ValueError("step_kernel must be 'auto', 'wg' or 'wave', got {!r}".format(cfg["step_kernel"]))
     if cfg["mover_capacity"] != 0 and (cfg["mover_capacity"] > 128 or cfg["mover_capacity"] < cfg["num_agents"]):

@@ -231,6 +231,8 @@ class HostScene(HostSceneBase):
             "physics_world_step_size", "random_spawn_lane_index", "traffic_density", "traffic_mode", "accident_prob",
             "static_traffic_object", "need_inverse_traffic", "random_lane_width", "random_lane_num", "random_agent_model",
             "random_dynamics", "initial_agents", "agent_policy", "spawn_roads", "random_traffic")})
+        if cfg.get("num_pedestrians"):     # only then: a scene without pedestrians is built (and memoised) from the same job as before
+            scene_cfg.update(num_pedestrians=int(cfg["num_pedestrians"]), pedestrian_config=dict(cfg["pedestrian_config"]))
         return scene_cfg
 
     def _build(self, uniq, scene_cfg):
@@ -577,6 +579,8 @@ class BatchedEngine:
         self.shape_f = sd["shape"].view(torch.float32).view(self.E, self.cap, 8)
         self.dyn_f = sd["dyn"].view(torch.float32).view(self.E, self.cap, 8)
         self.nav_i = sd["nav"].view(torch.int32).view(self.E, self.cap, 16)
+        # crossing pedestrians (include/md_ped.h): md_ped's argument block; None = no launch
+        self._ped = abi.make_md_ped(self.cfg["pedestrian_config"]) if self.cfg.get("num_pedestrians") else None
         self.agent_id = sd["agent_id"].view(torch.int32).view(self.E, self.cap) if "agent_id" in sd else None
         self._topdown_setup()
         if getattr(h, "tracks", None) is not None:     # scenario mode: the scenes' recorded frames come with the host scene
@@ -685,6 +689,8 @@ class BatchedEngine:
             self._step_raw()
 
     def _step_raw(self):
+        if self._ped is not None:        # the pedestrians' policy on the state the previous step left, then the world steps
+            self._check(self.lib.md_ped(C.byref(self.s), C.byref(self.k), C.byref(self._ped), self._stream()), "md_ped")
         self._launch("md_step")
         L = self.host.layout
         vc = self.cfg["vehicle_config"]
@@ -969,6 +975,26 @@ class BatchedEngine:
     def object_positions(self, slot):
         """[E, 2] tensor view of the slot's centre in every env."""
         return self.shape_f[:, slot, 0:2]
+
+    def pedestrian_state(self):
+        """The policy-driven pedestrians of every env, as device tensors: positions [E, P, 2] float32, phase [E, P] and slot
+        [E, P] int32 (abi.PED_*; ascending slot order), P = config num_pedestrians; an env that holds fewer (a map without
+        enough straight roads; clear_objects) is padded with -1.  Read from the live state: no host sync."""
+        torch = self.torch
+        P_ = int(self.cfg.get("num_pedestrians") or 0)
+        flags = self.state_dev["shape"].view(torch.int32).view(self.E, self.cap, 8)[:, :, 6]
+        phase = self.nav_i[:, :, 13]
+        driven = ((flags & abi.KIND_MASK) == abi.KIND_PEDESTRIAN) & ((flags & abi.F_ALIVE) != 0) & ((flags & abi.F_STATIC) == 0) & (phase != 0)
+        slots = torch.arange(self.cap, device=self.device, dtype=torch.int64).expand(self.E, self.cap)
+        first = torch.where(driven, slots, torch.full_like(slots, self.cap)).sort(dim=1).values[:, :P_]
+        if first.shape[1] < P_:          # more pedestrians asked for than slots
+            first = torch.nn.functional.pad(first, (0, P_ - first.shape[1]), value=self.cap)
+        have = first < self.cap
+        at = first.clamp(max=self.cap - 1)
+        pos = torch.gather(self.shape_f[:, :, 0:2], 1, at.unsqueeze(-1).expand(-1, -1, 2))
+        pos = torch.where(have.unsqueeze(-1), pos, torch.full_like(pos, -1.0))
+        ph = torch.where(have, torch.gather(phase, 1, at), torch.full_like(at, -1, dtype=torch.int32))
+        return pos, ph, torch.where(have, at, torch.full_like(at, -1)).to(torch.int32)
 
     def download_state(self):
         """Device state -> dict of numpy arrays with the host dtypes (tests / checkpoints)."""

@@ -265,7 +265,15 @@ class ObjectSpawnMixin:
         return self.engine.spawn_object(kind, position, heading_theta, envs)
 
     def set_velocity(self, handle, direction, value=None, in_local_frame=False, envs=None):
+        """On a policy-driven pedestrian (config num_pedestrians; its slot from pedestrian_state()) the velocity holds until the
+        next step() at most: md_ped rewrites the walker's velocity at the start of every step."""
         self.engine.set_velocity(handle, direction, value, in_local_frame, envs)
 
     def clear_objects(self, handles, envs=None):
+        """A policy-driven pedestrian cleared here is back when its env resets (its snapshot rows are untouched)."""
         self.engine.clear_objects(list(handles), envs)
+
+    def pedestrian_state(self):
+        """The crossing pedestrians of config num_pedestrians (include/md_ped.h) as device tensors: positions [E, P, 2], phase
+        [E, P] (0 .. 4: abi.PED_*) and slot [E, P], padded with -1 where an env holds fewer than P.  No host sync."""
+        return self.engine.pedestrian_state()

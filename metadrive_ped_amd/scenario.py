@@ -97,6 +97,8 @@ def make_scenario_config(user=None):
     base.update(user)
     base["vehicle_config"] = vc
     base.setdefault("traffic_density", 0.0)
+    if base.get("num_pedestrians"):
+        raise NotImplementedError("num_pedestrians > 0 in BatchedScenarioEnv is not built: its pedestrians come from the scenario data")
     cfg = make_config(base)
     cfg.update(own)
     cfg["scenario_mode"] = True

@@ -235,6 +235,101 @@ class EnvScene:
         # reference's PGTrafficManager.reset ends with (tests/golden/traffic_spawn.json)
         self.stream_probe = dict(engine=_peek(engine.np_random), traffic=_peek(traffic_mgr.np_random))
 
+        # ---- crossing pedestrians (include/md_ped.h): after everything else, from a stream of their own, so that every row
+        # that is not a pedestrian's is what the scene without them holds ----
+        self.ped_slots, self.ped_sites = [], []
+        if cfg.get("num_pedestrians"):
+            self._place_pedestrians(int(cfg["num_pedestrians"]), cfg["pedestrian_config"], Randomizable(seed).np_random,
+                                    first_free=slot)
+
+    # -- crossing pedestrians ----------------------------------------------------------------------
+    PED_RADIUS = 0.35            # participants.HALF_EXTENT of a pedestrian
+    PED_SITE_TRIES = 32          # draws per pedestrian before the scene goes without it
+
+    def _crossing_roads(self, min_len):
+        """[(lanes, lanes of the reverse road or None)] of the roads a crossing can lie on: every lane (the reverse road's too)
+        a StraightLane at least `min_len` long"""
+        from metadrive_ped_amd.mapgen.lanes import StraightLane
+        from metadrive_ped_amd.mapgen.pg import DECORATION, negate_road
+        net = self.tables.pg_map.net
+        ok = lambda lanes: all(isinstance(l, StraightLane) and l.length >= min_len for l in lanes)
+        out = []
+        for a, b, lanes in net.roads():
+            if a in DECORATION or not lanes or not ok(lanes):
+                continue
+            ra, rb = negate_road(a, b)
+            rev = net.graph.get(ra, {}).get(rb)
+            if rev is not None and not (rev and ok(rev)):
+                continue
+            out.append((lanes, rev))
+        return out
+
+    def _on_some_lane(self, p):
+        """p lies inside the extent of a lane of the map (decoration lanes included)"""
+        for _, _, lanes in self.tables.pg_map.net.roads():
+            for l in lanes:
+                s, lat = l.local_coordinates(p)
+                if 0.0 <= s <= l.length and abs(lat) <= l.width / 2:
+                    return True
+        return False
+
+    def _place_pedestrians(self, count, pc, rng, first_free):
+        roads = self._crossing_roads(float(pc["min_road_length"]))
+        spawn = np.array([self.shape[0]["cx"], self.shape[0]["cy"]], np.float64)
+        off = float(pc["kerb_offset"])
+        for _ in range(count if roads else 0):
+            site = None
+            for _ in range(self.PED_SITE_TRIES):
+                lanes, rev = roads[int(rng.randint(len(roads)))]
+                out_lane = lanes[-1]
+                s = float(rng.uniform(5.0, out_lane.length - 5.0))
+                A = out_lane.position(s, out_lane.width / 2 + off)
+                if rev is not None:
+                    B = rev[-1].position(rev[-1].length - s, rev[-1].width / 2 + off)
+                else:
+                    B = lanes[0].position(s, -lanes[0].width / 2 - off)
+                A, B = np.asarray(A, np.float32), np.asarray(B, np.float32)
+                ab = B.astype(np.float64) - A
+                t = min(1.0, max(0.0, float(np.dot(spawn - A, ab) / np.dot(ab, ab))))     # the crossing's point nearest to the spawn
+                if math.hypot(*(A + t * ab - spawn)) < float(pc["spawn_clearance"]) or self._on_some_lane(A) or self._on_some_lane(B):
+                    continue
+                site = (A, B)
+                road = (tuple(out_lane.index[:2]), s)
+                break
+            if site is None:
+                continue
+            if self._next_prop_slot < first_free:
+                raise ValueError("env seed {}: no free slot for a pedestrian; raise `mover_capacity`".format(self.seed))
+            A, B = site
+            at_b = bool(rng.randint(2))
+            countdown = int(rng.randint(0, 25))
+            draws = [int(rng.randint(0, 25)) for _ in range(abi.MD_IDM_RAND)]
+            slot = self._take_prop_slot()
+            d64 = B.astype(np.float64) - A.astype(np.float64)
+            h_ab = math.atan2(d64[1], d64[0])
+            h_ba = wrap_to_pi(h_ab + math.pi)
+            pos, heading = (B, h_ba) if at_b else (A, h_ab)
+            sh = self.shape[slot]
+            sh["cx"], sh["cy"] = pos
+            sh["c"], sh["s"] = math.cos(heading), math.sin(heading)
+            sh["hl"] = sh["hw"] = self.PED_RADIUS
+            sh["flags"] = abi.KIND_PEDESTRIAN | abi.F_ALIVE
+            sh["aux"] = -1
+            d = self.dyn[slot]
+            d["heading"] = heading
+            d["last_x"], d["last_y"] = pos
+            d["last_c"], d["last_s"] = sh["c"], sh["s"]
+            # the policy data in the walker's own rows (include/md_ped.h)
+            p = self.pid[slot]
+            p["hp"], p["hi"], p["hd"], p["lp"] = A[0], A[1], B[0], B[1]
+            p["li"], p["ld"], p["target_speed"], p["energy"] = float(pc["speed"]), h_ab, h_ba, 0.0
+            nv = self.nav[slot]
+            nv["toll_state"] = abi.PED_WAIT_B if at_b else abi.PED_WAIT_A
+            nv["timer"], nv["rand_cursor"] = countdown, 0
+            self.idm_rand[slot] = draws
+            self.ped_slots.append(slot)
+            self.ped_sites.append(road)       # ((start node, end node) of the drawn road, station): what the tests check the site against
+
     @property
     def n_props(self):
         return len(self.shape) - 1 - self._next_prop_slot
@@ -256,6 +351,7 @@ class EnvScene:
             cfgs[cap - n_props:] = self.vehicle_cfgs[old - n_props:]
         self.vehicle_cfgs = cfgs
         self._next_prop_slot = cap - 1 - n_props
+        self.ped_slots = [s - (old - cap) for s in self.ped_slots]
 
     # -- TrafficObjectManager.reset (manager/object_manager.py:40-151) ---------------------------
     ALERT_DIST, ACCIDENT_AREA_LEN, CONE_LONGITUDE, CONE_LATERAL, PROHIBIT_SCENE_PROB = 10, 10, 2, 1, 0.67
