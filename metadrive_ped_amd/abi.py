@@ -176,6 +176,55 @@ def make_md_ped(pedestrian_config):
     return p
 
 
+# include/md_vector_obs.h: the ceilings MD_VO_MAX_*, and md_vector_obs's argument block
+MD_VO_MAX_AGENTS, MD_VO_MAX_HISTORY, MD_VO_MAX_ROUTE_POINTS, MD_VO_MAX_LANES, MD_VO_MAX_LANE_POINTS = 16, 8, 32, 16, 16
+VECTOR_OBS_OUTPUTS = ("agents", "agents_mask", "agents_meta", "ego", "ego_mask", "route", "route_mask", "lanes", "lanes_meta", "lanes_mask")
+VECTOR_OBS_HISTORY = ("ring_pose", "ring_flags", "cursor")
+
+
+class MdVectorObs(C.Structure):
+    """include/md_vector_obs.h: the vector scene observation's counts and lengths, the per-env strides, its outputs and the
+    engine-owned history arrays"""
+    _fields_ = [("struct_size", C.c_int32), ("num_agents", C.c_int32), ("history", C.c_int32), ("route_points", C.c_int32),
+                ("num_lanes", C.c_int32), ("lane_points", C.c_int32), ("radius", C.c_float), ("max_jump", C.c_float),
+                ("route_spacing", C.c_float), ("reserved", C.c_int32), ("out_stride", C.c_int32), ("hist_stride", C.c_int32)] + \
+        [(k, P) for k in VECTOR_OBS_OUTPUTS + VECTOR_OBS_HISTORY]
+
+
+def vector_obs_blocks(vo_cfg, A, cap):
+    """-> (outputs, output row bytes, history, history row bytes); outputs / history: name -> (byte offset in an env's row, shape
+    after the env axis, numpy dtype).  One row per env, every block 16-byte aligned; a block whose count is 0 has no bytes."""
+    K, T, M, Pn, S = (int(vo_cfg[k]) for k in ("num_agents", "history", "route_points", "num_lanes", "lane_points"))
+    u1 = np.uint8
+    outs = [("agents", (A, K, T, 4), f4), ("agents_mask", (A, K, T), u1), ("agents_meta", (A, K, 4), f4), ("ego", (A, T, 4), f4),
+            ("ego_mask", (A, T), u1), ("route", (A, M, 4), f4), ("route_mask", (A, M), u1), ("lanes", (A, Pn, S, 2), f4),
+            ("lanes_meta", (A, Pn, 4), f4), ("lanes_mask", (A, Pn), u1)]
+    hist = [("ring_pose", (T, cap, 4), f4), ("ring_flags", (T, cap), i4), ("cursor", (4, ), i4)]
+    tables = []
+    for blocks in (outs, hist):
+        table, at = {}, 0
+        for name, shape, dt in blocks:
+            table[name] = (at, shape, np.dtype(dt))
+            at = (at + int(np.prod(shape)) * np.dtype(dt).itemsize + 15) // 16 * 16
+        tables += [table, at]
+    return tuple(tables)
+
+
+def make_md_vector_obs(vo_cfg, tensors):
+    """MdVectorObs of the finished config["vector_obs"]; `tensors`: out_stride, hist_stride and name -> device address of env 0's
+    block (None / missing: NULL)"""
+    v = MdVectorObs()
+    v.struct_size = C.sizeof(MdVectorObs)
+    for k in ("num_agents", "history", "route_points", "num_lanes", "lane_points"):
+        setattr(v, k, int(vo_cfg[k]))
+    for k in ("radius", "max_jump", "route_spacing"):
+        setattr(v, k, float(vo_cfg[k]))
+    v.out_stride, v.hist_stride = int(tensors["out_stride"]), int(tensors["hist_stride"])
+    for k in VECTOR_OBS_OUTPUTS + VECTOR_OBS_HISTORY:
+        setattr(v, k, tensors.get(k))
+    return v
+
+
 class MdState(C.Structure):
     _fields_ = [
         ("shape", P), ("dyn", P), ("param", P), ("nav", P), ("pid", P), ("action", P), ("route_nodes", P),
@@ -276,6 +325,8 @@ RENDER_ENTRY_POINTS = {"md_render": (_i, [_W, _S, _K, C.POINTER(MdRender), P])}
 BRANCH_ENTRY_POINTS = {"md_branch": (_i, [_S, _S, _K, C.POINTER(MdBranch), P])}
 # include/md_ped.h: (s, c, p, stream)
 PED_ENTRY_POINTS = {"md_ped": (_i, [_S, _K, C.POINTER(MdPed), P])}
+# include/md_vector_obs.h: (w, s, c, vo, stream)
+VECTOR_OBS_ENTRY_POINTS = {"md_vector_obs": (_i, [_W, _S, _K, C.POINTER(MdVectorObs), P])}
 # declared in no header: the hooks of diagnostic (-DMD_STAMP) builds, and md_localize through the lean step's road-first path
 # (the parity tests call it; a -DMD_LOC_ROAD_FIRST=0 build runs the plain walk under that name)
 OPTIONAL_ENTRY_POINTS = {"md_debug_set_stamp_buffer": (_i, [P]), "md_debug_set_env_order": (_i, [P]),

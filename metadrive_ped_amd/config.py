@@ -151,7 +151,41 @@ BATCH_DEFAULT_CONFIG = dict(
         kerb_offset=1.0,        # m: the end points lie this far outside the outermost lanes' edges
         min_road_length=20.0,   # m: shorter roads hold no crossing
         spawn_clearance=15.0),  # m: no crossing closer than this to the agent's spawn position
+    # the vector scene observation (include/md_vector_obs.h; no key of the reference's, the numbers are a design choice): None = off,
+    # no launch and no array; a dict (an empty one too) is laid over VECTOR_OBS_DEFAULT_CONFIG and env.vector_obs() returns the blocks
+    vector_obs=None,
 )
+
+VECTOR_OBS_DEFAULT_CONFIG = dict(
+    num_agents=8,           # K nearest movers, 1 .. 16
+    history=5,              # T frames of pose history, the current one included, 1 .. 8
+    radius=50.0,            # m: movers farther from the observer than this are no neighbours
+    max_jump=8.0,           # m: a displacement between two frames beyond this ends a slot's history (a respawn in the slot)
+    route_points=16,        # M waypoints along the route ahead, 0 .. 32
+    route_spacing=4.0,      # m between them
+    num_lanes=8,            # P nearest lane centre-lines, 0 .. 16
+    lane_points=8,          # S points per lane, 2 .. 16
+)
+# key -> (lowest, highest): MD_VO_MAX_* of include/md_vector_obs.h
+VECTOR_OBS_RANGES = dict(num_agents=(1, 16), history=(1, 8), route_points=(0, 32), num_lanes=(0, 16), lane_points=(2, 16))
+
+
+def check_vector_obs(user):
+    """config["vector_obs"] (a dict) laid over its defaults -> the finished dict; a ValueError names the key at fault"""
+    if not isinstance(user, dict):
+        raise ValueError("vector_obs={!r}: None (off) or a dict of {}".format(user, sorted(VECTOR_OBS_DEFAULT_CONFIG)))
+    unknown = sorted(set(user) - set(VECTOR_OBS_DEFAULT_CONFIG))
+    if unknown:
+        raise ValueError("vector_obs: unknown key(s) {} (known: {})".format(unknown, sorted(VECTOR_OBS_DEFAULT_CONFIG)))
+    vo = dict(VECTOR_OBS_DEFAULT_CONFIG, **user)
+    for k, (lo, hi) in VECTOR_OBS_RANGES.items():
+        if isinstance(vo[k], bool) or not isinstance(vo[k], int) or not lo <= vo[k] <= hi:
+            raise ValueError("vector_obs['{}']={!r}: an int in [{}, {}]".format(k, vo[k], lo, hi))
+    for k in ("radius", "max_jump", "route_spacing"):
+        if isinstance(vo[k], bool) or not isinstance(vo[k], (int, float)) or not 0 < vo[k] <= 1e18:
+            raise ValueError("vector_obs['{}']={!r}: a positive number of metres".format(k, vo[k]))
+        vo[k] = float(vo[k])
+    return vo
 
 # The top-down observation envs' own keys (envs/top_down_env.py:12-21,54-61 of the reference): they exist for BatchedTopDownMetaDrive /
 # BatchedTopDownMetaDriveEnvV2 only (make_config(top_down=True)); any other class given one raises KeyError, as the reference's would.
@@ -405,6 +439,8 @@ def make_config(user=None, top_down=False):
         if pc["min_road_length"] < 10:
             raise ValueError("pedestrian_config['min_road_length']={!r}: at least 10 m (a crossing keeps 5 m from both road ends)".format(
                 pc["min_road_length"]))
+    if cfg["vector_obs"] is not None:
+        cfg["vector_obs"] = check_vector_obs(cfg["vector_obs"])
     if cfg["step_kernel"] not in ("auto", "wg", "wave"):
         raise ValueError("step_kernel must be 'auto', 'wg' or 'wave', got {!r}".format(cfg["step_kernel"]))
     if cfg["mover_capacity"] != 0 and (cfg["mover_capacity"] > 128 or cfg["mover_capacity"] < cfg["num_agents"]):

@@ -583,6 +583,7 @@ class BatchedEngine:
         self._ped = abi.make_md_ped(self.cfg["pedestrian_config"]) if self.cfg.get("num_pedestrians") else None
         self.agent_id = sd["agent_id"].view(torch.int32).view(self.E, self.cap) if "agent_id" in sd else None
         self._topdown_setup()
+        self._vector_obs_setup()
         if getattr(h, "tracks", None) is not None:     # scenario mode: the scenes' recorded frames come with the host scene
             tr = h.tracks
             self.set_tracks(dict(shape=torch.from_numpy(np.ascontiguousarray(tr["shape"]).view(np.uint8).reshape(tr["shape"].shape[0], -1)),
@@ -612,6 +613,44 @@ class BatchedEngine:
         for k, t in self.topdown_dev.items():
             setattr(td, k, t.data_ptr())
         self._td = td
+
+    def _vector_obs_setup(self):
+        """The vector scene observation (config vector_obs; include/md_vector_obs.h): TWO allocations with one row per env -- the ten
+        output blocks, and the engine-owned history (pose ring, flag ring, cursor) -- md_vector_obs's arguments, not MdState's.
+        self.vector_obs_out holds the blocks as typed views [E, A, ...] of the output rows.  All None when the key is None."""
+        torch, vo = self.torch, self.cfg.get("vector_obs")
+        self._vo = self.vector_obs_out = self.vector_obs_rows = self.vector_obs_hist = None
+        if vo is None:
+            return
+        if self.cfg.get("scenario_mode"):
+            raise NotImplementedError("vector_obs is not built for BatchedScenarioEnv")
+        outs, out_bytes, hist, hist_bytes = abi.vector_obs_blocks(vo, self.A, self.cap)
+        self.vector_obs_rows = torch.zeros((self.E, out_bytes), dtype=torch.uint8, device=self.device)
+        self.vector_obs_hist = torch.zeros((self.E, hist_bytes), dtype=torch.uint8, device=self.device)
+        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32}
+        views, ptrs = OrderedDict(), dict(out_stride=out_bytes, hist_stride=hist_bytes)
+        for table, rows, into in ((outs, self.vector_obs_rows, views), (hist, self.vector_obs_hist, None)):
+            for name, (off, shape, dt) in table.items():
+                n = int(np.prod(shape)) * dt.itemsize
+                if n:                       # a block whose count is 0 has no bytes: its pointer stays NULL, its view is empty
+                    ptrs[name] = rows.data_ptr() + off
+                if into is not None:
+                    into[name] = rows[:, off:off + n].view(tdt[dt]).view((self.E, ) + tuple(shape))
+        self.vector_obs_out = views
+        self._vo_blocks = (outs, hist)
+        self._vo = abi.make_md_vector_obs(vo, ptrs)
+
+    def vector_obs_history(self):
+        """The vector observation's history as host numpy copies: ring_pose [E, T, cap, 4], ring_flags [E, T, cap], cursor [E, 4]
+        (the tests compare them)"""
+        rows = self.vector_obs_hist.cpu().numpy()
+        return {name: rows[:, off:off + int(np.prod(shape)) * dt.itemsize].copy().view(dt).reshape((self.E, ) + tuple(shape))
+                for name, (off, shape, dt) in self._vo_blocks[1].items()}
+
+    def vector_obs_forget(self):
+        """Empty every env's history (env.set_state: a checkpoint does not carry it, like the renderer's)"""
+        if self.vector_obs_hist is not None:
+            self.vector_obs_hist.zero_()
 
     def topdown_history(self):
         """The top-down history arrays as host numpy copies: ring_traffic, ring_pos, cursor (the tests compare them; the top-down
@@ -712,6 +751,8 @@ class BatchedEngine:
         self._lidar_noise()
         if self._td is not None:         # the top-down image of the state this step left, on the map of the episode it belongs to
             self._launch("md_topdown", C.byref(self._td))
+        if self._vo is not None:         # the vector scene observation, likewise: a walking env's last frame is traced on the old map
+            self._launch("md_vector_obs", C.byref(self._vo))
         # Only now, with the step's observation complete, do the envs whose episode just ended move on: the swap of a walk rewrites
         # MdWorld.env_map, and the detector launches above trace the map of the episode that ended
         if self._cur is not None:        # the scenario walk: the curriculum's step, and the envs whose episode just ended move on
@@ -1022,7 +1063,7 @@ class BatchedEngine:
 
     def branch_extras(self):
         """[(name, tensor, bytes per env)]: the per-env arrays the engine owns outside MdState -- MdWorld.env_map, the top-down
-        history and image, the AIProtect bytes, the staged-draw index of random_traffic"""
+        history and image, the AIProtect bytes, the staged-draw index of random_traffic, the vector observation's history and rows"""
         ex = [("env_map", self.world_dev["env_map"])]
         if self.topdown_dev is not None:
             ex += [(k, self.topdown_dev[k]) for k in ("ring_traffic", "ring_pos", "cursor")] + [("topdown", self.topdown)]
@@ -1032,6 +1073,8 @@ class BatchedEngine:
                    ("protect_flags", self.protect_flags)]
         if self._staged is not None and not self._walk:
             ex.append(("draw_idx", self.draw_idx))
+        if self._vo is not None:
+            ex += [("vector_obs_hist", self.vector_obs_hist), ("vector_obs", self.vector_obs_rows)]
         out = []
         for name, t in ex:
             nbytes = t.numel() * t.element_size()

@@ -88,6 +88,33 @@ class BatchedEnvBase:
         if self.engine is None:
             raise RuntimeError("call reset() before {}()".format(what))
 
+    # -- the vector scene observation (include/md_vector_obs.h) ---------------------------------
+    def _vector_obs_config(self, what):
+        vo = self.config.get("vector_obs")
+        if vo is None:
+            raise RuntimeError("{}(): config['vector_obs'] is None; give it a dict ({{}} takes the defaults) to turn the vector "
+                               "scene observation on".format(what))
+        return vo
+
+    def vector_obs_spec(self):
+        """{name: (shape, numpy dtype)} of vector_obs()'s tensors: [E, A, ...] in a multi-agent env, [E, ...] in a single-agent one"""
+        from metadrive_ped_amd import abi as _abi
+        vo = self._vector_obs_config("vector_obs_spec")
+        multi = bool(self.config["is_multi_agent"])
+        outs = _abi.vector_obs_blocks(vo, int(self.config["num_agents"]) if multi else 1, 1)[0]
+        return {name: ((self.num_envs, ) + (tuple(shape) if multi else tuple(shape[1:])), dt.type) for name, (_, shape, dt) in outs.items()}
+
+    def vector_obs(self):
+        """The vector scene observation of the state the last step() / reset() left, a dict of device tensors in the observer's ego
+        frame, metres: agents [.., K, T, 4] (x, y, cos, sin per frame, frame 0 = now), agents_mask, agents_meta [.., K, 4] (length,
+        width, speed, kind), ego [.., T, 4], ego_mask, route [.., M, 4], route_mask, lanes [.., P, S, 2], lanes_meta [.., P, 4]
+        (width, length, on_route, distance), lanes_mask.  Views of the engine's buffers, valid until the next step() / reset();
+        no host sync.  Leading axes [E, A] in a multi-agent env, [E] in a single-agent one."""
+        self._vector_obs_config("vector_obs")
+        self._require_engine("vector_obs")
+        out = self.engine.vector_obs_out
+        return dict(out) if self.config["is_multi_agent"] else {k: t[:, 0] for k, t in out.items()}
+
     # -- step() helpers -----------------------------------------------------------------------
     def _coerce_actions(self, actions, lead_shape, discrete):
         """-> float tensor [*lead_shape, 2]: a tensor is taken as it is, anything else goes through numpy; ONE action [2] is

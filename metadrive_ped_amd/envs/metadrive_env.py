@@ -237,6 +237,7 @@ class BatchedMetaDriveEnv(ObjectSpawnMixin, BatchedEnvBase):
         if draw_idx is not None and getattr(self.engine, "_staged", None) is not None and not self.engine.host.walk:
             self.engine.draw_idx.copy_(self.engine.torch.from_numpy(np.asarray(draw_idx, dtype=np.int32)))
         self.engine.upload_state(arrays)
+        self.engine.vector_obs_forget()     # a checkpoint does not carry the vector observation's history
         if self.engine.host.walk:     # the walk: each env's line map is its scene's
             self.engine.world_dev["env_map"].copy_(self.engine.state_dev["scene_of"])
 
