@@ -555,6 +555,9 @@ EXPORT float ref_ray_shape(float ox, float oy, float dx, float dy, const MdShape
 EXPORT int ref_obb_obb(const MdShape* a, const MdShape* b) {
     return md_obb_obb(a->cx, a->cy, a->c, a->s, a->hl, a->hw, b->cx, b->cy, b->c, b->s, b->hl, b->hw);
 }
+EXPORT int ref_obb_circle(const MdShape* a, float bx, float by, float r) {
+    return md_obb_circle(a->cx, a->cy, a->c, a->s, a->hl, a->hw, bx, by, r);
+}
 EXPORT int ref_obb_quad(const MdShape* a, const float* q) { return md_obb_quad(a->cx, a->cy, a->c, a->s, a->hl, a->hw, q); }
 /* st5 = x, y, psi, v, yaw increment per sub-step carried in from the step before */
 EXPORT void ref_bicycle(float* st4, float steer, float thr, const MdParam* P, float dt, int n) {

@@ -71,6 +71,8 @@ def load(path=None):
     lib.ref_ray_shape.argtypes = [f, f, f, f, C.c_void_p]
     lib.ref_obb_obb.restype = C.c_int
     lib.ref_obb_obb.argtypes = [C.c_void_p, C.c_void_p]
+    lib.ref_obb_circle.restype = C.c_int
+    lib.ref_obb_circle.argtypes = [C.c_void_p, f, f, f]
     lib.ref_obb_quad.restype = C.c_int
     lib.ref_obb_quad.argtypes = [C.c_void_p, C.c_void_p]
     lib.ref_bicycle.argtypes = [C.c_void_p, f, f, C.c_void_p, f, C.c_int]
