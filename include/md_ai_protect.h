@@ -3,7 +3,7 @@
  * EnvInputControl"): the PPO expert (include/md_expert.h) runs next to the agent's own action and overrides steering and / or
  * throttle when the vehicle is about to leave the road or to hit something, graded by config["save_level"]; every step reports
  * takeover / takeover_start / takeover_end.  With vehicle.expert_takeover set the expert drives outright (the branch of
- * ManualControlPolicy.act, policy/manual_control_policy.py:46-68).  Shared by the md_ai_protect kernel (mdstep.hip: the
+ * ManualControlPolicy.act, policy/manual_control_policy.py:46-68).  Shared by the md_ai_protect kernel (csrc/parts/expert.inc: the
  * epilogue of the expert's MLP, one thread per env) and the host restatement of the tests: the rule uses + - * /, md_fabs,
  * md_min and comparisons only, so a gcc -ffp-contract=off build reproduces the device bit for bit.
  *

@@ -14,7 +14,7 @@
  * (md_entity.h) advances the same pointers by the same extents; tests/test_branch.py holds the two together, and both lists
  * to the fields of MdState, so a field added later cannot be silently left out of a snapshot.
  *
- * The md_branch kernel (mdstep.hip: branch_kernel), the host build of the tests (tests/branch_host.c) and branch.py all walk
+ * The md_branch kernel (csrc/parts/branch.inc: branch_kernel), the host build of the tests (tests/branch_host.c) and branch.py all walk
  * this table.  What the engine owns outside MdState (MdWorld.env_map, the top-down history and image, the takeover bytes,
  * the staged-draw index) travels through MdBranch.extra: up to MD_BR_MAX_EXTRAS arrays of row_bytes bytes per env.
  */

@@ -1,7 +1,7 @@
 /*
  * md_expert.h -- the reference's PPO driving expert (metadrive/examples/ppo_expert/numpy_expert.py:34-77): a
  * 275 -> 256 -> 256 -> 4 tanh MLP on the LidarStateObservation of the agent, shared by the HIP kernel (md_expert in
- * mdstep.hip) and its host restatement (tests), so that the GPU result is reproducible on the host to the last bit.
+ * csrc/parts/expert.inc) and its host restatement (tests), so that the GPU result is reproducible on the host to the last bit.
  *
  * Reproducibility contract (what both builds compute, output element by output element):
  *   - every pre-activation is ONE k-ordered fmaf chain that starts from the bias:

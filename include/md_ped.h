@@ -2,7 +2,7 @@
  * md_ped.h -- crossing pedestrians driven on the device (config num_pedestrians; metadrive_ped_amd/scene.py places them,
  * BatchedEngine launches md_ped before every md_step).  No reference counterpart: the reference's pedestrians move with the
  * constant velocity the user set (tests/test_functionality/test_pedestrian.py); here a walker crosses its road back and forth,
- * waits at the kerb for a gap in the traffic and stops for a vehicle bearing down on it.  Shared by the kernel (mdstep.hip:
+ * waits at the kerb for a gap in the traffic and stops for a vehicle bearing down on it.  Shared by the kernel (csrc/parts/ped.inc:
  * ped_kernel) and the host restatement of the tests (tests/ped_host.c): float32, only + - * /, md_sqrt / md_norm / md_sincos of
  * md_math.h, no libm, so that a gcc -ffp-contract=off build reproduces the device bit for bit.
  *

@@ -6,7 +6,7 @@
  * out of it and, heading up, turns it with a bilinear rotozoom; its edges are anti-aliased by nothing and rounded by everything.
  * Built here is the GEOMETRY the reference draws, sampled exactly: one sample per pixel, at its centre.  Every rule below names the
  * reference's file and line.  Parity is pinned like md_topdown.h: this header is the single source of the md_render kernels
- * (mdstep.hip: tiled, primitive order, painter's order through ranks) and of the host build of the tests (tests/render_host.c: brute
+ * (csrc/parts/render.inc: tiled, primitive order, painter's order through ranks) and of the host build of the tests (tests/render_host.c: brute
  * force in pixel order); the rules use + - * /, comparisons and the shared md_math.h / md_geom.h formulas only, so a
  * gcc -ffp-contract=off build reproduces the device bit for bit.  Left out: the red dots the reference leaves where an agent
  * finished (:476-492); and heading up the whole window is sampled, where the reference turns a canvas that reaches 100 * sqrt(2) m

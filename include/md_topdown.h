@@ -6,7 +6,7 @@
  * What this is NOT: the reference's pixels.  There the image is a chain of pygame blits on a 2000 x 2000 canvas whose scale is
  * rounded per map, a bilinear rotozoom and a smoothscale; nobody can restate that bit for bit.  Built here is the GEOMETRY the
  * reference draws, sampled exactly; every rule below names the reference's file and line.  Parity is pinned like md_ai_protect.h:
- * this header is the single source of the md_topdown kernel (mdstep.hip, rasterised in primitive order) and of the host build
+ * this header is the single source of the md_topdown kernel (csrc/parts/topdown.inc, rasterised in primitive order) and of the host build
  * of the tests (tests/topdown_host.c, brute force in pixel order); the rules use + - * /, comparisons and the shared md_math.h /
  * md_geom.h formulas only, so a gcc -ffp-contract=off build reproduces the device bit for bit.
  *

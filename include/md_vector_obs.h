@@ -3,7 +3,7 @@
  * what VectorNet-style encoders and Waymax / nuPlan style planners read -- the K nearest movers with a short pose history, the
  * route ahead as waypoints and the nearby lane centre-lines as polylines, all in the observer's ego frame, in metres, not
  * normalised.  No reference counterpart: the reference observes through its lidar vector or a raster, and every number of this rule
- * (K, T, the radius, the jump bound, the spacings) is a design choice.  Shared by the kernel (mdstep.hip:
+ * (K, T, the radius, the jump bound, the spacings) is a design choice.  Shared by the kernel (csrc/parts/vector_obs.inc:
  * vector_obs_kernel) and the host build of the tests (tests/vector_obs_host.c): float32, only + - * /, comparisons and the
  * md_math.h / md_geom.h / md_entity.h functions, so that a gcc -ffp-contract=off build reproduces the device bit for bit.
  * md_vector_obs_env below states, as plain loops, what the kernel computes for one env.

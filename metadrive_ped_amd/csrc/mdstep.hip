@@ -3813,1514 +3813,26 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
     MD_STAMP_AT(11);
 }
 
-// Lidar.perceive as a sensor on its own (md_lidar_detect): cloud points AND the detected-object sets, from nothing but
-// the shape table.  One workgroup per env, shapes + sets in LDS, (agent, sector) items dealt to the waves.
-struct LidarDetectLds { uint32_t shape, det, bytes; };
-__host__ __device__ inline LidarDetectLds lidar_detect_lds(int cap, int agents) {
-    LidarDetectLds L;
-    L.shape = 0;                                                     // copy16
-    L.det = L.shape + (uint32_t)cap * sizeof(MdShape);                 // [agents][2] detected sets
-    L.bytes = L.det + (uint32_t)agents * 2 * sizeof(unsigned long long);
-    return L;
-}
-__global__ __launch_bounds__(256) void lidar_detect_kernel(MdWorld w, MdState g, MdConfig c, float* out, int out_stride, int out_offset,
-                                                          unsigned long long* detected) {
-    const int e = blockIdx.x;
-    if (e >= c.n_envs) return;
-    const int tid = threadIdx.x;
-    const LidarDetectLds L = lidar_detect_lds(c.cap, c.agents_per_env);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    MdShape* l_shape = reinterpret_cast<MdShape*>(smem + L.shape);
-    unsigned long long* l_det = reinterpret_cast<unsigned long long*>(smem + L.det);
-    copy16(l_shape, g.shape + (size_t)e * c.cap, c.cap * (int)sizeof(MdShape), tid, 256);
-    for (int j = tid; j < 2 * c.agents_per_env; j += 256) l_det[j] = 0ull;
-    __syncthreads();
-    MdState s = g;
-    s.shape = l_shape;
-    phase_lidar(w, s, c, e, tid, 4, out, out_stride, out_offset, l_det);
-    __syncthreads();
-    for (int j = tid; j < 2 * c.agents_per_env; j += 256) detected[(size_t)e * c.agents_per_env * 2 + j] = l_det[j];
-}
+}  // namespace
 
-// The move of an env onto a staged draw / pool scene: the snapshot rows and per-slot constants of live slots [row, + cap) from
-// staged slots [from, + cap), by threads tid of nthr (swap_draw_kernel, curriculum_kernel).
-__device__ void copy_draw_rows(const MdState& live, const MdState& staged, int cap, size_t row, size_t from, int tid, int nthr) {
-    auto words = [&](void* dst, const void* src, size_t elem_words) {   // cap slots of elem_words 4-byte words each
-        if (dst == nullptr || src == nullptr) return;
-        uint32_t* d = reinterpret_cast<uint32_t*>(dst) + row * elem_words;
-        const uint32_t* q = reinterpret_cast<const uint32_t*>(src) + from * elem_words;
-        for (size_t i = tid; i < (size_t)cap * elem_words; i += nthr) d[i] = q[i];
-    };
-    words(const_cast<MdShape*>(live.shape0), staged.shape0, sizeof(MdShape) / 4);
-    words(const_cast<MdDyn*>(live.dyn0), staged.dyn0, sizeof(MdDyn) / 4);
-    words(const_cast<MdNav*>(live.nav0), staged.nav0, sizeof(MdNav) / 4);
-    words(const_cast<MdPid*>(live.pid0), staged.pid0, sizeof(MdPid) / 4);
-    words(live.param, staged.param, sizeof(MdParam) / 4);
-    words(const_cast<MdParam*>(live.param0), staged.param, sizeof(MdParam) / 4);
-    words(live.route_nodes, staged.route_nodes, MD_ROUTE_LEN);
-    words(const_cast<int32_t*>(live.route_nodes0), staged.route_nodes, MD_ROUTE_LEN);
-    words(live.route_roads, staged.route_roads, MD_ROUTE_LEN);
-    words(const_cast<int32_t*>(live.route_roads0), staged.route_roads, MD_ROUTE_LEN);
-    words(live.final_lane, staged.final_lane, 1);
-    words(const_cast<int32_t*>(live.final_lane0), staged.final_lane, 1);
-    words(const_cast<int32_t*>(live.idm_rand), staged.idm_rand, MD_IDM_RAND);
-}
+// Everything above is the step path: the wave-level stages, the three step kernels and the sensors they share.  What follows
+// it is one part per side feature: kernel, LDS layout and, beside them, the extern "C" entry point with its argument checks;
+// entry_checks (host only) stands before them.  A part is included here and not compiled on its own; it opens its own namespace.
+#include "parts/entry_checks.inc" // host only: TRY / NEED, check_struct_size, check_common, need, the kNeeds table, need_fields, launch_status
+#include "parts/draws.inc"        // lidar_detect_kernel, swap_draw_kernel, curriculum_kernel; md_swap_draw, md_curriculum
+#include "parts/branch.inc"       // branch_kernel; md_branch (env snapshots)
+#include "parts/ped.inc"          // ped_kernel; md_ped (crossing pedestrians)
+#include "parts/vector_obs.inc"   // vector_obs_kernel; md_vector_obs
+#include "parts/others.inc"       // others_kernel: the observation's "others" block, launched by md_step
+#include "parts/expert.inc"       // expert_kernel, expert_sense_kernel, ai_protect_kernel; md_expert, md_ai_protect, md_expert_sense
+#include "parts/topdown.inc"      // topdown_kernel (its entry point md_topdown stays below: see DESIGN.md section 4)
+#include "parts/render.inc"       // render_push_kernel, render_kernel; md_render
 
-// random_traffic with auto-reset (PGTrafficManager with `random_traffic`: the traffic stream is not re-seeded at reset, every episode
-// sees other traffic, manager/traffic_manager.py:335-337): the caller stages n_draws host-built traffic draws on the device; an env
-// that has just finished its episode (need_reset != 0: md_step restores it from the snapshot at the NEXT step) takes the next draw --
-// the snapshot rows and the per-slot constants of the traffic (parameters, routes, pre-drawn lane-change timers) of that env are
-// replaced.  One workgroup per env, a no-op for the envs that go on.
-// The scenario walk (traffic_mode 4, MdState.walk.mode > 0) is the same move with the scenes for draws: `staged` holds the snapshot rows
-// of the n_draws = n_scenes scenes of the pool (scene p at p * cap), `draw_idx` is MdWorld.env_map (the scene's line map); the env
-// takes scene md_walk_scene(c, e, walk_ep[e] + 1) and scene_of / walk_ep / env_map follow.  The per-scene tables are only redirected.
-// The PG walk (traffic_mode 0 / 1 / 2 with MdState.walk.mode > 0) is that move over a pool of PG scenes: scene p = scenario seed
-// start_seed + p, env_map[e] = p picks its map, and the scene's traffic stream state (MdState.rng, the respawn modes) comes along
-// with the rows -- the reference re-seeds the traffic manager with the scenario seed at every reset.
-__global__ __launch_bounds__(256) void swap_draw_kernel(MdState live, MdState staged, MdConfig c, int n_draws, int32_t* draw_idx) {
-    const int e = blockIdx.x;
-    if (e >= c.n_envs || live.need_reset[e] == 0) return;   // block-uniform
-    const int tid = threadIdx.x;
-    const bool walk = live.walk.mode != 0;
-    const int ep = walk ? live.walk_ep[e] + 1 : 0;
-    const int k = walk ? md_walk_scene(&live.walk, e, ep) : (draw_idx[e] + 1) % n_draws;
-    __syncthreads();   // every thread has read the index
-    if (tid == 0) {
-        draw_idx[e] = k;
-        if (walk) {
-            live.scene_of[e] = k;
-            live.walk_ep[e] = ep;
-            if (live.rng && staged.rng) live.rng[e] = staged.rng[k];
-        }
-    }
-    const size_t row = (size_t)e * c.cap, from = walk ? (size_t)k * c.cap : ((size_t)k * c.n_envs + e) * c.cap;
-    copy_draw_rows(live, staged, c.cap, row, from, tid, 256);
-}
-
-// ScenarioEnv's curriculum manager (include/md_curriculum.h), one wave per env: lane 0 runs the env's state machine, and when the
-// env moves on (n_levels > 1) the whole wave copies the new scene's snapshot rows from the pool (`staged`, scene p at p * cap).
-// reset = 1: an env reset (every env restarts at its worker's first scene of its level; no report, no put).
-__global__ __launch_bounds__(64) void curriculum_kernel(MdState live, MdState staged, MdConfig c, MdCurriculum cu, int32_t* env_map,
-                                                        int reset) {
-    const int e = blockIdx.x;
-    if (e >= c.n_envs) return;
-    const int lane = threadIdx.x;
-    const bool moves = cu.n_levels > 1;
-    int p = -1;
-    if (lane == 0) {
-        const int follow = moves ? -1 : live.scene_of[e];   // one level: md_swap_draw has moved the env already
-        if (reset) {
-            p = md_cur_restart(&cu, e, follow);
-        } else {
-            const size_t a = (size_t)e * c.agents_per_env;
-            const int success = (live.flags[(size_t)e * c.cap] & MD_FL_ARRIVE_DEST) != 0;
-            p = md_cur_after_step(&cu, e, success, live.step_info[8 * a + 6], live.need_reset[e] != 0, follow);
-        }
-    }
-    p = __shfl(p, 0);
-    if (!moves || p < 0) return;   // wave-uniform
-    if (lane == 0) {
-        live.scene_of[e] = p;
-        live.walk_ep[e] = reset ? 0 : live.walk_ep[e] + 1;
-        env_map[e] = p;
-    }
-    copy_draw_rows(live, staged, c.cap, (size_t)e * c.cap, (size_t)p * c.cap, lane, 64);
-}
-
-// md_branch (include/md_branch.h): the copy of whole envs between two states, one workgroup per (source row, destination row) pair.
-// A pure gather-copy: the workgroup walks the table of per-env extents, then the extras.  Per field the row is moved with the widest
-// access both row bases and the length allow -- 16 bytes (the 32 / 64-byte records always), else 4 (an obs row of 259 floats is no
-// multiple of 16 bytes), else single bytes (the 1-byte extras) -- decided block-uniformly, and a thread issues up to four loads before
-// their stores, so that a field costs one memory round trip, not one per word.  A fan-out reads its one source row from L2.
-// No LDS, no atomics; the pairs never meet (the caller keeps destination rows distinct and apart from the source rows).
-template <typename T>
-__device__ __forceinline__ void branch_copy_as(char* d, const char* s, size_t n, int tid) {
-    T* dp = reinterpret_cast<T*>(d);
-    const T* sp = reinterpret_cast<const T*>(s);
-    for (size_t i = tid; i < n; i += 4 * 256) {
-        T v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            v[u] = T{};
-            if (i + u * 256 < n) v[u] = sp[i + u * 256];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if (i + u * 256 < n) dp[i + u * 256] = v[u];
-    }
-}
-
-// One copy of the three loops for all ~50 call sites (called, not inlined: the kernel stays a few KB of code instead of ~40).
-__device__ __noinline__ void branch_rows(void* dst, const void* src, size_t row_bytes, int srow, int drow, int tid) {
-    if (dst == nullptr || src == nullptr || row_bytes == 0) return;   // an array this batch does not have
-    const char* s = reinterpret_cast<const char*>(src) + (size_t)srow * row_bytes;
-    char* d = reinterpret_cast<char*>(dst) + (size_t)drow * row_bytes;
-    const uintptr_t bits = (uintptr_t)s | (uintptr_t)d | (uintptr_t)row_bytes;   // block-uniform
-    if ((bits & 15) == 0) branch_copy_as<md_u32x4>(d, s, row_bytes >> 4, tid);
-    else if ((bits & 3) == 0) branch_copy_as<uint32_t>(d, s, row_bytes >> 2, tid);
-    else branch_copy_as<uint8_t>(d, s, row_bytes, tid);
-}
-
-__global__ __launch_bounds__(256) void branch_kernel(MdState dst, MdState src, MdConfig c, MdBranch b) {
-    const int p = blockIdx.x;
-    if (p >= b.n_pairs) return;
-    const int srow = b.src_row[p], drow = b.dst_row[p];
-    if (srow < 0 || srow >= b.src_n_envs || drow < 0 || drow >= b.dst_n_envs) return;   // block-uniform; the host refuses such a pair
-    const int tid = threadIdx.x;
-#define MD_BR_COPY(field, unit, bytes, scale) \
-    branch_rows((void*)dst.field, (const void*)src.field, md_branch_row_bytes(&c, unit, bytes, scale), srow, drow, tid);
-    MD_BRANCH_FIELDS(MD_BR_COPY)
-#undef MD_BR_COPY
-#pragma unroll
-    for (int k = 0; k < MD_BR_MAX_EXTRAS; ++k)
-        if (k < b.n_extras) branch_rows(b.extra[k].dst, b.extra[k].src, (size_t)b.extra[k].row_bytes, srow, drow, tid);
-}
-
-// ---- crossing pedestrians (include/md_ped.h): ONE WAVE PER ENV, kPedEnvs envs per workgroup ----
-// The wave's lanes each load one mover's shape record and speed (two rounds when cap > 64); a lane whose mover is a policy-driven
-// pedestrian also loads that walker's nav / pid rows and keeps its crossing (md_ped_geom) in registers, so every global load of
-// the launch is issued in the first round trip.  A ballot finds the pedestrians; for each of them in slot order its crossing is
-// broadcast from the lane that owns it, every lane tests ITS vehicle(s) (md_ped_vehicle) and two ballots give the hold / yield
-// verdicts, which the owner keeps.  After the loop the owners evaluate the scalar part (md_ped_apply) side by side and store their
-// walkers' rows: the first version did that on lane 0 inside the loop, one dependent chain of loads per pedestrian (9.5 / 15.3 us
-// at 4096 envs x 4 / 8 pedestrians; EXPERIMENTS "Crossing pedestrians").  A pedestrian is no vehicle and reads no other
-// pedestrian, so the order of the stores does not matter.  No LDS, no atomics, plain vector stores.
-constexpr int kPedEnvs = 4;
-static_assert(MD_MAX_CAP <= 128, "ped_kernel: two lane rounds per env");
-__device__ __forceinline__ MdPedGeom bcast_ped_geom(const MdPedGeom& g, int src) {
-    MdPedGeom o;
-    o.ax = bcast_f(g.ax, src);
-    o.ay = bcast_f(g.ay, src);
-    o.ux = bcast_f(g.ux, src);
-    o.uy = bcast_f(g.uy, src);
-    o.L = bcast_f(g.L, src);
-    o.along = bcast_f(g.along, src);
-    o.dir = bcast_f(g.dir, src);
-    o.t_cross = bcast_f(g.t_cross, src);
-    return o;
-}
-
-__global__ __launch_bounds__(64 * kPedEnvs) void ped_kernel(MdState g, MdConfig c, MdPed p) {
-    const int lane = threadIdx.x & 63;
-    const int e = blockIdx.x * kPedEnvs + (threadIdx.x >> 6);
-    if (e >= c.n_envs) return;              // wave-uniform, as everything below that is not a lane's own mover
-    if (g.need_reset[e] != 0) return;       // md_step replaces this env's rows by the snapshot
-    const int cap = c.cap;
-    const size_t b = (size_t)e * (size_t)cap;
-    MdState s = g;                          // the env view of the arrays the rule touches
-    s.shape = g.shape + b;
-    s.dyn = g.dyn + b;
-    s.nav = g.nav + b;
-    s.pid = g.pid + b;
-    s.idm_rand = g.idm_rand + b * MD_IDM_RAND;
-    s.need_reset = g.need_reset + e;
-    MdShape vs[2] = {};
-    float vspeed[2] = {0.0f, 0.0f};
-    MdPedGeom mine[2] = {};                 // the crossing of this lane's own pedestrian
-    int verdict[2] = {0, 0};
-    unsigned long long peds[2] = {0ull, 0ull};
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        if (r * 64 >= cap) break;
-        const int j = r * 64 + lane;
-        bool driven = false;
-        if (j < cap) {
-            vs[r] = s.shape[j];
-            vspeed[r] = s.dyn[j].speed;
-            driven = md_ped_driven(vs[r].flags, &s.nav[j]);
-            if (driven) mine[r] = md_ped_geom(&vs[r], &s.nav[j], &s.pid[j], &p);
-        }
-        peds[r] = __ballot(driven);
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        unsigned long long m = peds[r];
-        while (m) {
-            const int k = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const MdPedGeom gm = bcast_ped_geom(mine[r], k);
-            int bits = md_ped_vehicle(&gm, &p, &vs[0], vspeed[0]);
-            if (cap > 64) bits |= md_ped_vehicle(&gm, &p, &vs[1], vspeed[1]);
-            const int hold = __ballot((bits & MD_PED_HOLD) != 0) != 0ull ? MD_PED_HOLD : 0;
-            const int yield = __ballot((bits & MD_PED_YIELD) != 0) != 0ull ? MD_PED_YIELD : 0;
-            if (lane == k) verdict[r] = hold | yield;
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-        if ((peds[r] >> lane) & 1ull) md_ped_apply(&s, &c, &p, r * 64 + lane, &mine[r], verdict[r]);
-}
-
-// ---- the vector scene observation (include/md_vector_obs.h): ONE WORKGROUP PER ENV, one wave per (observer, block) ----
-// The workgroup first pushes the env's frame into the history ring: every wave reads the cursor as the previous call left it,
-// a barrier, the threads store the slots of the newest frame and thread 0 the new cursor, a second barrier.  So the push happens
-// once per env and is ordered before every read of the ring.  Then the 3 * A work items (observer a, block: agents + ego | route |
-// lanes) are dealt to the waves -- a single-agent env keeps three waves busy, a 40-agent env loops.  Within a wave:
-//   agents  lanes take the slots (two per lane at cap > 64) and pack (float bits of d2) << 32 | slot: d2 >= 0, so the key orders
-//           as an unsigned integer and the slot breaks ties.  A candidate's rank is the number of candidates with a smaller key,
-//           counted over a ballot walk (the candidates inside the radius are few); ranks below K go to an LDS list.  The (K + 1) x T
-//           items (the ego is group K) are dealt to the lanes in whole groups of T: a lane evaluates ITS link and a ballot gives the
-//           prefix "links 0 .. t all hold" with one mask compare.
-//   route   lane i fetches the chain's i-th road, its chain lane and length (three dependent loads in all); the cumulative sum is
-//           the serial loop the header states, at most 47 additions over broadcast lengths, during which lane m keeps the first
-//           chain lane that reaches waypoint m; the M rows are then evaluated side by side.
-//   lanes   the candidate lanes are strided over the wave and their distances kept in LDS, so md_atan2 runs once per (observer,
-//           lane); a candidate's rank is counted over the LDS distances, ranks below P go to an LDS list, and the P x S points
-//           are dealt to the lanes.
-// No atomics, plain vector stores.
-constexpr int kVoWaves = 4;
-struct VectorObsLds { uint32_t sel, taken, dist, per_wave; };
-__host__ __device__ constexpr VectorObsLds vector_obs_lds(int max_lanes) {
-    const uint32_t taken = 4u * MD_VO_MAX_AGENTS, dist = taken + 4u * MD_VO_MAX_LANES;
-    return VectorObsLds{0u, taken, dist, align_up(dist + 4u * (uint32_t)(max_lanes > 0 ? max_lanes : 0), 16)};
-}
-__device__ __forceinline__ unsigned long long vo_key(float d, int id) {
-    return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(unsigned)id;
-}
-
-// the chain's roads, one per lane of the wave (lane i < *n_chain holds road i; -1 elsewhere)
-__device__ __forceinline__ int vo_chain_roads(const MdState& s, const MdObsCtx& k, int a, int lane, int* n_chain) {
-    const MdNav* nav = &s.nav[a];
-    int n = k.valid ? md_vo_chain_len(nav) : 0;
-    int road = -1;
-    if (lane < n) road = s.route_roads[(size_t)a * MD_ROUTE_LEN + nav->ck0 + lane];
-    const unsigned long long cut = __ballot(lane < n && road < 0);
-    if (cut) n = __ffsll((long long)cut) - 1;
-    *n_chain = n;
-    return lane < n ? road : -1;
-}
-
-__device__ __forceinline__ void vo_agents_block(const MdState& s, const MdConfig& c, const MdVectorObs& vo, const MdVoHist& h,
-                                                const MdObsCtx& k, const MdVoEgo& ego, const MdVoOut& o, int a, int lane, int* l_sel) {
-    const int K = vo.num_agents, T = vo.history, cap = c.cap;
-    const float radius2 = vo.radius * vo.radius, max_jump2 = vo.max_jump * vo.max_jump;
-    const MdShape me = s.shape[a];
-    unsigned long long key[2] = {~0ull, ~0ull};
-    bool cand[2] = {false, false};
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int j = r * 64 + lane;
-        if (k.valid && j < cap && j != a) {
-            const MdShape other = s.shape[j];
-            float d2;
-            cand[r] = md_vo_candidate(&me, &other, radius2, &d2);
-            key[r] = vo_key(d2, j);
-        }
-    }
-    if (lane < MD_VO_MAX_AGENTS) l_sel[lane] = -1;
-    int rank[2] = {0, 0};
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        unsigned long long m = __ballot(cand[q]);
-        while (m) {
-            const int l = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const unsigned long long kq = __shfl(key[q], l, 64);
-            rank[0] += kq < key[0];
-            rank[1] += kq < key[1];
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-        if (cand[r] && rank[r] < K) l_sel[rank[r]] = r * 64 + lane;
-    wave_lds_sync();
-    const int per = 64 / T;                 // whole groups of T items per round
-    for (int g0 = 0; g0 < K + 1; g0 += per) {
-        const int gi = lane / T, t = lane - gi * T, r = g0 + gi;
-        const bool act = gi < per && r <= K;
-        int j = -1;
-        if (act) j = r < K ? l_sel[r] : (k.valid ? a : -1);
-        const bool link = act && j >= 0 && md_vo_link(&h, max_jump2, j, t);
-        const unsigned long long links = __ballot(link);
-        if (act) {
-            const unsigned long long need = ((2ull << t) - 1ull) << (gi * T);    // links 0 .. t of this group
-            const int valid = (links & need) == need;
-            if (r < K) {
-                md_vo_agent_item(&h, &ego, &o, r, t, j, valid);
-                if (t == 0) md_vo_agent_meta(&s, &o, r, j);
-            } else {
-                md_vo_ego_item(&h, &ego, &o, t, j, valid);
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ void vo_route_block(const MdLane* lanes, const MdRoad* roads, const MdVectorObs& vo, const MdObsCtx& k,
-                                               const MdVoEgo& ego, const MdVoOut& o, int lane, int my_road, int n_chain) {
-    const int M = vo.route_points;
-    int my_lane = 0;
-    float my_len = 0.0f;
-    if (lane < n_chain) {
-        my_lane = md_vo_chain_lane(roads, my_road, k.rl->idx);
-        my_len = lanes[my_lane].length;
-    }
-    float cum = 0.0f;
-    if (n_chain > 0) cum = 0.0f - md_vo_chain_start(&lanes[bcast_i(my_lane, 0)], ego.cx, ego.cy);
-    const float d = md_vo_waypoint_d(&vo, lane);
-    int at = -1;
-    float lng = 0.0f;
-    for (int i = 0; i < n_chain; ++i) {       // serial, in the header's order: the sum is bit-exact
-        const float next = cum + bcast_f(my_len, i);
-        if (at < 0 && d <= next) {
-            at = i;
-            lng = d - cum;
-        }
-        cum = next;
-    }
-    const int at_lane = __shfl(my_lane, at < 0 ? 0 : at, 64);
-    if (lane < M) md_vo_route_item(&o, lane, at >= 0 ? &lanes[at_lane] : nullptr, lng, &ego);
-}
-
-__device__ __forceinline__ void vo_lanes_block(const MdLane* lanes, int n_lanes, const MdVectorObs& vo, const MdObsCtx& k,
-                                               const MdVoEgo& ego, const MdVoOut& o, int lane, int my_road, int n_chain, int* l_taken,
-                                               float* l_dist) {
-    const int P = vo.num_lanes, S = vo.lane_points;
-    if (lane < MD_VO_MAX_LANES) l_taken[lane] = -1;
-    if (k.valid)
-        for (int l = lane; l < n_lanes; l += 64) l_dist[l] = md_vo_lane_dist(&lanes[l], ego.cx, ego.cy);
-    wave_lds_sync();
-    if (k.valid)
-        for (int l = lane; l < n_lanes; l += 64) {
-            const unsigned long long mine = vo_key(l_dist[l], l);
-            int rank = 0;
-            for (int q = 0; q < n_lanes && rank < P; ++q) rank += vo_key(l_dist[q], q) < mine;
-            if (rank < P) l_taken[rank] = l;
-        }
-    wave_lds_sync();
-    for (int it = lane; it < P * S; it += 64) {
-        const int p = it / S, i = it - p * S;
-        const int tl = l_taken[p];
-        md_vo_lane_item(&o, S, p, i, tl >= 0 ? &lanes[tl] : nullptr, &ego);
-    }
-    const int tl = lane < P ? l_taken[lane] : -1;
-    const int road = tl >= 0 ? lanes[tl].road : -2;
-    int on_route = 0;
-    for (int i = 0; i < n_chain; ++i) on_route |= bcast_i(my_road, i) == road;
-    if (lane < P) md_vo_lane_meta(&o, lane, tl >= 0 ? &lanes[tl] : nullptr, on_route, tl >= 0 ? l_dist[tl] : 0.0f);
-}
-
-__global__ __launch_bounds__(64 * kVoWaves) void vector_obs_kernel(const MdWorld w, const MdState g, const MdConfig c, const MdVectorObs vo) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int e = blockIdx.x;                       // the grid is n_envs workgroups
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
-    const VectorObsLds LD = vector_obs_lds(w.max_lanes);
-    unsigned char* base = smem + wave * LD.per_wave;
-    int* l_sel = reinterpret_cast<int*>(base + LD.sel);
-    int* l_taken = reinterpret_cast<int*>(base + LD.taken);
-    float* l_dist = reinterpret_cast<float*>(base + LD.dist);
-    const MdState s = md_env_view(&g, &c, e);
-    const int clock = md_rd_clock(&g, &c, e, &s.nav[0]);
-    const MdVoHist h = md_vo_hist_of(&vo, &c, e, clock);   // the cursor as the previous call left it, advanced in registers
-    __syncthreads();                                       // ... by every wave, before it is rewritten
-    for (int j = tid; j < c.cap; j += blockDim.x) md_vo_push_slot(&h, j, &s.shape[j]);
-    if (tid == 0) md_vo_push_cursor(&h, clock);
-    __threadfence_block();
-    __syncthreads();                                       // the newest frame is in the ring for every wave of the env
-    const int m = w.env_map[e];
-    const MdLane* lanes = w.lanes + w.lane_off[m];
-    const MdRoad* roads = w.roads + w.road_off[m];
-    const int map_lanes = w.lane_off[m + 1] - w.lane_off[m];
-    const int n_lanes = map_lanes < w.max_lanes ? map_lanes : w.max_lanes;     // l_dist holds max_lanes entries
-    for (int item = wave; item < 3 * c.agents_per_env; item += n_waves) {   // wave-uniform
-        const int a = item / 3, block = item - 3 * a;
-        const MdVoOut o = md_vo_out_of(&vo, e, a);
-        MdObsCtx k;
-        md_observe_ctx(lanes, roads, &s, a, &k);
-        const MdVoEgo ego = {s.shape[a].cx, s.shape[a].cy, s.shape[a].c, s.shape[a].s};
-        if (block == 0) {
-            vo_agents_block(s, c, vo, h, k, ego, o, a, lane, l_sel);
-        } else if ((block == 1 && vo.route_points > 0) || (block == 2 && vo.num_lanes > 0)) {
-            int n_chain;
-            const int my_road = vo_chain_roads(s, k, a, lane, &n_chain);
-            if (block == 1) vo_route_block(lanes, roads, vo, k, ego, o, lane, my_road, n_chain);
-            else vo_lanes_block(lanes, n_lanes, vo, k, ego, o, lane, my_road, n_chain, l_taken, l_dist);
-        }
-        wave_lds_sync();                                   // the lists are reused by the wave's next item
-    }
-}
-
-// "Others" block of the observation (Lidar.get_surrounding_vehicles_info): one thread per agent, after the
-// step kernel has written the detected sets and the new state back.  Off in the headline configs.
-__global__ __launch_bounds__(64) void others_kernel(MdWorld w, MdState g, MdConfig c) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= c.n_envs * c.agents_per_env) return;
-    const int e = i / c.agents_per_env, a = i - e * c.agents_per_env;
-    const MdState s = md_env_view(&g, &c, e);
-    const int m = w.env_map[e];
-    md_others_block(w.lanes + w.lane_off[m], w.roads + w.road_off[m], &s, &c, a, s.detected[2 * a], s.detected[2 * a + 1],
-                    s.obs + (size_t)a * c.obs_dim + md_obs_others(&c));
-}
-
-// ----------------------------------------------------------------------------------------------------------------------------
-// md_expert: the PPO expert (numpy_expert.py:34-77) over the batch.  One workgroup of 4 waves per tile of 16 envs:
-//   1. x = the expert's 275-vector of each env in LDS (the env's obs row + the "others" block of md_others_block with
-//      num_others = 4), corrected; rows past the last env stay zero and are never written out;
-//   2. h1 = tanh(x W1 + b1), h2 = tanh(h1 W2 + b2): wave w owns the output columns [64w, 64w + 64) as four 16x16 tiles,
-//      every tile ONE accumulator chained over the k-steps in order (A = 16 env rows from LDS, B = one 16-byte load per
-//      lane per four k-steps from the packed weights, which stay in L2), bias as the accumulator's start value;
-//   3. out = h2 W3 + b3 on wave 0 (one tile, N padded to 16), then mean / log_std / action.
-// Each output element is the k-ordered fmaf chain of include/md_expert.h: v_mfma_f32_16x16x4_f32 rounds once per product
-// in k order, and nothing else touches the accumulator.
-constexpr int kExpM = 16;                                  // envs per workgroup (the MFMA's M)
-constexpr int kExpXS = MD_EXPERT_IN_PAD + 4;               // LDS row strides: = 4 mod 32, so the 16 rows x 4 k of one
-constexpr int kExpHS = MD_EXPERT_HID + 4;                  //   A-operand read spread over the banks
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// acc[j] (+)= A[16 rows][K] . W[K][tile nt0 + j], j < NT; A row r at a + r * lda, W packed (md_expert_widx)
-template <int NT>
-__device__ __forceinline__ void expert_tiles(const float* __restrict__ W, int K, int nt0, const float* a, int lda, int lane,
-                                             f32x4* acc) {
-    const int G = K >> 4;
-    const float* arow = a + (lane & 15) * lda + (lane >> 4);
-    const f32x4* wp[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) wp[j] = reinterpret_cast<const f32x4*>(W + (size_t)(nt0 + j) * G * 256) + lane;
-    f32x4 cur[NT], nxt[NT];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) cur[j] = wp[j][0];
-    for (int g = 0; g < G; ++g) {
-        if (g + 1 < G) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) nxt[j] = wp[j][(size_t)(g + 1) * 64];
-        }
-#pragma unroll
-        for (int st = 0; st < 4; ++st) {
-            const float av = arow[16 * g + 4 * st];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, cur[j][st], acc[j], 0, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < NT; ++j) cur[j] = nxt[j];
-    }
-}
-
-// one hidden layer: out[r][n] = tanh(in[r] . W[:, n] + b[n]) for the 64 columns of this wave
-__device__ __forceinline__ void expert_hidden(const float* __restrict__ W, const float* __restrict__ b, int K, const float* in,
-                                              int lds_in, float* out, int wave, int lane) {
-    f32x4 acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float bv = b[(4 * wave + j) * 16 + (lane & 15)];
-        acc[j] = f32x4{bv, bv, bv, bv};
-    }
-    expert_tiles<4>(W, K, 4 * wave, in, lds_in, lane, acc);
-    // C/D layout of the 16x16 MFMAs: column = lane & 15, row = (lane >> 4) * 4 + register
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) out[((lane >> 4) * 4 + r) * kExpHS + (4 * wave + j) * 16 + (lane & 15)] = md_tanh(acc[j][r]);
-}
-
-// Stage 1 of md_expert for the tile of envs [e0, e0 + n_here): x from the env's obs row (state 19 | cloud 240) and the "others"
-// block of md_others_block on the env's detected sets, corrected, in l_x [kExpM * kExpXS]; behind a barrier.
-__device__ __forceinline__ void expert_fill_x(const MdWorld& w, const MdState& g, const MdConfig& c, float* l_x, int e0, int n_here) {
-    const int tid = threadIdx.x;
-    const int od = c.obs_dim;   // 259: state 19 | cloud 240
-    for (int i = tid; i < kExpM * kExpXS; i += 256) {
-        const int r = i / kExpXS, k = i - r * kExpXS;
-        float v = 0.0f;
-        if (r < n_here && k < MD_EXPERT_IN) {
-            const float* o = g.obs + (size_t)(e0 + r) * od;
-            if (k < MD_EXPERT_STATE) v = o[k];
-            else if (k >= MD_EXPERT_STATE + 4 * MD_EXPERT_OTHERS) v = o[k - 4 * MD_EXPERT_OTHERS];
-        }
-        l_x[i] = v;
-    }
-    __syncthreads();
-    if (tid < n_here) {
-        MdConfig cc = c;                          // the expert's lidar: num_others = 4, no navigation dims of the others
-        cc.num_others = MD_EXPERT_OTHERS;
-        cc.add_others_navi = 0;
-        const int e = e0 + tid;
-        const MdState s = md_env_view(&g, &c, e);
-        const int m = w.env_map[e];
-        float* x = l_x + tid * kExpXS;
-        md_others_block(w.lanes + w.lane_off[m], w.roads + w.road_off[m], &s, &cc, 0, s.detected[0], s.detected[1],
-                        x + MD_EXPERT_STATE);
-        md_expert_correct(x);
-    }
-    __syncthreads();
-}
-
-// Stages 2-3 for the tile of rows [row0, row0 + n_here) whose x stands in l_x (expert_fill_x, or md_expert_sense's own): obs_out rows,
-// then the MLP; leaves mean | log_std of row r in l_out[r * MD_EXPERT_OUT ...], behind a barrier.
-// l_x [kExpM * kExpXS] (x; later h2 at stride kExpHS), l_h [kExpM * kExpHS] (h1) and l_out are the calling kernel's LDS.
-__device__ __forceinline__ void expert_tile_forward(const float* __restrict__ wts, float* __restrict__ obs_out, float* l_x, float* l_h,
-                                                    float* l_out, int row0, int n_here) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    if (obs_out)
-        for (int i = tid; i < n_here * MD_EXPERT_IN; i += 256) {
-            const int r = i / MD_EXPERT_IN, k = i - r * MD_EXPERT_IN;
-            obs_out[(size_t)row0 * MD_EXPERT_IN + i] = l_x[r * kExpXS + k];
-        }
-    // 2. hidden layers
-    expert_hidden(wts + MD_EXPERT_W1, wts + MD_EXPERT_B1, MD_EXPERT_IN_PAD, l_x, kExpXS, l_h, wave, lane);
-    __syncthreads();
-    expert_hidden(wts + MD_EXPERT_W2, wts + MD_EXPERT_B2, MD_EXPERT_HID, l_h, kExpHS, l_x, wave, lane);
-    __syncthreads();
-    // 3. output layer (one 16x16 tile; columns 4..15 are zero padding)
-    if (wave == 0) {
-        const float bv = wts[MD_EXPERT_B3 + (lane & 15)];
-        f32x4 acc[1] = {f32x4{bv, bv, bv, bv}};
-        expert_tiles<1>(wts + MD_EXPERT_W3, MD_EXPERT_HID, 0, l_x, kExpHS, lane, acc);
-        if ((lane & 15) < MD_EXPERT_OUT)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) l_out[((lane >> 4) * 4 + r) * MD_EXPERT_OUT + (lane & 15)] = acc[0][r];
-    }
-    __syncthreads();
-}
-
-// The tile's results from l_out: mlp_out rows and the action (mean, or the draw with `noise`) of rows [row0, row0 + n_here).  Rows
-// whose bit in `skip` is set (md_expert_sense: rows that were not sensed) get zeros.
-__device__ __forceinline__ void expert_tile_emit(const float* l_out, const float* __restrict__ noise, float* __restrict__ action_out,
-                                                 float* __restrict__ mlp_out, int row0, int n_here, unsigned skip) {
-    const int tid = threadIdx.x;
-    if (tid < n_here * MD_EXPERT_OUT) {
-        const int r = tid >> 2, q = tid & 3;
-        const size_t e = (size_t)(row0 + r);
-        const bool off = ((skip >> r) & 1u) != 0u;
-        if (mlp_out) mlp_out[e * MD_EXPERT_OUT + q] = off ? 0.0f : l_out[tid];
-        if (q < 2) {
-            const float mean = l_out[r * MD_EXPERT_OUT + q];
-            const float act = noise ? md_expert_sample(mean, l_out[r * MD_EXPERT_OUT + 2 + q], noise[e * 2 + q]) : mean;
-            action_out[e * 2 + q] = off ? 0.0f : act;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void expert_kernel(MdWorld w, MdState g, MdConfig c, const float* __restrict__ wts,
-                                                     const float* __restrict__ noise, float* __restrict__ action_out,
-                                                     float* __restrict__ mlp_out, float* __restrict__ obs_out) {
-    __shared__ __attribute__((aligned(16))) float l_x[kExpM * kExpXS];   // x; later h2 (stride kExpHS)
-    __shared__ __attribute__((aligned(16))) float l_h[kExpM * kExpHS];   // h1
-    __shared__ float l_out[kExpM * MD_EXPERT_OUT];
-    const int tid = threadIdx.x;
-    const int e0 = blockIdx.x * kExpM;
-    const int n_here = min(kExpM, c.n_envs - e0);
-    expert_fill_x(w, g, c, l_x, e0, n_here);
-    expert_tile_forward(wts, obs_out, l_x, l_h, l_out, e0, n_here);
-    expert_tile_emit(l_out, noise, action_out, mlp_out, e0, n_here, 0u);
-}
-
-// md_expert_sense (include/md_expert_sense.h): the expert observes for itself.  Tile of kExpM rows, row i = agent i % A of env i / A.
-//   1. wave w, 16-lane group q: the state dims of row 4 w + q (md_observe_ctx, the six tasks the obs dims read on lanes of the group,
-//      md_observe_state_dims on its lane 0) into the row in LDS;
-//   2. the 16 rows x 4 sectors of the 240-beam cast by LDS ticket: lidar_item against the env's shape table, cloud straight into the
-//      row, the detected set into the row's two LDS words;
-//   3. behind a barrier, one thread per row: md_others_block on the row's own set, md_expert_correct;
-//   4. expert_tile_forward / expert_tile_emit, as expert_kernel.
-// The shape tables are read through L2, not staged: the 16 rows of a single-agent tile belong to 16 envs, and 16 tables of up to 128
-// slots x 32 B (64 KB) cannot stand in LDS beside x and h1; a row's four sectors read the same 4 KB at most, which stays in L2 / the
-// vector cache between them.  Static LDS: x 18.3 KB + h1 16.3 KB + 3 KB of task results + 0.6 KB = 38.3 KB at every capacity.
-// Rows of an env with need_reset != 0 and rows past the last stay zero in LDS and are written out as zeros (expert_tile_emit).
-__global__ __launch_bounds__(256) void expert_sense_kernel(MdWorld w, MdState g, MdConfig c, const float* __restrict__ wts,
-                                                           const float* __restrict__ beam_cs240, const float* __restrict__ noise,
-                                                           float* __restrict__ action_out, float* __restrict__ mlp_out,
-                                                           float* __restrict__ obs_out) {
-    __shared__ __attribute__((aligned(16))) float l_x[kExpM * kExpXS];
-    __shared__ __attribute__((aligned(16))) float l_h[kExpM * kExpHS];
-    __shared__ float l_out[kExpM * MD_EXPERT_OUT];
-    __shared__ float l_task[kExpM * 48];                 // MD_OBS_TASKS * 5 (= 45) task results per row, padded
-    __shared__ unsigned long long l_det[kExpM * 2];      // the rows' detected sets
-    __shared__ int l_env[kExpM];                         // the row's env, -1 = not sensed
-    __shared__ int l_tk;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int A = c.agents_per_env;
-    const int rows = c.n_envs * A;
-    const int row0 = blockIdx.x * kExpM;
-    const int n_here = min(kExpM, rows - row0);
-    // the expert's sensor config (numpy_expert.py:39-46) over the env's
-    c.n_beams = MD_EXPERT_BEAMS;
-    c.lidar_range = MD_EXPERT_RANGE;
-    c.n_side = 0;
-    c.n_lane_line = 0;
-    c.random_agent_model = 0;
-    c.num_others = MD_EXPERT_OTHERS;
-    c.add_others_navi = 0;
-    c.obs_dim = MD_EXPERT_IN;
-    w.beam_cs = beam_cs240;
-    for (int i = tid; i < kExpM * kExpXS; i += 256) l_x[i] = 0.0f;
-    if (tid < kExpM) {
-        int e = -1;
-        if (tid < n_here) {
-            e = (row0 + tid) / A;
-            if (g.need_reset[e] != 0) e = -1;
-        }
-        l_env[tid] = e;
-        l_det[2 * tid] = 0ull;
-        l_det[2 * tid + 1] = 0ull;
-    }
-    if (tid == 0) l_tk = 0;
-    __syncthreads();
-    // the slices of env e that the sensors read (md_env_view without the arrays nothing here touches)
-    auto view_of = [&](int e) {
-        MdState s = g;
-        const size_t b = (size_t)e * (size_t)c.cap;
-        s.shape = g.shape + b;
-        s.dyn = g.dyn + b;
-        s.param = g.param + b;
-        s.nav = g.nav + b;
-        s.action = g.action + 2 * b;
-        s.final_lane = g.final_lane + b;
-        return s;
-    };
-    unsigned skip = 0u;
-#pragma unroll
-    for (int r = 0; r < kExpM; ++r) skip |= (l_env[r] < 0 ? 1u : 0u) << r;
-    // 1. state dims
-    {
-        const int q = lane >> 4, sub = lane & 15;
-        const int r = 4 * wave + q;
-        const int e = l_env[r];
-        float* scratch = l_task + r * 48;
-        MdObsCtx k;
-        MdState s = g;
-        int a = 0;
-        if (e >= 0) {
-            a = row0 + r - e * A;
-            s = view_of(e);
-            const int m = w.env_map[e];
-            md_observe_ctx(w.lanes + w.lane_off[m], w.roads + w.road_off[m], &s, a, &k);
-            if (sub < 5 || sub == 8) {     // the tasks whose results the obs dims read
-                float mine[5];
-                md_observe_task(sub, &k, &s, &c, a, mine);
-#pragma unroll
-                for (int i = 0; i < 5; ++i) scratch[sub * 5 + i] = mine[i];
-            }
-        }
-        wave_lds_sync();
-        // a slot without a driving agent keeps its zeros
-        if (e >= 0 && sub == 0 && k.valid) md_observe_state_dims(&k, &s, &c, a, (const float (*)[5])scratch, l_x + r * kExpXS);
-    }
-    // 2. cloud and detected sets
-    constexpr int kSectors = (MD_EXPERT_BEAMS + 63) / 64;
-    for (int guard = 0; guard < kExpM * kSectors; ++guard) {
-        int it = 0;
-        if (lane == 0) it = atomicAdd(&l_tk, 1);
-        it = __builtin_amdgcn_readfirstlane(it);
-        if (it < 0 || it >= kExpM * kSectors) break;
-        const int r = it / kSectors, sec = it - r * kSectors;
-        const int e = l_env[r];
-        if (e < 0) continue;
-        MdState s = g;
-        s.shape = g.shape + (size_t)e * (size_t)c.cap;
-        lidar_item<true>(w, s, c, row0 + r - e * A, sec, lane, l_x + r * kExpXS + MD_EXPERT_STATE + 4 * MD_EXPERT_OTHERS, l_det + 2 * r);
-    }
-    __syncthreads();
-    // 3. others, correction: row r on lane 0 of its 16-lane group
-    if ((tid & 15) == 0) {
-        const int r = tid >> 4;
-        const int e = l_env[r];
-        if (e >= 0) {
-            const MdState s = view_of(e);
-            const int m = w.env_map[e];
-            float* x = l_x + r * kExpXS;
-            md_others_block(w.lanes + w.lane_off[m], w.roads + w.road_off[m], &s, &c, row0 + r - e * A, l_det[2 * r], l_det[2 * r + 1],
-                            x + MD_EXPERT_STATE);
-            md_expert_correct(x);
-        }
-    }
-    __syncthreads();
-    expert_tile_forward(wts, obs_out, l_x, l_h, l_out, row0, n_here);
-    expert_tile_emit(l_out, noise, action_out, mlp_out, row0, n_here, skip);
-}
-
-// md_ai_protect: AIProtectPolicy (include/md_ai_protect.h) in one launch.  The expert's draw exactly as expert_kernel computes it (the
-// same tile, the same chains), then the rule as an epilogue, one thread per env: obs[0], obs[1] and the four lidar windows come from
-// the env's obs row in HBM (l_x holds h2 by now), speed / heading / lane from the env's state and the map tables.  No LDS beyond
-// expert_kernel's.
-__global__ __launch_bounds__(256) void ai_protect_kernel(MdWorld w, MdState g, MdConfig c, const float* __restrict__ wts,
-                                                         const float* __restrict__ noise, const float* __restrict__ actions,
-                                                         float save_level, unsigned char* __restrict__ takeover,
-                                                         unsigned char* __restrict__ expert_takeover, float* __restrict__ applied_out,
-                                                         unsigned char* __restrict__ flags_out, float* __restrict__ saver_out) {
-    __shared__ __attribute__((aligned(16))) float l_x[kExpM * kExpXS];
-    __shared__ __attribute__((aligned(16))) float l_h[kExpM * kExpHS];
-    __shared__ float l_out[kExpM * MD_EXPERT_OUT];
-    const int tid = threadIdx.x;
-    const int e0 = blockIdx.x * kExpM;
-    const int n_here = min(kExpM, c.n_envs - e0);
-    expert_fill_x(w, g, c, l_x, e0, n_here);
-    expert_tile_forward(wts, nullptr, l_x, l_h, l_out, e0, n_here);
-    if (tid >= n_here) return;
-    const int e = e0 + tid;
-    const float* o4 = l_out + tid * MD_EXPERT_OUT;
-    float sv[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) sv[q] = noise ? md_expert_sample(o4[q], o4[2 + q], noise[(size_t)e * 2 + q]) : o4[q];
-    if (saver_out) {
-        saver_out[(size_t)e * 2] = sv[0];
-        saver_out[(size_t)e * 2 + 1] = sv[1];
-    }
-    const float raw[2] = {actions[(size_t)e * 2], actions[(size_t)e * 2 + 1]};
-    float applied[2];
-    unsigned char tk = takeover[e], et = expert_takeover[e];
-    unsigned fl;
-    if (g.need_reset[e] != 0) {
-        fl = md_ai_protect_reset(raw, &tk, &et, applied);
-    } else {
-        const MdState s = md_env_view(&g, &c, e);
-        MdProtectIn in;
-        md_ai_protect_inputs(w.lanes + w.lane_off[w.env_map[e]], &s, &c, &in);
-        fl = md_ai_protect_act(raw, sv, &in, save_level, et != 0, &tk, applied);
-    }
-    takeover[e] = tk;
-    expert_takeover[e] = et;
-    applied_out[(size_t)e * 2] = applied[0];
-    applied_out[(size_t)e * 2 + 1] = applied[1];
-    flags_out[e] = (unsigned char)fl;
-}
-
-// ---- md_topdown (include/md_topdown.h): the top-down observation, one workgroup per env -------------------------------------
-// Rasterised in PRIMITIVE order into an LDS image: every route lane, line piece and mover that survives its cull touches only the
-// pixels of its own bounding box in the image.  The road plane holds one byte per pixel, two bits per sub-sample (bit 0: on a
-// route lane, bit 1: on a line, which wins), so that navigation and lines are set with ds_or and need no order between them; the
-// traffic and past_pos planes hold one bit per pixel.  The epilogue composes the env's R x R x C block and writes it with 16-byte
-// non-temporal stores wherever the block is 16-byte aligned.
-// Diagnostic builds only (tools/topdown_bench.py under MD_LIB_PATH): phases of topdown_kernel left out, each by one #if around it,
-// to read their cost off the launch time (1 route lanes, 2 line pieces, 4 movers, 8 compose + write).  0 in the product.
-#ifndef MD_TD_SKIP
-#define MD_TD_SKIP 0
-#endif
-struct TopdownLds { uint32_t road, traffic, past, queue, pieces, stage, bytes; };
-constexpr int kTdQueue = 128;     // pixels a wave keeps between its cull and its exact test (two passes' worth)
-// `staged`: the older traffic frames (frame_stack - 1 of them) the epilogue reads, copied into LDS first
-__host__ __device__ constexpr TopdownLds topdown_lds(int R, int staged) {
-    // a plane is R * ceil(R / 32) words, an odd count for many an odd R: rounded up so that every part below starts on 16 bytes
-    // (the piece lists are written with 16-byte LDS stores)
-    const uint32_t plane = align_up((uint32_t)R * (uint32_t)MD_TD_ROW_WORDS(R) * 4u, 16);
-    const uint32_t traffic = align_up((uint32_t)R * (uint32_t)R, 16);
-    const uint32_t queue = traffic + 2u * plane, pieces = queue + 4u * kTdQueue * 2u, stage = pieces + 4u * 64u * 32u;
-    return TopdownLds{0u, traffic, traffic + plane, queue, pieces, stage, stage + (uint32_t)staged * plane};
-}
-// the older frames are staged while the image fits the 64 KB of LDS a launch may ask for without more ado; beyond (R and
-// frame_stack both near their limits) the epilogue reads them from the ring
-__host__ __device__ constexpr int topdown_staged(int R, int frame_stack) {
-    return topdown_lds(R, frame_stack - 1).bytes <= 64u * 1024u ? frame_stack - 1 : 0;
-}
-
-struct TdView { float px, py, hc, hs, m, inv_m, half; int R; };
-struct TdBox { int r0, c0, w, h; };
-
-// the pixels that can hold a sample of the convex hull of the four world points xy, grown by `grow` pixels
-__device__ __forceinline__ TdBox td_bbox(const TdView& v, const float* xy, int grow) {
-    float rmin = 3.0e38f, rmax = -3.0e38f, cmin = 3.0e38f, cmax = -3.0e38f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float dx = xy[2 * i] - v.px, dy = xy[2 * i + 1] - v.py;
-        const float fr = v.half - (dx * v.hc + dy * v.hs) * v.inv_m;
-        const float fc = v.half - (dy * v.hc - dx * v.hs) * v.inv_m;
-        rmin = md_min(rmin, fr); rmax = md_max(rmax, fr);
-        cmin = md_min(cmin, fc); cmax = md_max(cmax, fc);
-    }
-    const float lo = -8.0f, hi = (float)v.R + 8.0f;     // keeps the conversions to int in range (NaN -> lo)
-    const int r0 = (int)md_floor(md_clip(rmin, lo, hi)) - grow, r1 = (int)md_floor(md_clip(rmax, lo, hi)) + grow;
-    const int c0 = (int)md_floor(md_clip(cmin, lo, hi)) - grow, c1 = (int)md_floor(md_clip(cmax, lo, hi)) + grow;
-    TdBox b;
-    b.r0 = r0 < 0 ? 0 : r0;
-    b.c0 = c0 < 0 ? 0 : c0;
-    const int r1c = r1 > v.R - 1 ? v.R - 1 : r1, c1c = c1 > v.R - 1 ? v.R - 1 : c1;
-    b.h = r1c >= b.r0 ? r1c - b.r0 + 1 : 0;
-    b.w = c1c >= b.c0 ? c1c - b.c0 + 1 : 0;
-    return b;
-}
-
-// One wave: the four sub-samples of every pixel of `b` against test(x, y); hits are OR-ed into the road plane as `code`.  The
-// pixels first pass near(x, y) of their CENTRE -- a cheap conservative test: it may only reject a pixel none of whose samples (at
-// most 0.36 m pixels from the centre) can hit -- and the survivors are compacted through the wave's `queue`, so that the exact
-// test runs on full waves: a curved lane's bounding box is mostly empty.
-template <typename Near, typename Test>
-__device__ __forceinline__ void td_raster_road(const TdView& v, const TdBox& b, uint32_t* road, unsigned code, int lane_id, uint16_t* queue,
-                                               Near near, Test test) {
-    const int n = b.w * b.h;
-    auto exact = [&](int p, int r, int cc) {
-        unsigned bits = 0u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float x, y;
-            md_td_window(v.px, v.py, v.hc, v.hs, v.R, v.m, (float)r + 0.25f + 0.5f * (float)(k >> 1), (float)cc + 0.25f + 0.5f * (float)(k & 1), &x, &y);
-            if (test(x, y)) bits |= code << (2 * k);
-        }
-        if (bits) atomicOr(&road[p >> 2], bits << (8 * (p & 3)));
-    };
-    if (n <= 64) {      // one pass: no compaction to gain
-        if (lane_id < n) {
-            const int dr = lane_id / b.w;
-            const int r = b.r0 + dr, cc = b.c0 + (lane_id - dr * b.w);
-            exact(r * v.R + cc, r, cc);
-        }
-        return;
-    }
-    int qn = 0;
-    for (int base = 0; base < n; base += 64) {
-        const int idx = base + lane_id;
-        bool keep = false;
-        int pix = 0;
-        if (idx < n) {
-            const int dr = idx / b.w;
-            const int r = b.r0 + dr, cc = b.c0 + (idx - dr * b.w);
-            float x, y;
-            md_td_window(v.px, v.py, v.hc, v.hs, v.R, v.m, (float)r + 0.5f, (float)cc + 0.5f, &x, &y);
-            keep = near(x, y);
-            pix = r * v.R + cc;
-        }
-        const unsigned long long mask = __ballot(keep);
-        if (keep) queue[qn + __popcll(mask & ((1ull << lane_id) - 1ull))] = (uint16_t)pix;
-        qn += __popcll(mask);
-        const bool last = base + 64 >= n;
-        while (qn >= 64 || (last && qn > 0)) {
-            wave_lds_sync();
-            const int take = qn < 64 ? qn : 64;
-            if (lane_id < take) {
-                const int p = queue[qn - take + lane_id];
-                const int r = p / v.R;
-                exact(p, r, p - r * v.R);
-            }
-            qn -= take;
-            wave_lds_sync();
-        }
-    }
-}
-
-template <bool NORM>
-__global__ __launch_bounds__(256) void topdown_kernel(const MdWorld w, const MdState g, const MdConfig c, const MdTopDown td, const int vec) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int e = blockIdx.x, tid = threadIdx.x, lane_id = tid & 63, wave = tid >> 6;
-    const int R = td.resolution, wpr = MD_TD_ROW_WORDS(R), FW = R * wpr;
-    const int staged = topdown_staged(R, td.frame_stack);
-    const TopdownLds lds = topdown_lds(R, staged);
-    uint32_t* road = reinterpret_cast<uint32_t*>(smem + lds.road);
-    uint32_t* traffic = reinterpret_cast<uint32_t*>(smem + lds.traffic);
-    uint32_t* past = reinterpret_cast<uint32_t*>(smem + lds.past);
-    uint16_t* queue = reinterpret_cast<uint16_t*>(smem + lds.queue) + wave * kTdQueue;
-    float* pieces = reinterpret_cast<float*>(smem + lds.pieces) + wave * 64 * 8;
-    uint32_t* stage = reinterpret_cast<uint32_t*>(smem + lds.stage);
-    for (int i = tid; i < (int)(lds.queue >> 2); i += 256) road[i] = 0u;
-
-    const size_t b0 = (size_t)e * (size_t)c.cap;
-    const MdShape ego = g.shape[b0];
-    const MdNav nav0 = g.nav[b0];
-    const bool reset = md_td_is_reset(&nav0);
-    const int Lt = md_td_ring_len(td.frame_stack, td.frame_skip), Lp = md_td_ring_len(td.post_stack, td.frame_skip);
-    int* cursor = td.cursor + 4 * (size_t)e;
-    // the cursors as the previous launch left them (sanitised: they index the rings)
-    const int tcur_old = (int)((unsigned)cursor[0] % (unsigned)Lt), pcur_old = (int)((unsigned)cursor[1] % (unsigned)Lp);
-    const int pcnt_old = cursor[2] < 0 ? 0 : (cursor[2] > Lp ? Lp : cursor[2]);
-    TdView v;
-    v.px = ego.cx; v.py = ego.cy; v.hc = ego.c; v.hs = ego.s; v.R = R;
-    v.m = md_td_metres_per_pixel(R, td.distance);
-    v.inv_m = 1.0f / v.m;
-    v.half = 0.5f * (float)R;
-    const float hw = md_td_line_half_width(v.m);
-    const float rwin = td.distance * 1.41422f + 2.0f * v.m;     // the window's circumscribed circle, with a margin
-    int map = w.env_map[e];
-    if (map < 0 || map >= w.n_maps) map = 0;
-    __syncthreads();
-
-    // ---- road_network: the route's lanes (a wave per road), then the line pieces (64 culled per wave and pass) ----
-    const int lane_a = w.lane_off[map], n_lanes = w.lane_off[map + 1] - lane_a;
-    const int road_a = w.road_off[map], n_roads = w.road_off[map + 1] - road_a;
-    int n_route = nav0.route_len - 1;
-    n_route = n_route > MD_ROUTE_LEN ? MD_ROUTE_LEN : n_route;
-    const float pad = 0.36f * v.m + 0.01f;      // a pixel's samples lie within 0.25 * sqrt(2) pixels of its centre
-    // the route's roads, one per lane of the wave (two dependent loads for all of them at once), then handed round
-    int my_first = 0, my_n = 0;
-    if (lane_id < n_route) {
-        const int rid = g.route_roads[b0 * MD_ROUTE_LEN + lane_id];
-        if (rid >= 0 && rid < n_roads) {
-            const MdRoad rd = w.roads[road_a + rid];
-            my_first = rd.first_lane;
-            my_n = rd.n_lanes;
-        }
-    }
-#if !(MD_TD_SKIP & 1)
-    int item = 0;                               // the route's lanes, dealt to the waves in turn
-    for (int j = 0; j < n_route; ++j) {
-        const int first_lane = bcast_i(my_first, j), road_lanes = min(bcast_i(my_n, j), n_lanes);
-        for (int l = 0; l < road_lanes; ++l) {
-            if (((item++) & 3) != wave) continue;
-            const int id = first_lane + l;
-            if (id < 0 || id >= n_lanes) continue;
-            const MdLane* L = &w.lanes[lane_a + id];
-            // the lane's AABB against the window's circle
-            const float ex = md_max(md_max(L->x0 - v.px, v.px - L->x1), 0.0f), ey = md_max(md_max(L->y0 - v.py, v.py - L->y1), 0.0f);
-            // MdLane.x0 .. y1 is the AABB of the lane's hull, which mapgen/lanes.py builds from a densely sampled polygon of the lane's
-            // outline with tangent extensions: chords of an arc miss it by centimetres, so 1.5 m (here and for the box below) is a wide
-            // margin.  tests/topdown_host.c culls on the same AABB with 1.0 m: should the hull ever be sampled coarsely, BOTH margins
-            // have to grow -- the two sides would otherwise miss the same part of an arc and still agree
-            if (ex * ex + ey * ey > (rwin + 1.5f) * (rwin + 1.5f)) continue;
-            float pts[8];
-            if (L->type == 0 && L->hull_n == 4) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) pts[i] = L->hull4[i];
-            } else {      // the AABB of the hull, grown beyond what a polygon of chords can miss of the arc
-                const float gx = 1.5f;
-                pts[0] = L->x0 - gx; pts[1] = L->y0 - gx; pts[2] = L->x1 + gx; pts[3] = L->y0 - gx;
-                pts[4] = L->x1 + gx; pts[5] = L->y1 + gx; pts[6] = L->x0 - gx; pts[7] = L->y1 + gx;
-            }
-            const TdBox b = td_bbox(v, pts, 2);
-            const float half = L->width / 2.0f + pad;
-            if (L->type == 0) {
-                td_raster_road(v, b, road, 1u, lane_id, queue,
-                               [&](float x, float y) {
-                                   const float dx = x - L->ax, dy = y - L->ay;
-                                   const float sl = dx * L->bx + dy * L->by, lat = dx * L->by - dy * L->bx;
-                                   return sl >= -pad && sl <= L->length + pad && md_fabs(lat) <= half;
-                               },
-                               [&](float x, float y) { return md_td_on_lane(L, x, y) != 0; });
-            } else {      // the ring of the arc's radius: no angle, no root
-                const float lo = md_max(L->bx - half, 0.0f), hi = L->bx + half;
-                td_raster_road(v, b, road, 1u, lane_id, queue,
-                               [&](float x, float y) {
-                                   const float dx = x - L->ax, dy = y - L->ay, r2 = dx * dx + dy * dy;
-                                   return r2 >= lo * lo && r2 <= hi * hi;
-                               },
-                               [&](float x, float y) { return md_td_on_lane(L, x, y) != 0; });
-            }
-        }
-    }
-#endif
-#if !(MD_TD_SKIP & 2)
-    const int qa = w.quad_off[map], qb = w.quad_off[map + 1];
-    const int line_grow = 1 + (int)(hw * v.inv_m + 0.5f);      // a sample on the strip lies within hw of the piece's own extent: at least half a pixel to spare
-    for (int q0 = qa + wave * 64; q0 < qb; q0 += 4 * 64) {
-        bool keep = false;
-        if (q0 + lane_id < qb) {
-            const QuadBall qbl = quad_ball_of(w, q0 + lane_id);
-            const float dx = qbl.mx - v.px, dy = qbl.my - v.py, reach = qbl.rr + rwin + hw;
-            keep = md_td_is_line_kind(qbl.kind) && dx * dx + dy * dy <= reach * reach;
-        }
-        // The pieces kept go into the wave's list (fetched by all lanes at once); then 16 lanes take a piece, four pieces at a
-        // time: a stripe's box is a dozen pixels, a whole wave on it would idle
-        const unsigned long long mask = __ballot(keep);
-        const int kept = __popcll(mask);
-        if (keep) {
-            const float4* qp = reinterpret_cast<const float4*>(w.quads) + 2 * (size_t)(q0 + lane_id);
-            float4* dst = reinterpret_cast<float4*>(pieces) + 2 * __popcll(mask & ((1ull << lane_id) - 1ull));
-            dst[0] = qp[0];
-            dst[1] = qp[1];
-        }
-        wave_lds_sync();
-        for (int k = lane_id >> 4; k < kept; k += 4) {
-            float q[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) q[i] = pieces[8 * k + i];
-            const TdBox b = td_bbox(v, q, line_grow);
-            const int n = b.w * b.h;
-            for (int idx = lane_id & 15; idx < n; idx += 16) {
-                const int dr = idx / b.w;
-                const int r = b.r0 + dr, cc = b.c0 + (idx - dr * b.w);
-                unsigned bits = 0u;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    float x, y;
-                    md_td_window(v.px, v.py, v.hc, v.hs, R, v.m, (float)r + 0.25f + 0.5f * (float)(u >> 1), (float)cc + 0.25f + 0.5f * (float)(u & 1), &x, &y);
-                    if (md_td_on_line(q, hw, x, y)) bits |= 2u << (2 * u);
-                }
-                const int pix = r * R + cc;
-                if (bits) atomicOr(&road[pix >> 2], bits << (8 * (pix & 3)));
-            }
-        }
-        wave_lds_sync();      // the list is rewritten by the next pass
-    }
-#endif
-#if !(MD_TD_SKIP & 4)
-    // ---- traffic(t): the drawn movers (64 culled per wave and pass), pixel centres ----
-    for (int j0 = wave * 64; j0 < c.cap; j0 += 4 * 64) {
-        bool keep = false;
-        MdShape mine = ego;
-        if (j0 + lane_id < c.cap) {
-            mine = g.shape[b0 + j0 + lane_id];
-            const float dx = mine.cx - v.px, dy = mine.cy - v.py, reach = md_fabs(mine.hl) + md_fabs(mine.hw) + rwin;
-            keep = md_td_drawn(mine.flags, j0 + lane_id) && dx * dx + dy * dy <= reach * reach;
-        }
-        unsigned long long mask = __ballot(keep);
-        while (mask) {
-            const int k = __ffsll((long long)mask) - 1;
-            mask &= mask - 1ull;
-            MdShape o;
-            o.cx = bcast_f(mine.cx, k); o.cy = bcast_f(mine.cy, k); o.c = bcast_f(mine.c, k); o.s = bcast_f(mine.s, k);
-            o.hl = bcast_f(mine.hl, k); o.hw = bcast_f(mine.hw, k); o.flags = bcast_i(mine.flags, k); o.aux = 0;
-            float oc, os;
-            md_td_snap(o.c, o.s, &oc, &os);
-            float pts[8];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float sl = (i == 0 || i == 3) ? o.hl : -o.hl, sw = (i < 2) ? o.hw : -o.hw;
-                pts[2 * i] = o.cx + sl * oc - sw * os;
-                pts[2 * i + 1] = o.cy + sl * os + sw * oc;
-            }
-            const TdBox b = td_bbox(v, pts, 1);
-            const int n = b.w * b.h;
-            for (int idx = lane_id; idx < n; idx += 64) {
-                const int dr = idx / b.w;
-                const int r = b.r0 + dr, cc = b.c0 + (idx - dr * b.w);
-                float x, y;
-                md_td_window(v.px, v.py, v.hc, v.hs, R, v.m, (float)r + 0.5f, (float)cc + 0.5f, &x, &y);
-                if (md_td_in_box(&o, x, y)) atomicOr(&traffic[r * wpr + (cc >> 5)], 1u << (cc & 31));
-            }
-        }
-    }
-#endif
-    // ---- past_pos: the position ring moves on, one dot per stacked position ----
-    const int pcur = reset ? 0 : (pcur_old + 1) % Lp;
-    const int pcnt = reset ? 1 : (pcnt_old + 1 > Lp ? Lp : pcnt_old + 1);
-    float* ring_pos = td.ring_pos + (size_t)e * (size_t)Lp * 2;
-    if (tid == 0) {
-        ring_pos[2 * pcur] = v.px;
-        ring_pos[2 * pcur + 1] = v.py;
-    }
-    if (tid < md_td_stack_count(pcnt, td.frame_skip)) {
-        const int back = pcnt - 1 - md_td_stack_index(pcnt, td.frame_skip, tid);    // positions back from the newest: tid * skip < pcnt
-        float ox = v.px, oy = v.py;
-        if (back > 0) {      // a slot an earlier launch wrote (back < Lp: never the slot written above)
-            const int slot = (pcur + Lp - back) % Lp;
-            ox = ring_pos[2 * slot];
-            oy = ring_pos[2 * slot + 1];
-        }
-        float sc, ss;
-        md_td_snap(v.hc, v.hs, &sc, &ss);
-        int row, col;
-        if (md_td_past_dot(ox, oy, v.px, v.py, sc, ss, R, td.distance, &row, &col)) atomicOr(&past[row * wpr + (col >> 5)], 1u << (col & 31));
-    }
-    __syncthreads();
-
-    // ---- the traffic ring moves on: the newest frame into its slot (every slot on a reset observation) ----
-    const int tcur = reset ? 0 : (tcur_old + 1) % Lt;
-    uint32_t* ring = td.ring_traffic + (size_t)e * (size_t)Lt * (size_t)FW;
-    for (int i = tid; i < FW; i += 256) {
-        const uint32_t word = traffic[i];
-        if (reset) {
-            for (int sl = 0; sl < Lt; ++sl) ring[(size_t)sl * FW + i] = word;
-        } else {
-            ring[(size_t)tcur * FW + i] = word;
-        }
-    }
-    // the older frames the epilogue reads (slots earlier launches wrote), into LDS with coalesced loads
-    if (!reset)
-        for (int i = tid; i < staged * FW; i += 256) {
-            const int f = i / FW;
-            stage[i] = ring[(size_t)((tcur + Lt - (f + 1) * td.frame_skip) % Lt) * FW + (i - f * FW)];
-        }
-    __syncthreads();
-    // ---- epilogue: compose and write the env's block ----
-    const int C = 2 + td.frame_stack, n = R * R * C;
-    typedef typename std::conditional<NORM, float, uint8_t>::type T;
-    const T t_on = NORM ? (T)md_td_traffic_float() : (T)md_td_traffic_byte();
-    const T p_on = NORM ? (T)1.0f : (T)255;
-    // the value of channel ch of pixel pix = (r, cc)
-    auto value = [&](int pix, int r, int cc, int ch) -> T {
-        if (ch == 0) {
-            const unsigned byte = (road[pix >> 2] >> (8 * (pix & 3))) & 0xFFu;
-            int sum4 = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const unsigned code = (byte >> (2 * k)) & 3u;
-                sum4 += (code & 2u) ? MD_TD_LINE : ((code & 1u) ? MD_TD_NAV : 0);
-            }
-            return NORM ? (T)md_td_road_float(sum4) : (T)md_td_road_byte(sum4);
-        }
-        const int wi = r * wpr + (cc >> 5);
-        uint32_t word;
-        if (ch == 1) word = past[wi];
-        else if (ch == 2 || reset) word = traffic[wi];
-        else if (staged) word = stage[(ch - 3) * FW + wi];
-        else word = ring[(size_t)((tcur + Lt - (ch - 2) * td.frame_skip) % Lt) * FW + wi];    // a slot of an earlier launch: (ch - 2) * skip < Lt
-        return ((word >> (cc & 31)) & 1u) ? (ch == 1 ? p_on : t_on) : (T)0;
-    };
-    T* out = (T*)td.out + (size_t)e * (size_t)n;
-    constexpr int VE = 16 / (int)sizeof(T);
-#if !(MD_TD_SKIP & 8)
-    if (vec) {      // n * sizeof(T) is a multiple of 16 and td.out is 16-byte aligned: so is every env's block
-        md_u32x4* out4 = reinterpret_cast<md_u32x4*>(out);
-        for (int q = tid; q < n / VE; q += 256) {      // consecutive lanes, consecutive 16 bytes
-            int pix = (q * VE) / C, ch = q * VE - pix * C;
-            int r = pix / R, cc = pix - r * R;
-            union { md_u32x4 q4; T t[VE]; } u;
-#pragma unroll
-            for (int j = 0; j < VE; ++j) {
-                u.t[j] = value(pix, r, cc, ch);
-                if (++ch == C) {
-                    ch = 0;
-                    ++pix;
-                    if (++cc == R) {
-                        cc = 0;
-                        ++r;
-                    }
-                }
-            }
-            __builtin_nontemporal_store(u.q4, &out4[q]);
-        }
-    } else {
-        for (int i = tid; i < n; i += 256) {
-            const int pix = i / C, r = pix / R;
-            out[i] = value(pix, r, pix - r * R, i - pix * C);
-        }
-    }
-#endif
-    if (tid == 0) {      // every thread read the cursors before the first barrier
-        cursor[0] = tcur;
-        cursor[1] = pcur;
-        cursor[2] = reset ? 0 : pcnt;     // the reference clears stack_past_pos after the reset observation's dot is drawn
-        cursor[3] = 0;
-    }
-}
-
-// ---- md_render (include/md_render.h): env.render(mode="topdown"), one workgroup per (tile, rendered env) ----------------------
-// A tile is MD_RD_TILE x MD_RD_TILE pixels, one LDS word each.  The word holds a RANK, not a colour: 0 the white ground, 1 .. 3 the
-// line kinds in their order, 4 + 2 * (k * cap + slot) + contour the box of `slot` in held frame k.  Ranks grow along the painter's
-// order, so every primitive is rasterised over its own bounding box in the tile with an LDS atomicMax and no order between
-// primitives is needed; the epilogue turns ranks into colours (the faded colour of every (frame, slot) sits in an LDS table) and
-// writes the tile's rows.  Nothing here depends on the order in which waves run: the image is a function of the ring alone.
-struct RenderLds { uint32_t pix, palette, pieces, kinds, bytes; };
-__host__ __device__ constexpr RenderLds render_lds(int num_stack, int cap) {
-    const uint32_t palette = 4u * MD_RD_TILE * MD_RD_TILE;
-    const uint32_t pieces = palette + align_up(4u * (uint32_t)num_stack * (uint32_t)cap, 16);      // written with 16-byte LDS stores
-    const uint32_t kinds = pieces + 4u * 64u * 32u;
-    return RenderLds{0u, palette, pieces, kinds, kinds + 4u * 64u * 4u};
-}
-
-// the launch before the raster: the current boxes into the ring of every rendered env, its cursor moved on
-__global__ __launch_bounds__(MD_MAX_CAP) void render_push_kernel(const MdState g, const MdConfig c, const MdRender r) {
-    const int ri = blockIdx.x, j = threadIdx.x;
-    int e = r.env_ids[ri];
-    e = e < 0 ? 0 : (e >= c.n_envs ? c.n_envs - 1 : e);
-    const size_t b0 = (size_t)e * (size_t)c.cap;
-    int32_t* cursor = r.cursor + 4 * (size_t)ri;
-    const int clock = md_rd_clock(&g, &c, e, &g.nav[b0]);
-    int newest, held;
-    md_rd_advance(cursor, r.num_stack, clock, &newest, &held);
-    __syncthreads();      // every thread has read the cursors
-    if (j < c.cap) r.ring[((size_t)ri * (size_t)r.num_stack + (size_t)newest) * (size_t)c.cap + j] = md_rd_box_of(&g.shape[b0 + j], j);
-    if (j == 0) {
-        cursor[0] = newest;
-        cursor[1] = held;
-        cursor[2] = clock;
-        cursor[3] = 0;
-    }
-}
-
-struct RdView { float px, py, uc, us, scaling; int W, H, r0, c0, th, tw; };      // the window, and this workgroup's tile of it
-struct RdBox { int r0, c0, w, h; };                                              // in the tile's own rows and columns
-
-// the pixels of the tile that can hold the centre of a sample of the convex hull of the four world points xy, grown by `grow` pixels
-__device__ __forceinline__ RdBox rd_bbox(const RdView& v, const float* xy, int grow) {
-    float rmin = 3.0e38f, rmax = -3.0e38f, cmin = 3.0e38f, cmax = -3.0e38f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float dx = xy[2 * i] - v.px, dy = xy[2 * i + 1] - v.py;
-        const float fr = 0.5f * (float)v.H - (dx * v.uc + dy * v.us) * v.scaling;
-        const float fc = 0.5f * (float)v.W + (dx * v.us - dy * v.uc) * v.scaling;
-        rmin = md_min(rmin, fr); rmax = md_max(rmax, fr);
-        cmin = md_min(cmin, fc); cmax = md_max(cmax, fc);
-    }
-    const float lo = -8.0f, hr = (float)v.H + 8.0f, hc = (float)v.W + 8.0f;     // keeps the conversions to int in range (NaN -> lo)
-    const int r0 = (int)md_floor(md_clip(rmin, lo, hr)) - grow - v.r0, r1 = (int)md_floor(md_clip(rmax, lo, hr)) + grow - v.r0;
-    const int c0 = (int)md_floor(md_clip(cmin, lo, hc)) - grow - v.c0, c1 = (int)md_floor(md_clip(cmax, lo, hc)) + grow - v.c0;
-    RdBox b;
-    b.r0 = r0 < 0 ? 0 : r0;
-    b.c0 = c0 < 0 ? 0 : c0;
-    const int r1c = r1 > v.th - 1 ? v.th - 1 : r1, c1c = c1 > v.tw - 1 ? v.tw - 1 : c1;
-    b.h = r1c >= b.r0 ? r1c - b.r0 + 1 : 0;
-    b.w = c1c >= b.c0 ? c1c - b.c0 + 1 : 0;
-    return b;
-}
-
-__global__ __launch_bounds__(256) void render_kernel(const MdWorld w, const MdState g, const MdConfig c, const MdRender r, const int tiles_x,
-                                                     const int vec) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int ri = blockIdx.y, tid = threadIdx.x, lane_id = tid & 63, wave = tid >> 6;
-    const RenderLds lds = render_lds(r.num_stack, c.cap);
-    uint32_t* pix = reinterpret_cast<uint32_t*>(smem + lds.pix);
-    uint32_t* palette = reinterpret_cast<uint32_t*>(smem + lds.palette);
-    float* pieces = reinterpret_cast<float*>(smem + lds.pieces) + wave * 64 * 8;
-    int* kinds = reinterpret_cast<int*>(smem + lds.kinds) + wave * 64;
-    for (int i = tid; i < MD_RD_TILE * MD_RD_TILE; i += 256) pix[i] = 0u;
-
-    int e = r.env_ids[ri];
-    e = e < 0 ? 0 : (e >= c.n_envs ? c.n_envs - 1 : e);
-    const size_t b0 = (size_t)e * (size_t)c.cap;
-    const MdShape tracked = g.shape[b0 + r.track_agent];
-    RdView v;
-    md_rd_camera(&r, &tracked, &v.px, &v.py, &v.uc, &v.us);
-    v.scaling = r.scaling; v.W = r.width; v.H = r.height;
-    const int ty = blockIdx.x / tiles_x;
-    v.r0 = ty * MD_RD_TILE;
-    v.c0 = (blockIdx.x - ty * tiles_x) * MD_RD_TILE;
-    v.th = min(MD_RD_TILE, v.H - v.r0);
-    v.tw = min(MD_RD_TILE, v.W - v.c0);
-    // the tile's circumscribed circle, with a margin of two pixels
-    float tcx, tcy;
-    md_rd_window(v.px, v.py, v.uc, v.us, v.W, v.H, v.scaling, (float)v.r0 + 0.5f * (float)v.th, (float)v.c0 + 0.5f * (float)v.tw, &tcx, &tcy);
-    const float rtile = (0.70711f * (float)MD_RD_TILE + 2.0f) / v.scaling;
-    const int32_t* cursor = r.cursor + 4 * (size_t)ri;      // as render_push_kernel left them
-    const int newest = (int)((uint32_t)cursor[0] % (uint32_t)r.num_stack);
-    const int held = cursor[1] < 1 ? 1 : (cursor[1] > r.num_stack ? r.num_stack : cursor[1]);
-    int map = w.env_map[e];
-    if (map < 0 || map >= w.n_maps) map = 0;
-    __syncthreads();
-
-    // ---- the map's line pieces: 64 culled per wave and pass, then 16 lanes to a piece ----
-    const float hw = md_rd_line_half_width(v.scaling);
-    const int line_grow = 2 + (int)(hw * v.scaling);      // a sample on the strip lies within hw of the piece's own extent
-    const int qa = w.quad_off[map], qb = w.quad_off[map + 1];
-    for (int q0 = qa + wave * 64; q0 < qb; q0 += 4 * 64) {
-        bool keep = false;
-        int order = 0;
-        if (q0 + lane_id < qb) {
-            const QuadBall qbl = quad_ball_of(w, q0 + lane_id);
-            const float dx = qbl.mx - tcx, dy = qbl.my - tcy, reach = qbl.rr + rtile + hw;
-            order = md_rd_line_order(qbl.kind);
-            keep = order != 0 && dx * dx + dy * dy <= reach * reach;
-        }
-        const unsigned long long mask = __ballot(keep);
-        const int kept = __popcll(mask);
-        if (keep) {
-            const int at = __popcll(mask & ((1ull << lane_id) - 1ull));
-            const float4* qp = reinterpret_cast<const float4*>(w.quads) + 2 * (size_t)(q0 + lane_id);
-            float4* dst = reinterpret_cast<float4*>(pieces) + 2 * at;
-            dst[0] = qp[0];
-            dst[1] = qp[1];
-            kinds[at] = order;
-        }
-        wave_lds_sync();
-        for (int k = lane_id >> 4; k < kept; k += 4) {
-            float q[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) q[i] = pieces[8 * k + i];
-            const unsigned rank = (unsigned)kinds[k];
-            const RdBox b = rd_bbox(v, q, line_grow);
-            const int n = b.w * b.h;
-            for (int idx = lane_id & 15; idx < n; idx += 16) {
-                const int dr = idx / b.w;
-                const int lr = b.r0 + dr, lc = b.c0 + (idx - dr * b.w);
-                float x, y;
-                md_rd_window(v.px, v.py, v.uc, v.us, v.W, v.H, v.scaling, (float)(v.r0 + lr) + 0.5f, (float)(v.c0 + lc) + 0.5f, &x, &y);
-                if (md_td_on_line(q, hw, x, y)) atomicMax(&pix[lr * MD_RD_TILE + lc], rank);
-            }
-        }
-        wave_lds_sync();      // the list is rewritten by the next pass
-    }
-
-    // ---- the movers of every held frame: item i = (frame k, slot), 64 culled per wave and pass, then the wave on each kept box ----
-    const int n_items = held * c.cap;
-    const float cw = MD_RD_CONTOUR_PIXELS / v.scaling;
-    for (int i0 = wave * 64; i0 < n_items; i0 += 4 * 64) {
-        bool keep = false;
-        MdShape mine = tracked;
-        const int i = i0 + lane_id;
-        if (i < n_items) {
-            const int k = i / c.cap, slot = i - k * c.cap;
-            mine = r.ring[((size_t)ri * (size_t)r.num_stack + (size_t)md_rd_ring_slot(newest, r.num_stack, held, k)) * (size_t)c.cap + slot];
-            if (mine.flags != 0 && !md_rd_frame_skipped(held, k, r.history_smooth)) {
-                palette[i] = (uint32_t)md_rd_fade(mine.aux, md_rd_alpha(held, k));
-                const float dx = mine.cx - tcx, dy = mine.cy - tcy, reach = md_fabs(mine.hl) + md_fabs(mine.hw) + rtile;
-                keep = dx * dx + dy * dy <= reach * reach;
-            }
-        }
-        unsigned long long mask = __ballot(keep);
-        while (mask) {
-            const int src = __ffsll((long long)mask) - 1;
-            mask &= mask - 1ull;
-            MdShape o;
-            o.cx = bcast_f(mine.cx, src); o.cy = bcast_f(mine.cy, src); o.c = bcast_f(mine.c, src); o.s = bcast_f(mine.s, src);
-            o.hl = bcast_f(mine.hl, src); o.hw = bcast_f(mine.hw, src); o.flags = bcast_i(mine.flags, src); o.aux = 0;
-            const int item = i0 + src;
-            const bool contour = r.draw_contour && item / c.cap == held - 1;
-            float oc, os;
-            md_td_snap(o.c, o.s, &oc, &os);
-            float pts[8];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const float sl = (t == 0 || t == 3) ? o.hl : -o.hl, sw = (t < 2) ? o.hw : -o.hw;
-                pts[2 * t] = o.cx + sl * oc - sw * os;
-                pts[2 * t + 1] = o.cy + sl * os + sw * oc;
-            }
-            const RdBox b = rd_bbox(v, pts, 1);
-            const int n = b.w * b.h;
-            for (int idx = lane_id; idx < n; idx += 64) {
-                const int dr = idx / b.w;
-                const int lr = b.r0 + dr, lc = b.c0 + (idx - dr * b.w);
-                float x, y;
-                md_rd_window(v.px, v.py, v.uc, v.us, v.W, v.H, v.scaling, (float)(v.r0 + lr) + 0.5f, (float)(v.c0 + lc) + 0.5f, &x, &y);
-                if (md_td_in_box(&o, x, y)) {
-                    const unsigned edge = (contour && md_rd_on_contour(&o, cw, x, y)) ? 1u : 0u;
-                    atomicMax(&pix[lr * MD_RD_TILE + lc], 4u + 2u * (unsigned)item + edge);
-                }
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- epilogue: ranks to colours, in place; then the tile's rows ----
-    for (int p = tid; p < MD_RD_TILE * MD_RD_TILE; p += 256) {
-        const uint32_t rank = pix[p];
-        pix[p] = rank == 0u ? (uint32_t)MD_RD_WHITE
-                            : (rank < 4u ? (uint32_t)md_rd_line_rgb((int)rank) : ((rank & 1u) ? (uint32_t)MD_RD_CONTOUR_RGB : palette[(rank - 4u) >> 1]));
-    }
-    __syncthreads();
-    uint8_t* out = r.out + (((size_t)ri * (size_t)v.H + (size_t)v.r0) * (size_t)v.W + (size_t)v.c0) * 3;      // the tile's first byte
-    const int row_bytes = v.tw * 3;
-    auto byte_of = [&](int lr, int b) -> uint32_t {
-        const int p = b / 3;
-        return (pix[lr * MD_RD_TILE + p] >> (8 * (b - 3 * p))) & 255u;
-    };
-    if (vec) {      // W is a multiple of 16 and r.out 16-byte aligned: so are every tile row's first byte and length
-        const int cpr = row_bytes >> 4;
-        for (int q = tid; q < v.th * cpr; q += 256) {      // consecutive lanes, consecutive 16 bytes of a row
-            const int lr = q / cpr, b = (q - lr * cpr) << 4;
-            md_u32x4 t;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                t[j] = byte_of(lr, b + 4 * j) | (byte_of(lr, b + 4 * j + 1) << 8) | (byte_of(lr, b + 4 * j + 2) << 16) | (byte_of(lr, b + 4 * j + 3) << 24);
-            __builtin_nontemporal_store(t, reinterpret_cast<md_u32x4*>(out + (size_t)lr * (size_t)v.W * 3 + b));
-        }
-    } else {
-        for (int q = tid; q < v.th * row_bytes; q += 256) {
-            const int lr = q / row_bytes, b = q - lr * row_bytes;
-            out[(size_t)lr * (size_t)v.W * 3 + b] = (uint8_t)byte_of(lr, b);
-        }
-    }
-}
+namespace {
 
 __global__ void probe_kernel(int op, const float* a, const float* b, float* out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = md_probe_eval(op, a[i], b[i]);
-}
-
-// return from the calling entry point unless x is MD_OK
-#define TRY(x)                       \
-    do {                             \
-        const int _r = (x);          \
-        if (_r != MD_OK) return _r;  \
-    } while (0)
-#define NEED(p) TRY(need((const void*)(p), #p))
-
-int check_struct_size(const MdConfig* c) {
-    if (c->struct_size == (int32_t)sizeof(MdConfig)) return MD_OK;
-    snprintf(g_err, sizeof g_err, "MdConfig.struct_size=%d, library expects %d", c->struct_size, (int)sizeof(MdConfig));
-    return MD_EABI;
-}
-
-int check_common(const MdWorld* w, const MdState* s, const MdConfig* c) {
-    if (!w || !s || !c) {
-        snprintf(g_err, sizeof g_err, "null MdWorld/MdState/MdConfig pointer");
-        return MD_EINVAL;
-    }
-    TRY(check_struct_size(c));
-    if (c->n_envs <= 0 || c->cap <= 0 || c->cap > MD_MAX_CAP || c->agents_per_env <= 0 || c->agents_per_env > c->cap) {
-        snprintf(g_err, sizeof g_err, "bad sizes: n_envs=%d cap=%d agents_per_env=%d (cap<=%d)", c->n_envs, c->cap,
-                 c->agents_per_env, MD_MAX_CAP);
-        return MD_EINVAL;
-    }
-    if (c->n_beams < 0 || c->n_beams > MD_MAX_BEAMS) {
-        snprintf(g_err, sizeof g_err, "n_beams=%d out of range [0,%d]", c->n_beams, MD_MAX_BEAMS);
-        return MD_EINVAL;
-    }
-    if (!s->shape) {
-        snprintf(g_err, sizeof g_err, "MdState.shape is null");
-        return MD_EINVAL;
-    }
-    if (w->n_envs != c->n_envs) {
-        snprintf(g_err, sizeof g_err, "MdWorld.n_envs=%d != MdConfig.n_envs=%d", w->n_envs, c->n_envs);
-        return MD_EINVAL;
-    }
-    return MD_OK;
-}
-
-int need(const void* p, const char* name) {
-    if (p) return MD_OK;
-    snprintf(g_err, sizeof g_err, "required pointer %s is null", name);
-    return MD_EINVAL;
-}
-
-// ---- the MdWorld / MdState pointers each entry point requires ----
-// A row: the entry points that require its fields (their PH_* bits: PH_RESET is md_step's alone; the k*Entry bits stand for
-// the entry points that run no phase), the condition under which they do, and the fields.  An entry point checks the rows of
-// a few conditions at a time (need_fields), each group where its code has validated what the condition reads; within a
-// group, table order is check order, so the first null field is the one the message names.
-enum When : unsigned {
-    ALWAYS = 1, LIDAR_ON = 2, MULTI = 4, RESPAWN = 8,   // check_phase, before anything but check_common
-    REPLAY = 16, SPAWN_TRAFFIC = 32,                     // check_phase, after traffic_mode is validated
-    SCENARIO = 64, ROUTE = 128, OTHERS = 256,            // md_step, each after the config checks of its branch
-};
-constexpr int kLidarEntry = 1 << 9, kDetectorEntry = 1 << 10, kExpertEntry = 1 << 11, kPgWalkEntry = 1 << 12, kProtectEntry = 1 << 13,
-              kSenseEntry = 1 << 14, kTopDownEntry = 1 << 15, kRenderEntry = 1 << 16, kPedEntry = 1 << 17, kVectorObsEntry = 1 << 18;
-constexpr int kMapPhases = PH_LOCALIZE | PH_CONTACTS | PH_OBSERVE | PH_IDM | PH_LIFECYCLE;
-constexpr int kTrafficPhases = PH_INTEGRATE | PH_TRAFFIC;
-
-struct Field { const char* name; bool world; size_t off; };   // "w->x" / "s->x" as the message spells it, MdWorld?, offset
-#define FW(f) Field{"w->" #f, true, offsetof(MdWorld, f)}
-#define FS(f) Field{"s->" #f, false, offsetof(MdState, f)}
-#define MAP_FIELDS FW(env_map), FW(lane_off), FW(lanes), FW(hull_xy), FW(road_off), FW(roads), FW(quad_off), FW(quads), \
-                   FW(quad_kind), FW(grid), FW(cell_start), FW(cell_items)
-struct Need { int entries; When when; Field fields[12]; };   // fields: up to 12, the unused tail has name == nullptr
-const Need kNeeds[] = {
-    {PH_ALL, ALWAYS, {FS(dyn), FS(param), FS(nav), FS(pid), FS(action), FS(flags), FS(route_nodes), FS(route_roads), FS(need_reset)}},
-    {kMapPhases, ALWAYS, {MAP_FIELDS}},
-    {PH_OBSERVE, ALWAYS, {FS(final_lane)}},
-    {PH_IDM, ALWAYS, {FS(idm_rand)}},
-    {PH_OBSERVE, ALWAYS, {FS(obs), FS(reward), FS(cost), FS(step_info)}},
-    {PH_IDM, ALWAYS, {FW(node_adj_off), FW(node_adj), FW(node_off)}},
-    {PH_RESET, LIDAR_ON, {FW(beam_cs)}},
-    {PH_RESET, ALWAYS, {FS(shape0), FS(dyn0), FS(nav0), FS(pid0)}},
-    {PH_LIFECYCLE, MULTI, {FS(rng), FS(env_steps), FS(agent_id), FS(next_agent_id), FS(route_nodes0), FS(route_roads0), FS(final_lane0),
-                           FS(final_lane)}},
-    {PH_LIFECYCLE, RESPAWN, {FW(spawn_off), FW(spawn_place), FW(spawn_lane), FW(spawn_route), FW(spawn_route_meta)}},
-    {kTrafficPhases, REPLAY, {FS(track_shape), FS(track_dyn)}},
-    {kTrafficPhases, SPAWN_TRAFFIC, {MAP_FIELDS}},
-    {kTrafficPhases, SPAWN_TRAFFIC, {FS(rng), FS(route_nodes0), FS(route_roads0), FS(final_lane0), FS(final_lane), FW(spawn_off),
-                                     FW(spawn_lane), FW(spawn_route), FW(spawn_route_meta)}},
-    {PH_RESET, SCENARIO, {FW(poly_off), FW(segs), FW(polyv_off), FW(polyv), FW(ckpt_off), FW(ckpt_xy), FW(track_meta), FS(track_shape),
-                          FS(track_dyn), FS(next_agent_id)}},
-    {PH_RESET, ROUTE, {FS(route_segs), FS(route_verts), FS(route_aux), FW(run_off), FW(runs)}},
-    {PH_RESET, OTHERS, {FS(detected)}},
-    {kLidarEntry, ALWAYS, {FW(beam_cs)}},
-    {kDetectorEntry, ALWAYS, {FW(env_map), FW(quad_off), FW(quads), FW(quad_kind)}},
-    {kExpertEntry, ALWAYS, {FS(obs), FS(detected), FS(dyn), FS(param), FS(nav), FW(env_map), FW(lanes), FW(lane_off), FW(roads),
-                            FW(road_off)}},
-    {kProtectEntry, ALWAYS, {FS(shape), FS(need_reset)}},
-    {kSenseEntry, ALWAYS, {FS(dyn), FS(param), FS(nav), FS(action), FS(final_lane), FS(need_reset), FW(env_map), FW(lanes), FW(lane_off),
-                           FW(roads), FW(road_off)}},
-    {kTopDownEntry, ALWAYS, {FS(nav), FS(route_roads), FW(env_map), FW(lane_off), FW(lanes), FW(road_off), FW(roads), FW(quad_off), FW(quads),
-                             FW(quad_kind)}},
-    {kRenderEntry, ALWAYS, {FS(nav), FW(env_map), FW(quad_off), FW(quads), FW(quad_kind)}},
-    {kRenderEntry, MULTI, {FS(env_steps)}},
-    {kPgWalkEntry, ALWAYS, {FS(scene_of), FS(walk_ep), FS(param), FS(route_nodes), FS(route_roads), FS(final_lane), FS(idm_rand)}},
-    {kPgWalkEntry, SPAWN_TRAFFIC, {FS(rng), FS(route_nodes0), FS(route_roads0), FS(final_lane0)}},
-    {kPedEntry, ALWAYS, {FS(shape), FS(dyn), FS(nav), FS(pid), FS(idm_rand), FS(need_reset)}},
-    {kVectorObsEntry, ALWAYS, {FS(shape), FS(dyn), FS(nav), FS(route_roads), FS(final_lane), FW(env_map), FW(lane_off), FW(lanes),
-                               FW(road_off), FW(roads)}},
-    {kVectorObsEntry, MULTI, {FS(env_steps)}},
-};
-#undef FW
-#undef FS
-#undef MAP_FIELDS
-
-bool holds(When when, const MdState* s, const MdConfig* c) {
-    switch (when) {
-    case ALWAYS: return true;
-    case LIDAR_ON: return c->n_beams > 0;
-    case MULTI: return c->is_multi_agent;
-    case RESPAWN: return c->is_multi_agent && c->allow_respawn;
-    case REPLAY: return c->traffic_mode == 3;
-    case SPAWN_TRAFFIC: return c->traffic_mode == 1 || c->traffic_mode == 2;   // respawn / hybrid
-    case SCENARIO: return c->traffic_mode == 4;
-    case ROUTE: return c->traffic_mode == 4 && s->route_n;
-    case OTHERS: return c->num_others > 0;
-    }
-    return false;
-}
-
-// MD_OK, or MD_EINVAL naming the first null field that `entry` requires under the conditions `whens`
-int need_fields(int entry, unsigned whens, const MdWorld* w, const MdState* s, const MdConfig* c) {
-    for (const Need& n : kNeeds) {
-        if (!(n.entries & entry) || !(n.when & whens) || !holds(n.when, s, c)) continue;
-        for (const Field& f : n.fields) {
-            if (f.name && !*(void* const*)((const char*)(f.world ? (const void*)w : (const void*)s) + f.off)) return need(nullptr, f.name);
-        }
-    }
-    return MD_OK;
 }
 
 // what the eight phase entry points check before they launch (md_step goes on checking)
@@ -5348,14 +3860,6 @@ int check_phase(int ph, const MdWorld* w, const MdState* s, const MdConfig* c) {
         return MD_EINVAL;
     }
     return MD_OK;
-}
-
-// after a hipLaunchKernelGGL: MD_OK, or MD_ELAUNCH with the HIP error in g_err
-int launch_status() {
-    const hipError_t err = hipGetLastError();
-    if (err == hipSuccess) return MD_OK;
-    snprintf(g_err, sizeof g_err, "kernel launch failed: %s", hipGetErrorString(err));
-    return MD_ELAUNCH;
 }
 
 // The kernel a phase launches.  md_step of the single-agent envs has two: env_kernel (one 4-wave workgroup per env) and
@@ -5554,94 +4058,6 @@ __attribute__((visibility("default"))) int md_line_detector(const MdWorld* w, co
 
 // Two detector fans (the side detector and the lane-line detector of one observation) in ONE launch and one pass over the map's
 // line pieces: what SideDetector.perceive + LaneLineDetector.perceive cost twice (obs/state_obs.py:77-86,129-140).
-__attribute__((visibility("default"))) int md_swap_draw(const MdState* s, const MdState* staged, const MdConfig* c, int n_draws,
-                                                        int32_t* draw_idx, void* stream) {
-    if (!s || !staged || !c || !draw_idx) {
-        snprintf(g_err, sizeof g_err, "md_swap_draw: null MdState / staged MdState / MdConfig / draw_idx");
-        return MD_EINVAL;
-    }
-    TRY(check_struct_size(c));
-    if (n_draws < 1 || c->n_envs <= 0 || c->cap <= 0 || c->cap > MD_MAX_CAP) {
-        snprintf(g_err, sizeof g_err, "md_swap_draw: n_draws=%d n_envs=%d cap=%d", n_draws, c->n_envs, c->cap);
-        return MD_EINVAL;
-    }
-    if (!s->need_reset || !s->shape0 || !s->dyn0 || !s->nav0 || !s->pid0 || !staged->shape0 || !staged->dyn0 || !staged->nav0 || !staged->pid0) {
-        snprintf(g_err, sizeof g_err, "md_swap_draw: need_reset and the snapshot arrays shape0 / dyn0 / nav0 / pid0 (live and staged) are required");
-        return MD_EINVAL;
-    }
-    const MdWalk& wk = s->walk;
-    if (wk.mode != 0 && c->traffic_mode >= 0 && c->traffic_mode <= 2) {   // the PG walk: n_draws PG scenes, draw_idx = MdWorld.env_map
-        if (wk.mode < 0 || wk.mode > 2 || c->is_multi_agent || c->agents_per_env != 1 || wk.n_scenes != n_draws || wk.stride < 1 ||
-            wk.offset < 0) {
-            snprintf(g_err, sizeof g_err, "md_swap_draw: the PG walk needs mode 1 or 2 (got %d), a single-agent batch (agents=%d), "
-                     "n_scenes == n_draws (%d, %d), stride >= 1 (%d) and offset >= 0 (%d)", wk.mode, c->agents_per_env, wk.n_scenes,
-                     n_draws, wk.stride, wk.offset);
-            return MD_EINVAL;
-        }
-        // the live batch and the pool hold the same per-slot constants: what the in-kernel reset of the next step reads
-        TRY(need_fields(kPgWalkEntry, ALWAYS | SPAWN_TRAFFIC, nullptr, s, c));
-        const bool spawn = c->traffic_mode == 1 || c->traffic_mode == 2;
-        if (!staged->param || !staged->route_nodes || !staged->route_roads || !staged->final_lane || !staged->idm_rand ||
-            (spawn && !staged->rng)) {
-            snprintf(g_err, sizeof g_err, "md_swap_draw: the PG walk's pool (staged) needs param / route_nodes / route_roads / "
-                     "final_lane / idm_rand, and rng in the respawn / hybrid modes");
-            return MD_EINVAL;
-        }
-    } else if (wk.mode != 0) {   // the scenario walk: n_draws scenes, draw_idx = MdWorld.env_map
-        if (wk.mode < 0 || wk.mode > 2 || c->traffic_mode != 4 || wk.n_scenes != n_draws || wk.stride < 1 || wk.offset < 0 ||
-            !s->scene_of || !s->walk_ep) {
-            snprintf(g_err, sizeof g_err, "md_swap_draw: the scenario walk needs mode 1 or 2 (got %d), traffic_mode 4, n_scenes == "
-                     "n_draws (%d, %d), stride >= 1 (%d), offset >= 0 (%d) and MdState.scene_of / walk_ep", wk.mode, wk.n_scenes,
-                     n_draws, wk.stride, wk.offset);
-            return MD_EINVAL;
-        }
-    }
-    hipLaunchKernelGGL(swap_draw_kernel, dim3(c->n_envs), dim3(256), 0, (hipStream_t)stream, *s, *staged, *c, n_draws, draw_idx);
-    return launch_status();
-}
-
-// include/md_curriculum.h
-__attribute__((visibility("default"))) int md_curriculum(const MdState* s, const MdState* staged, const MdConfig* c,
-                                                         const MdCurriculum* cu, int32_t* env_map, int reset, void* stream) {
-    if (!s || !staged || !c || !cu || !env_map) {
-        snprintf(g_err, sizeof g_err, "md_curriculum: null MdState / staged MdState / MdConfig / MdCurriculum / env_map");
-        return MD_EINVAL;
-    }
-    TRY(check_struct_size(c));
-    if (c->n_envs <= 0 || c->cap <= 0 || c->cap > MD_MAX_CAP || c->agents_per_env != 1 || c->traffic_mode != 4) {
-        snprintf(g_err, sizeof g_err, "md_curriculum: a single-agent scenario batch is required (n_envs=%d cap=%d agents=%d "
-                 "traffic_mode=%d)", c->n_envs, c->cap, c->agents_per_env, c->traffic_mode);
-        return MD_EINVAL;
-    }
-    const MdWalk& wk = s->walk;
-    if (wk.mode == 0 || wk.n_scenes != cu->n_scenes || wk.stride != cu->stride || wk.offset != cu->offset || !s->scene_of ||
-        !s->walk_ep || !s->need_reset || !s->flags || !s->step_info) {
-        snprintf(g_err, sizeof g_err, "md_curriculum: needs the scenario walk (MdState.walk mode %d, n_scenes %d / %d, stride %d / %d, "
-                 "offset %d / %d), MdState.scene_of / walk_ep / need_reset / flags / step_info", wk.mode, wk.n_scenes, cu->n_scenes,
-                 wk.stride, cu->stride, wk.offset, cu->offset);
-        return MD_EINVAL;
-    }
-    if (cu->n_levels < 1 || cu->n_scenes < 1 || cu->per_level * cu->n_levels != cu->n_scenes || cu->eval < 1 || cu->stride < 1 ||
-        cu->offset < 0 || cu->cover_words != (cu->n_scenes + 31) / 32 || (cu->n_levels > 1 && wk.mode != 1)) {
-        snprintf(g_err, sizeof g_err, "md_curriculum: n_levels=%d per_level=%d n_scenes=%d eval=%d stride=%d offset=%d cover_words=%d "
-                 "walk mode %d (levels > 1 need the sequential walk)", cu->n_levels, cu->per_level, cu->n_scenes, cu->eval, cu->stride,
-                 cu->offset, cu->cover_words, wk.mode);
-        return MD_EINVAL;
-    }
-    if (!cu->level || !cu->seed || !cu->q_len || !cu->q_key || !cu->q_success || !cu->q_route || !cu->cover || !cu->cover_n ||
-        !cu->rep_i || !cu->rep_f) {
-        snprintf(g_err, sizeof g_err, "md_curriculum: every MdCurriculum array is required");
-        return MD_EINVAL;
-    }
-    if (cu->n_levels > 1 && (!s->shape0 || !s->dyn0 || !s->nav0 || !s->pid0 || !staged->shape0 || !staged->dyn0 || !staged->nav0 ||
-                             !staged->pid0)) {
-        snprintf(g_err, sizeof g_err, "md_curriculum: the snapshot arrays shape0 / dyn0 / nav0 / pid0 (live and staged) are required");
-        return MD_EINVAL;
-    }
-    hipLaunchKernelGGL(curriculum_kernel, dim3(c->n_envs), dim3(64), 0, (hipStream_t)stream, *s, *staged, *c, *cu, env_map, reset);
-    return launch_status();
-}
-
 __attribute__((visibility("default"))) int md_line_detectors(const MdWorld* w, const MdState* s, const MdConfig* c,
                                                             const float* beam_cs0, int n_beams0, float range0, uint32_t kind_mask0,
                                                             int out_offset0, const float* beam_cs1, int n_beams1, float range1,
@@ -5741,81 +4157,6 @@ __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdSta
     return launch_status();
 }
 
-// the configs where the reference's rewrite of the vehicle config (numpy_expert.py:58-62) changes nothing
-static int check_expert_config(const MdConfig* c, const char* who) {
-    if (c->is_multi_agent || c->agents_per_env != 1 || c->traffic_mode == 4 || c->n_beams != 240 || c->lidar_range != 50.0f ||
-        c->num_others != 0 || c->n_side != 0 || c->n_lane_line != 0 || c->random_agent_model != 0 ||
-        c->obs_dim != MD_EXPERT_IN - 4 * MD_EXPERT_OTHERS) {
-        snprintf(g_err, sizeof g_err, "%s: needs a single-agent batch with the expert's lidar (240 beams, 50 m, num_others 0), "
-                 "no side / lane-line detector and random_agent_model off (obs_dim 259)", who);
-        return MD_EINVAL;
-    }
-    return MD_OK;
-}
-
-__attribute__((visibility("default"))) int md_expert(const MdWorld* w, const MdState* s, const MdConfig* c, const float* weights,
-                                                    const float* noise, float* action_out, float* mlp_out, float* obs_out,
-                                                    void* stream) {
-    TRY(check_common(w, s, c));
-    NEED(weights); NEED(action_out);
-    TRY(need_fields(kExpertEntry, ALWAYS, w, s, c));
-    TRY(check_expert_config(c, "md_expert"));
-    if ((uintptr_t)weights & 15) {
-        snprintf(g_err, sizeof g_err, "md_expert: the packed weights must be 16-byte aligned");
-        return MD_EINVAL;
-    }
-    hipLaunchKernelGGL(expert_kernel, dim3((c->n_envs + kExpM - 1) / kExpM), dim3(256), 0, (hipStream_t)stream, *w, *s, *c, weights,
-                       noise, action_out, mlp_out, obs_out);
-    return launch_status();
-}
-
-__attribute__((visibility("default"))) int md_ai_protect(const MdWorld* w, const MdState* s, const MdConfig* c, const float* weights,
-                                                        const float* noise, const float* actions, float save_level,
-                                                        unsigned char* takeover, unsigned char* expert_takeover, float* applied_out,
-                                                        unsigned char* flags_out, float* saver_out, void* stream) {
-    TRY(check_common(w, s, c));
-    NEED(weights); NEED(actions); NEED(takeover); NEED(expert_takeover); NEED(applied_out); NEED(flags_out);
-    TRY(need_fields(kExpertEntry | kProtectEntry, ALWAYS, w, s, c));
-    TRY(check_expert_config(c, "md_ai_protect"));
-    if ((uintptr_t)weights & 15) {
-        snprintf(g_err, sizeof g_err, "md_ai_protect: the packed weights must be 16-byte aligned");
-        return MD_EINVAL;
-    }
-    if (!(save_level >= 0.0f && save_level <= 1.0f)) {
-        snprintf(g_err, sizeof g_err, "md_ai_protect: save_level=%g is not in [0, 1]", (double)save_level);
-        return MD_EINVAL;
-    }
-    hipLaunchKernelGGL(ai_protect_kernel, dim3((c->n_envs + kExpM - 1) / kExpM), dim3(256), 0, (hipStream_t)stream, *w, *s, *c, weights,
-                       noise, actions, save_level, takeover, expert_takeover, applied_out, flags_out, saver_out);
-    return launch_status();
-}
-
-__attribute__((visibility("default"))) int md_expert_sense(const MdWorld* w, const MdState* s, const MdConfig* c, const float* weights,
-                                                          const float* beam_cs240, const float* noise, float* action_out, float* mlp_out,
-                                                          float* obs_out, void* stream) {
-    TRY(check_common(w, s, c));
-    NEED(weights); NEED(beam_cs240); NEED(action_out);
-    TRY(need_fields(kSenseEntry, ALWAYS, w, s, c));
-    if (((uintptr_t)weights & 15) || ((uintptr_t)beam_cs240 & 15)) {
-        snprintf(g_err, sizeof g_err, "md_expert_sense: %s must be 16-byte aligned",
-                 ((uintptr_t)weights & 15) ? "the packed weights" : "the beam table beam_cs240");
-        return MD_EINVAL;
-    }
-    if (c->traffic_mode == 4) {
-        snprintf(g_err, sizeof g_err, "md_expert_sense: not in scenario mode (traffic_mode 4): the expert's observation needs a road "
-                 "network's navigation");
-        return MD_EINVAL;
-    }
-    if (c->is_multi_agent && c->ma_kind == MD_MA_TOLLGATE) {
-        snprintf(g_err, sizeof g_err, "md_expert_sense: not in the tollgate env (ma_kind 1): its observation has no navigation dims");
-        return MD_EINVAL;
-    }
-    const int rows = c->n_envs * c->agents_per_env;
-    hipLaunchKernelGGL(expert_sense_kernel, dim3((rows + kExpM - 1) / kExpM), dim3(256), 0, (hipStream_t)stream, *w, *s, *c, weights,
-                       beam_cs240, noise, action_out, mlp_out, obs_out);
-    return launch_status();
-}
-
 __attribute__((visibility("default"))) int md_topdown(const MdWorld* w, const MdState* s, const MdConfig* c, const MdTopDown* td, void* stream) {
     TRY(check_common(w, s, c));
     NEED(td);
@@ -5864,180 +4205,6 @@ __attribute__((visibility("default"))) int md_topdown(const MdWorld* w, const Md
     const int vec = (block_bytes % 16 == 0) && (((uintptr_t)td->out & 15) == 0);
     if (td->norm_pixel) hipLaunchKernelGGL((topdown_kernel<true>), dim3(c->n_envs), dim3(256), lds, (hipStream_t)stream, *w, *s, *c, *td, vec);
     else hipLaunchKernelGGL((topdown_kernel<false>), dim3(c->n_envs), dim3(256), lds, (hipStream_t)stream, *w, *s, *c, *td, vec);
-    return launch_status();
-}
-
-__attribute__((visibility("default"))) int md_render(const MdWorld* w, const MdState* s, const MdConfig* c, const MdRender* r, void* stream) {
-    TRY(check_common(w, s, c));
-    NEED(r);
-    if (r->struct_size != (int32_t)sizeof(MdRender)) {
-        snprintf(g_err, sizeof g_err, "MdRender.struct_size=%d, library expects %d", r->struct_size, (int)sizeof(MdRender));
-        return MD_EABI;
-    }
-    NEED(r->env_ids); NEED(r->out); NEED(r->ring); NEED(r->cursor);
-    TRY(need_fields(kRenderEntry, ALWAYS | MULTI, w, s, c));
-    if (r->n_render < 1 || r->n_render > 65535) {
-        snprintf(g_err, sizeof g_err, "md_render: n_render=%d must lie in [1, 65535]", r->n_render);
-        return MD_EINVAL;
-    }
-    if (r->width < 1 || r->height < 1 || r->width > MD_RD_MAX_SIZE || r->height > MD_RD_MAX_SIZE) {
-        snprintf(g_err, sizeof g_err, "md_render: width=%d height=%d must lie in [1, MD_RD_MAX_SIZE=%d]", r->width, r->height, MD_RD_MAX_SIZE);
-        return MD_EINVAL;
-    }
-    if (!(r->scaling > 0.0f) || !(r->scaling <= 3.0e38f)) {
-        snprintf(g_err, sizeof g_err, "md_render: scaling=%g must be positive and finite", (double)r->scaling);
-        return MD_EINVAL;
-    }
-    if (r->num_stack < 1 || r->num_stack > MD_RD_MAX_STACK) {
-        snprintf(g_err, sizeof g_err, "md_render: num_stack=%d must lie in [1, MD_RD_MAX_STACK=%d]", r->num_stack, MD_RD_MAX_STACK);
-        return MD_EINVAL;
-    }
-    if (r->history_smooth < 0) {
-        snprintf(g_err, sizeof g_err, "md_render: history_smooth=%d must not be negative", r->history_smooth);
-        return MD_EINVAL;
-    }
-    if (r->track_agent < 0 || r->track_agent >= c->agents_per_env) {
-        snprintf(g_err, sizeof g_err, "md_render: track_agent=%d is no agent slot (agents_per_env=%d)", r->track_agent, c->agents_per_env);
-        return MD_EINVAL;
-    }
-    if (((uintptr_t)w->quads & 15) || ((uintptr_t)w->quad_ball & 15)) {     // read as float4 (quad_ball may be NULL)
-        snprintf(g_err, sizeof g_err, "md_render: MdWorld.%s must be 16-byte aligned", ((uintptr_t)w->quads & 15) ? "quads" : "quad_ball");
-        return MD_EINVAL;
-    }
-    if (w->n_maps <= 0) {
-        snprintf(g_err, sizeof g_err, "md_render: MdWorld.n_maps=%d", w->n_maps);
-        return MD_EINVAL;
-    }
-    const int tiles_x = (r->width + MD_RD_TILE - 1) / MD_RD_TILE, tiles_y = (r->height + MD_RD_TILE - 1) / MD_RD_TILE;
-    const int vec = (r->width % 16 == 0) && (((uintptr_t)r->out & 15) == 0);
-    hipLaunchKernelGGL(render_push_kernel, dim3(r->n_render), dim3(MD_MAX_CAP), 0, (hipStream_t)stream, *s, *c, *r);
-    hipLaunchKernelGGL(render_kernel, dim3(tiles_x * tiles_y, r->n_render), dim3(256), render_lds(r->num_stack, c->cap).bytes, (hipStream_t)stream,
-                       *w, *s, *c, *r, tiles_x, vec);
-    return launch_status();
-}
-
-__attribute__((visibility("default"))) int md_branch(const MdState* dst, const MdState* src, const MdConfig* c, const MdBranch* b, void* stream) {
-    NEED(dst); NEED(src); NEED(c); NEED(b);
-    TRY(check_struct_size(c));
-    if (b->struct_size != (int32_t)sizeof(MdBranch)) {
-        snprintf(g_err, sizeof g_err, "MdBranch.struct_size=%d, library expects %d", b->struct_size, (int)sizeof(MdBranch));
-        return MD_EABI;
-    }
-    NEED(b->src_row); NEED(b->dst_row);
-    if (c->cap <= 0 || c->cap > MD_MAX_CAP || c->agents_per_env <= 0 || c->agents_per_env > c->cap || c->obs_dim < 0 ||
-        c->route_seg_cap < 0 || c->route_vert_cap < 0) {
-        snprintf(g_err, sizeof g_err, "md_branch: bad sizes: cap=%d agents_per_env=%d obs_dim=%d route_seg_cap=%d route_vert_cap=%d (cap<=%d)",
-                 c->cap, c->agents_per_env, c->obs_dim, c->route_seg_cap, c->route_vert_cap, MD_MAX_CAP);
-        return MD_EINVAL;
-    }
-    if (b->n_pairs <= 0) {
-        snprintf(g_err, sizeof g_err, "md_branch: n_pairs=%d must be positive", b->n_pairs);
-        return MD_EINVAL;
-    }
-    if (b->src_n_envs <= 0 || b->dst_n_envs <= 0) {
-        snprintf(g_err, sizeof g_err, "md_branch: src_n_envs=%d and dst_n_envs=%d must be positive", b->src_n_envs, b->dst_n_envs);
-        return MD_EINVAL;
-    }
-    if (b->n_extras < 0 || b->n_extras > MD_BR_MAX_EXTRAS) {
-        snprintf(g_err, sizeof g_err, "md_branch: n_extras=%d must lie in [0, MD_BR_MAX_EXTRAS=%d]", b->n_extras, MD_BR_MAX_EXTRAS);
-        return MD_EINVAL;
-    }
-    for (int k = 0; k < b->n_extras; ++k) {
-        if (!b->extra[k].dst || !b->extra[k].src) {
-            snprintf(g_err, sizeof g_err, "required pointer b->extra[%d].%s is null", k, b->extra[k].dst ? "src" : "dst");
-            return MD_EINVAL;
-        }
-        if (b->extra[k].row_bytes <= 0) {
-            snprintf(g_err, sizeof g_err, "md_branch: extra[%d].row_bytes=%lld must be positive", k, (long long)b->extra[k].row_bytes);
-            return MD_EINVAL;
-        }
-    }
-    hipLaunchKernelGGL(branch_kernel, dim3(b->n_pairs), dim3(256), 0, (hipStream_t)stream, *dst, *src, *c, *b);
-    return launch_status();
-}
-
-__attribute__((visibility("default"))) int md_ped(const MdState* s, const MdConfig* c, const MdPed* p, void* stream) {
-    NEED(s); NEED(c); NEED(p);
-    TRY(check_struct_size(c));
-    if (p->struct_size != (int32_t)sizeof(MdPed)) {
-        snprintf(g_err, sizeof g_err, "MdPed.struct_size=%d, library expects %d", p->struct_size, (int)sizeof(MdPed));
-        return MD_EABI;
-    }
-    if (c->n_envs <= 0 || c->cap <= 0 || c->cap > MD_MAX_CAP || c->substeps <= 0 || !(c->dt > 0.0f)) {
-        snprintf(g_err, sizeof g_err, "md_ped: bad sizes: n_envs=%d cap=%d substeps=%d dt=%g (cap<=%d)", c->n_envs, c->cap, c->substeps,
-                 (double)c->dt, MD_MAX_CAP);
-        return MD_EINVAL;
-    }
-    if (p->wait_min_steps < 0) {
-        snprintf(g_err, sizeof g_err, "md_ped: wait_min_steps=%d must not be negative", p->wait_min_steps);
-        return MD_EINVAL;
-    }
-    TRY(need_fields(kPedEntry, ALWAYS, nullptr, s, c));
-    hipLaunchKernelGGL(ped_kernel, dim3((c->n_envs + kPedEnvs - 1) / kPedEnvs), dim3(64 * kPedEnvs), 0, (hipStream_t)stream, *s, *c, *p);
-    return launch_status();
-}
-
-__attribute__((visibility("default"))) int md_vector_obs(const MdWorld* w, const MdState* s, const MdConfig* c, const MdVectorObs* vo,
-                                                        void* stream) {
-    NEED(w); NEED(s); NEED(c); NEED(vo);
-    TRY(check_struct_size(c));
-    if (vo->struct_size != (int32_t)sizeof(MdVectorObs)) {
-        snprintf(g_err, sizeof g_err, "MdVectorObs.struct_size=%d, library expects %d", vo->struct_size, (int)sizeof(MdVectorObs));
-        return MD_EABI;
-    }
-    TRY(check_common(w, s, c));
-    const struct { const char* name; int v, lo, hi; const char* limit; } counts[] = {
-        {"num_agents", vo->num_agents, 1, MD_VO_MAX_AGENTS, "MD_VO_MAX_AGENTS"},
-        {"history", vo->history, 1, MD_VO_MAX_HISTORY, "MD_VO_MAX_HISTORY"},
-        {"route_points", vo->route_points, 0, MD_VO_MAX_ROUTE_POINTS, "MD_VO_MAX_ROUTE_POINTS"},
-        {"num_lanes", vo->num_lanes, 0, MD_VO_MAX_LANES, "MD_VO_MAX_LANES"},
-        {"lane_points", vo->lane_points, 2, MD_VO_MAX_LANE_POINTS, "MD_VO_MAX_LANE_POINTS"},
-    };
-    for (const auto& r : counts)
-        if (r.v < r.lo || r.v > r.hi) {
-            snprintf(g_err, sizeof g_err, "md_vector_obs: %s=%d must lie in [%d, %s=%d]", r.name, r.v, r.lo, r.limit, r.hi);
-            return MD_EINVAL;
-        }
-    const struct { const char* name; float v; } lengths[] = {{"radius", vo->radius}, {"max_jump", vo->max_jump},
-                                                             {"route_spacing", vo->route_spacing}};
-    for (const auto& r : lengths)
-        if (!(r.v > 0.0f) || !(r.v <= 1.0e18f)) {      // its square stays finite
-            snprintf(g_err, sizeof g_err, "md_vector_obs: %s=%g must be positive (and at most 1e18)", r.name, (double)r.v);
-            return MD_EINVAL;
-        }
-    if (vo->out_stride <= 0 || vo->out_stride % 16 || vo->hist_stride <= 0 || vo->hist_stride % 16) {
-        snprintf(g_err, sizeof g_err, "md_vector_obs: out_stride=%d and hist_stride=%d must be positive multiples of 16", vo->out_stride,
-                 vo->hist_stride);
-        return MD_EINVAL;
-    }
-    if (c->traffic_mode == 4) {
-        snprintf(g_err, sizeof g_err, "md_vector_obs: not in scenario mode (traffic_mode 4): it has no lane table and its routes are polylines");
-        return MD_EINVAL;
-    }
-    TRY(need_fields(kVectorObsEntry, ALWAYS | MULTI, w, s, c));
-    NEED(vo->agents); NEED(vo->agents_mask); NEED(vo->agents_meta); NEED(vo->ego); NEED(vo->ego_mask);
-    if (vo->route_points > 0) { NEED(vo->route); NEED(vo->route_mask); }
-    if (vo->num_lanes > 0) { NEED(vo->lanes); NEED(vo->lanes_meta); NEED(vo->lanes_mask); }
-    NEED(vo->ring_pose); NEED(vo->ring_flags); NEED(vo->cursor);
-    const void* const words[] = {vo->agents, vo->agents_meta, vo->ego, vo->route, vo->lanes, vo->lanes_meta, vo->ring_pose, vo->ring_flags,
-                                 vo->cursor};
-    for (const void* p : words)
-        if ((uintptr_t)p & 3) {
-            snprintf(g_err, sizeof g_err, "md_vector_obs: the float and int32 arrays of MdVectorObs must be 4-byte aligned");
-            return MD_EINVAL;
-        }
-    if (w->n_maps <= 0 || w->max_lanes <= 0) {
-        snprintf(g_err, sizeof g_err, "md_vector_obs: MdWorld.n_maps=%d max_lanes=%d", w->n_maps, w->max_lanes);
-        return MD_EINVAL;
-    }
-    const int n_waves = 3 * c->agents_per_env < kVoWaves ? 3 * c->agents_per_env : kVoWaves;
-    const size_t lds = (size_t)n_waves * vector_obs_lds(w->max_lanes).per_wave;
-    if (lds > 64 * 1024) {
-        snprintf(g_err, sizeof g_err, "md_vector_obs: the lane distances of %d waves need %zu B of LDS (max_lanes=%d); limit 65536", n_waves, lds,
-                 w->max_lanes);
-        return MD_EINVAL;
-    }
-    hipLaunchKernelGGL(vector_obs_kernel, dim3(c->n_envs), dim3(64 * n_waves), lds, (hipStream_t)stream, *w, *s, *c, *vo);
     return launch_status();
 }
 

@@ -1,4 +1,4 @@
-"""env.render(mode="topdown") on the device (include/md_render.h; mdstep.hip rasterises tile by tile in primitive order and settles
+"""env.render(mode="topdown") on the device (include/md_render.h; csrc/parts/render.inc rasterises tile by tile in primitive order and settles
 the painter's order through ranks) against the host build of the same header (tests/render_host.c, pixel order): after every call
 the state, MdWorld.env_map and the viewer's history are downloaded, the host build runs on them and the WHOLE output tensor, the
 ring and the cursors are compared bit for bit."""

@@ -1,4 +1,4 @@
-"""md_topdown on the device (include/md_topdown.h; mdstep.hip rasterises in primitive order into an LDS image) against the host
+"""md_topdown on the device (include/md_topdown.h; csrc/parts/topdown.inc rasterises in primitive order into an LDS image) against the host
 build of the same header (tests/topdown_host.c, pixel order): after every step the state and the history arrays are downloaded, the
 host build runs on them and the WHOLE tensor and the history it leaves are compared bit for bit.  Every env auto-resets inside the
 run; an env whose episode ended in a step is rendered on the map and the route it had in that step (MdWorld.env_map and

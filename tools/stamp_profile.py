@@ -3,7 +3,6 @@ library, runs the bench workload, prints per-phase cycle shares (mean / p50 / ma
 SHARES from it, never the run time of this build."""
 import ctypes as C
 import os
-import subprocess
 import sys
 from collections import OrderedDict
 
@@ -28,11 +27,9 @@ def main():
     out = os.path.join(ROOT, "gpurun_out", "libmdstep_stamp.so")
     if os.environ.get("MD_STAMP_LIB"):       # a -DMD_STAMP build made before: used as it is
         out = os.environ["MD_STAMP_LIB"]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
     if not os.environ.get("MD_STAMP_LIB"):
-        subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared",
-                               "-fvisibility=hidden", "-std=c++17", "-DMD_STAMP"] + os.environ.get("MD_EXTRA_FLAGS", "").split() + ["-I" + os.path.join(ROOT, "include"),
-                               os.path.join(ROOT, "metadrive_ped_amd", "csrc", "mdstep.hip"), "-o", out])
+        from __graft_entry__ import build_hip
+        build_hip(["-DMD_STAMP"] + os.environ.get("MD_EXTRA_FLAGS", "").split(), out)
     from metadrive_ped_amd import _lib
     _lib.LIB_PATH = out
     import torch

@@ -7,7 +7,6 @@ start on the same CU.  Read SHAPES from it (ramp, plateau, tail), never the run 
 """
 import ctypes as C
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,10 +16,8 @@ sys.path.insert(0, ROOT)
 def main():
     import numpy as np
     out = os.path.join(ROOT, "gpurun_out", "libmdstep_stamp.so")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared",
-                           "-fvisibility=hidden", "-std=c++17", "-DMD_STAMP"] + os.environ.get("MD_EXTRA_FLAGS", "").split() +
-                          ["-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "metadrive_ped_amd", "csrc", "mdstep.hip"), "-o", out])
+    from __graft_entry__ import build_hip
+    build_hip(["-DMD_STAMP"] + os.environ.get("MD_EXTRA_FLAGS", "").split(), out)
     from metadrive_ped_amd import _lib
     _lib.LIB_PATH = out
     from metadrive_ped_amd.config import make_config
