@@ -182,9 +182,11 @@ def record_episode(o, actions):
     return dict(shape=shape, dyn=dyn, seeds=list(o.host.seeds), cap=o.host.cap)
 
 
-def lidar_raw(shape, beam_cs, E, cap, n_beams, lidar_range):
-    """ref_lidar on a bare shape table (one agent per env in slot 0): the lidar micro-bench's checker."""
+def lidar_raw(shape, beam_cs, E, cap, n_beams, lidar_range, agents_per_env=1):
+    """ref_lidar on a bare shape table (the agents of an env in its first slots; rows [E * agents_per_env, n_beams]): the lidar
+    micro-bench's checker."""
     lib = load()
+    A = agents_per_env
     shape = np.ascontiguousarray(shape)
     beam_cs = np.ascontiguousarray(beam_cs, np.float32)
     w = abi.MdWorld()
@@ -194,10 +196,40 @@ def lidar_raw(shape, beam_cs, E, cap, n_beams, lidar_range):
     s.shape = shape.ctypes.data
     k = abi.MdConfig()
     k.struct_size = C.sizeof(abi.MdConfig)
-    k.n_envs, k.agents_per_env, k.cap, k.n_beams, k.obs_dim = E, 1, cap, n_beams, n_beams
+    k.n_envs, k.agents_per_env, k.cap, k.n_beams, k.obs_dim = E, A, cap, n_beams, n_beams
     k.lidar_range = lidar_range
-    out = np.zeros((E, n_beams), np.float32)
+    out = np.zeros((E * A, n_beams), np.float32)
     rc = lib.ref_lidar(C.byref(w), C.byref(s), C.byref(k), C.c_void_p(out.ctypes.data), n_beams, 0)
+    assert rc == 0
+    return out
+
+
+def bare_detector_structs(E, cap, A, ptr):
+    """MdWorld / MdState / MdConfig for the line detectors on bare tables: ptr(name) -> the address of quads, quad_kind, quad_off,
+    env_map, shape and (0 = NULL) quad_ball"""
+    w = abi.MdWorld()
+    w.n_maps, w.n_envs, w.max_lanes, w.max_roads = E, E, 1, 1
+    w.env_map, w.quad_off, w.quads, w.quad_kind = ptr("env_map"), ptr("quad_off"), ptr("quads"), ptr("quad_kind")
+    w.quad_ball = ptr("quad_ball") or None
+    s = abi.MdState()
+    s.shape = ptr("shape")
+    k = abi.MdConfig()
+    k.struct_size = C.sizeof(abi.MdConfig)
+    k.n_envs, k.agents_per_env, k.cap = E, A, cap
+    return w, s, k
+
+
+def line_detector_raw(world, beam_cs, rng, mask):
+    """ref_line_detector on bare tables (a dict of quads, quad_kind, quad_off, env_map, shape [E, cap]; the agents are the slots
+    0 .. cap-1) -> [E * cap, n]"""
+    lib = load()
+    held = {k: np.ascontiguousarray(v) for k, v in world.items()}
+    beam_cs = np.ascontiguousarray(beam_cs, np.float32)
+    E, cap = held["shape"].shape
+    w, s, k = bare_detector_structs(E, cap, cap, lambda name: held[name].ctypes.data if name in held else 0)
+    out = np.zeros((E * cap, len(beam_cs)), np.float32)
+    rc = lib.ref_line_detector(C.byref(w), C.byref(s), C.byref(k), C.c_void_p(beam_cs.ctypes.data), len(beam_cs), C.c_float(rng),
+                               C.c_uint32(mask), C.c_void_p(out.ctypes.data), len(beam_cs), 0)
     assert rc == 0
     return out
 
