@@ -220,33 +220,68 @@ typedef struct MdObsCtx {
     int cur_block; /* navigation.current_road.block_ID() */
 } MdObsCtx;
 
-MD_HD void md_observe_ctx(const MdLane* lanes, const MdRoad* roads, const MdState* s, int n, MdObsCtx* k) {
-    const MdShape* sh = &s->shape[n];
-    const MdNav* nav = &s->nav[n];
-    k->valid = md_drives(sh->flags) && nav->lane >= 0;
-    k->lane = k->ref0 = k->ref_last = k->next0 = k->fin = k->rl = lanes;
-    k->cur_w = k->cur_n = k->positive_road = 0.0f;
-    k->cur_block = 0;
-    if (!k->valid) return;
-    const MdRoad* cur_road = &roads[nav->road0];
-    k->cur_block = cur_road->block_kind;
-    int has_next = nav->ck1 != nav->ck0;
-    const MdRoad* next_road = has_next ? &roads[nav->road1] : cur_road;
-    k->lane = &lanes[nav->lane];
-    k->ref0 = &lanes[cur_road->first_lane];
-    k->ref_last = &lanes[cur_road->first_lane + cur_road->n_lanes - 1];
-    k->next0 = &lanes[next_road->first_lane];
-    k->fin = &lanes[s->final_lane[n]];
-    k->cur_w = k->lane->width; /* get_current_lane_width = current_lane.width */
-    k->cur_n = (float)cur_road->n_lanes;
-    /* reward lane (metadrive_env.py:248-254) */
-    k->positive_road = 1.0f;
-    if (k->lane->road == nav->road0) k->rl = k->lane;
-    else {
-        k->rl = k->ref0;
-        k->positive_road = cur_road->negative ? -1.0f : 1.0f;
-    }
+/* What the context reads of the vehicle's MdNav, as a copy: the context (and with it the nine task results) is a function of
+ * these five words, the slot's shape flags and final lane, the pose and the map.  The lean step kernel evaluates context and
+ * tasks from such a copy while the localisation may still commit, and keeps the result iff the committed words equal the
+ * copy (md_obs_key_same): csrc/mdstep.hip, the locate stage. */
+typedef struct MdObsKey {
+    int32_t lane, road0, road1, ck0, ck1;
+} MdObsKey;
+#define MD_OBS_KEY_WORDS 5
+
+MD_HD void md_obs_key_of(const MdNav* nav, MdObsKey* q) {
+    q->lane = nav->lane;
+    q->road0 = nav->road0;
+    q->road1 = nav->road1;
+    q->ck0 = nav->ck0;
+    q->ck1 = nav->ck1;
 }
+
+MD_HD int md_obs_key_same(const MdObsKey* q, const MdNav* nav) {
+    return q->lane == nav->lane && q->road0 == nav->road0 && q->road1 == nav->road1 && q->ck0 == nav->ck0 && q->ck1 == nav->ck1;
+}
+
+/* The context's body, once, for both holders of the navigation words: NAV points at an MdNav or at an MdObsKey (the five fields
+ * have the same names), and nothing else of the navigation is read.  Expanded by both rather than md_observe_ctx copying the
+ * key and calling md_observe_ctx_of: the copy loads all five words ahead of the `valid` test, which shifted the register
+ * allocation of step kernels that were to stay as they are (EXPERIMENTS.md, "Observation tasks beside the localisation"). */
+#define MD_OBSERVE_CTX_BODY(NAV)                                                                    \
+    const MdShape* sh = &s->shape[n];                                                               \
+    k->valid = md_drives(sh->flags) && (NAV)->lane >= 0;                                            \
+    k->lane = k->ref0 = k->ref_last = k->next0 = k->fin = k->rl = lanes;                            \
+    k->cur_w = k->cur_n = k->positive_road = 0.0f;                                                  \
+    k->cur_block = 0;                                                                               \
+    if (!k->valid) return;                                                                          \
+    const MdRoad* cur_road = &roads[(NAV)->road0];                                                  \
+    k->cur_block = cur_road->block_kind;                                                            \
+    int has_next = (NAV)->ck1 != (NAV)->ck0;                                                        \
+    const MdRoad* next_road = has_next ? &roads[(NAV)->road1] : cur_road;                           \
+    k->lane = &lanes[(NAV)->lane];                                                                  \
+    k->ref0 = &lanes[cur_road->first_lane];                                                         \
+    k->ref_last = &lanes[cur_road->first_lane + cur_road->n_lanes - 1];                             \
+    k->next0 = &lanes[next_road->first_lane];                                                       \
+    k->fin = &lanes[s->final_lane[n]];                                                              \
+    k->cur_w = k->lane->width; /* get_current_lane_width = current_lane.width */                    \
+    k->cur_n = (float)cur_road->n_lanes;                                                            \
+    /* reward lane (metadrive_env.py:248-254) */                                                    \
+    k->positive_road = 1.0f;                                                                        \
+    if (k->lane->road == (NAV)->road0) k->rl = k->lane;                                             \
+    else {                                                                                          \
+        k->rl = k->ref0;                                                                            \
+        k->positive_road = cur_road->negative ? -1.0f : 1.0f;                                       \
+    }
+
+/* The context of slot n with the navigation words taken from `q` and from nowhere else (s->nav is not read). */
+MD_HD void md_observe_ctx_of(const MdLane* lanes, const MdRoad* roads, const MdState* s, int n, const MdObsKey* q, MdObsCtx* k) {
+    MD_OBSERVE_CTX_BODY(q)
+}
+
+/* ... and from the slot's own MdNav, read where the body uses them: the same as md_observe_ctx_of on md_obs_key_of(&s->nav[n]) */
+MD_HD void md_observe_ctx(const MdLane* lanes, const MdRoad* roads, const MdState* s, int n, MdObsCtx* k) {
+    const MdNav* nav = &s->nav[n];
+    MD_OBSERVE_CTX_BODY(nav)
+}
+#undef MD_OBSERVE_CTX_BODY
 
 MD_HD void md_observe_task(int task, const MdObsCtx* k, const MdState* s, const MdConfig* c, int n, float* out5) {
     const MdShape* sh = &s->shape[n];
@@ -497,9 +532,13 @@ MD_HD void md_observe_lane(int lane, const MdObsCtx* k, const MdState* s, const 
 }
 
 /* dist to left/right of the route (base_vehicle.py:491-499) from the lateral on the current road's first lane */
+MD_HD void md_route_borders_of(float cur_w, float cur_n, const float (*r)[5], float* to_left, float* to_right) {
+    *to_left = r[0][1] + cur_w / 2.0f;
+    *to_right = cur_w * cur_n - *to_left;
+}
+
 MD_HD void md_route_borders(const MdObsCtx* k, const float (*r)[5], float* to_left, float* to_right) {
-    *to_left = r[0][1] + k->cur_w / 2.0f;
-    *to_right = k->cur_w * k->cur_n - *to_left;
+    md_route_borders_of(k->cur_w, k->cur_n, r, to_left, to_right);
 }
 
 /* The dims of slot n's observation row that precede the "others" block, [0, md_obs_others(c)), under the layout of `c`:
@@ -508,11 +547,11 @@ MD_HD void md_route_borders(const MdObsCtx* k, const float (*r)[5], float* to_le
  * the caller's to write.  Dims that a side / lane-line detector of `c` owns are left alone.  Reads the state, writes nothing
  * but `obs`: md_observe_combine calls it for the env's own row, the expert's own sensors (md_expert_sense) for a row under
  * the expert's layout. */
-MD_HD void md_observe_state_dims(const MdObsCtx* k, const MdState* s, const MdConfig* c, int n, const float (*r)[5], float* obs) {
+MD_HD void md_observe_state_dims_of(float cur_w, float cur_n, const MdState* s, const MdConfig* c, int n, const float (*r)[5], float* obs) {
     const MdDyn* d = &s->dyn[n];
     const int o_mid = md_obs_mid(c), o_ll = md_obs_ll(c), o_navi = md_obs_navi(c);
     float to_left, to_right;
-    md_route_borders(k, r, &to_left, &to_right);
+    md_route_borders_of(cur_w, cur_n, r, &to_left, &to_right);
     /* ---- state obs (obs/state_obs.py:64-151) ---- */
     float speed_kmh = md_fabs(d->speed) * 3.6f;
     const MdParam* P = &s->param[n];
@@ -541,8 +580,24 @@ MD_HD void md_observe_state_dims(const MdObsCtx* k, const MdState* s, const MdCo
         }
 }
 
-MD_HD void md_observe_combine(const MdObsCtx* k, const MdState* s, const MdConfig* c, int a, int env_just_reset,
-                              const float (*r)[5]) {
+MD_HD void md_observe_state_dims(const MdObsCtx* k, const MdState* s, const MdConfig* c, int n, const float (*r)[5], float* obs) {
+    md_observe_state_dims_of(k->cur_w, k->cur_n, s, c, n, r, obs);
+}
+
+/* What the combine needs of the context: a few words, so that the wave that evaluated the context can hand them to the wave
+ * that combines (the lean step kernel: through LDS).  The two words of lane records stay behind pointers and are read where
+ * the combine uses them -- the speed limit under the tollgate rules only -- so a caller points them at the records
+ * (md_observe_combine) or at copies of the words. */
+typedef struct MdObsHand {
+    int valid;
+    float cur_w, cur_n, positive_road;
+    int cur_block;
+    const float* fin_length;        /* &ctx.fin->length */
+    const float* lane_speed_limit;  /* &ctx.lane->speed_limit: MultiAgentTollgateEnv only */
+} MdObsHand;
+
+MD_HD void md_observe_combine_of(const MdObsHand* k, const MdState* s, const MdConfig* c, int a, int env_just_reset,
+                                 const float (*r)[5]) {
     int n = a;
     /* a vehicle (re)spawned at the start of this step only reports its first observation
      * (multi_agent_metadrive.py:190-212: new_obs, reward 0, not terminated) */
@@ -566,20 +621,20 @@ MD_HD void md_observe_combine(const MdObsCtx* k, const MdState* s, const MdConfi
     float cur_w = k->cur_w, cur_n = k->cur_n;
 
     float to_left, to_right;
-    md_route_borders(k, r, &to_left, &to_right);
+    md_route_borders_of(k->cur_w, k->cur_n, r, &to_left, &to_right);
     uint32_t fl = s->flags[n] & (MD_FL_CRASH_VEHICLE | MD_FL_CRASH_OBJECT | MD_FL_CRASH_HUMAN | MD_FL_CRASH_BUILDING |
                                  MD_FL_CRASH_SIDEWALK | MD_FL_ON_WHITE_CONT | MD_FL_ON_YELLOW_CONT | MD_FL_ON_BROKEN |
                                  MD_FL_ON_CROSSWALK | MD_FL_ON_LANE);
     if (to_right < 0.0f || to_left < 0.0f) fl |= MD_FL_OUT_OF_ROUTE;
 
-    md_observe_state_dims(k, s, c, n, r, obs);
+    md_observe_state_dims_of(k->cur_w, k->cur_n, s, c, n, r, obs);
     float speed_kmh = md_fabs(d->speed) * 3.6f;
     const MdParam* P = &s->param[n];
     float ls = r[2][0], llat = r[2][1];
 
     /* ---- arrive destination (metadrive_env.py:213-227) ---- */
     float fs = r[5][0], flat = r[5][1];
-    int arrive = (k->fin->length - 5.0f < fs) && (fs < k->fin->length + 5.0f) && (cur_w / 2.0f >= flat) &&
+    int arrive = (*k->fin_length - 5.0f < fs) && (fs < *k->fin_length + 5.0f) && (cur_w / 2.0f >= flat) &&
                  (flat >= (0.5f - cur_n) * cur_w);
     /* ---- out of road (metadrive_env.py:229-237) ---- */
     int out_of_road = !(fl & MD_FL_ON_LANE);
@@ -610,7 +665,7 @@ MD_HD void md_observe_combine(const MdObsCtx* k, const MdState* s, const MdConfi
                  * block the speed term gives way to a penalty that REPLACES the reward while lane.speed_limit < speed [km/h] */
         reward += c->driving_reward * (long_now - long_last) * lateral_factor;
         if (k->cur_block == '$') {
-            if (k->lane->speed_limit < speed_kmh) reward = -c->overspeed_penalty * speed_kmh / P->max_speed_kmh;
+            if (*k->lane_speed_limit < speed_kmh) reward = -c->overspeed_penalty * speed_kmh / P->max_speed_kmh;
         } else reward += c->speed_reward * (speed_kmh / P->max_speed_kmh);
     } else {
         reward += c->driving_reward * (long_now - long_last) * lateral_factor * positive_road;
@@ -727,6 +782,12 @@ MD_HD void md_observe_combine(const MdObsCtx* k, const MdState* s, const MdConfi
     info[7] = (float)nav->steps;
     if (c->auto_reset && !c->is_multi_agent && !just_reset && (fl & (MD_FL_TERMINATED | MD_FL_TRUNCATED)))
         s->need_reset[0] = 1;
+}
+
+MD_HD void md_observe_combine(const MdObsCtx* k, const MdState* s, const MdConfig* c, int a, int env_just_reset,
+                              const float (*r)[5]) {
+    const MdObsHand h = {k->valid, k->cur_w, k->cur_n, k->positive_road, k->cur_block, &k->fin->length, &k->lane->speed_limit};
+    md_observe_combine_of(&h, s, c, a, env_just_reset, r);
 }
 
 /* serial form (oracle): all tasks, then combine */

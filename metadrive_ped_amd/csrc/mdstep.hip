@@ -95,10 +95,23 @@ __device__ const int* g_env_order = nullptr;
             if (hit) atomicAdd(&g_stamp_buf[(size_t)blockIdx.x * 32 + 16 + 13], 1ull);         \
         }                                                                                      \
     } while (0)
+// the lean kernel's observation ahead (observe_ahead_wave): start / end of the evaluation in stamp slots 2 / 5, which that kernel does
+// not write otherwise, by the lane that `cond` picks; its counts per env above the localisations in fine slot 12, a byte each
+#define MD_AHEAD_STAMP(cond, i)                                                                \
+    do {                                                                                       \
+        if ((cond) && g_stamp_buf) g_stamp_buf[(size_t)blockIdx.x * 32 + (i)] = __builtin_readcyclecounter(); \
+    } while (0)
+enum : int { MD_AHEAD_EVALUATED = 32, MD_AHEAD_HIT = 40, MD_AHEAD_MISS = 48 };
+#define MD_AHEAD_COUNT(cond, what)                                                             \
+    do {                                                                                       \
+        if ((cond) && g_stamp_buf) atomicAdd(&g_stamp_buf[(size_t)blockIdx.x * 32 + 16 + 12], 1ull << (what)); \
+    } while (0)
 #else
 #define MD_STAMP_AT(i) do { } while (0)
 #define MD_FINE_STAMP(cond, i) do { } while (0)
 #define MD_LOC_COUNT(cond, hit) do { } while (0)
+#define MD_AHEAD_STAMP(cond, i) do { } while (0)
+#define MD_AHEAD_COUNT(cond, what) do { } while (0)
 #endif
 // Diagnostic builds only (tools/ab/env_knockout.sh): stages of the fused env kernel left out to read their marginal cost off the
 // launch time.  0 in the product.
@@ -1637,11 +1650,87 @@ __device__ __forceinline__ void idm_group_wave(const MdWorld& w, const MdLane* l
 // One agent per wave (`a` wave-uniform: its context lives in scalar registers) -- the single-agent envs' form.
 // kLockstep (the lean kernel): the tasks as md_observe_lane, sixteen lanes on one straight-line sequence of three square
 // roots and three quotients instead of nine lanes on four bodies run one after the other; same 45 words in the scratch.
-template <bool kLockstep = false>
+//
+// The observation AHEAD (the lean kernel; -DMD_OBS_AHEAD=0 compiles it out).  In an env whose locate stage leaves a wave without an item
+// (one or two driving vehicles: localisations + the agent's contacts < the waves), that wave evaluates agent 0's context and tasks
+// DURING the locate stage (observe_ahead_wave) into wave 0's observe scratch, which nothing touches before the observe stage.  All
+// they read is final by then but five words of the agent's MdNav (MdObsKey), which the localisation on wave 0 may be committing at
+// that moment.  The ahead wave reads each of the five ONCE into registers, evaluates from those registers and stores the same
+// registers beside the results; wave 0, behind the stage barriers, keeps the results iff the stored words equal the committed
+// ones.  A torn read is harmless: every word read is the old or the new value of that word (valid indices both), context and
+// results are a pure function of the words read, and a mix of old and new that differs from the committed key is a miss like any
+// other.  On a hit wave 0 goes straight to the combine, with the few context words it needs (MdObsHand) from the scratch too.
+// The hand-over's words in wave 0's 48-word scratch: 45 .. 47 and result slots that md_observe_combine_of never reads (tasks 0 and 2
+// have two results, task 1 one; md_observe_lane writes only the words that are results):
+enum ObsAheadWord : int {
+    kAhMark = 45,                                                          // evaluated in this step (zeroed at stage-in)
+    kAhLane = 46, kAhRoad0 = 47, kAhRoad1 = 2, kAhCk0 = 3, kAhCk1 = 4,     // the MdObsKey the evaluation used
+    kAhValid = 6, kAhCurW = 7, kAhCurN = 8, kAhPosRoad = 9, kAhFinLen = 12 // MdObsHand (cur_block, the speed limit: tollgate envs only)
+};
+#ifndef MD_OBS_AHEAD
+#define MD_OBS_AHEAD 1
+#endif
+__device__ __forceinline__ void observe_ahead_wave(const MdLane* lanes, const MdRoad* roads, const MdState& s, const MdConfig& c, int lane_id,
+                                                   float* scratch0 /* wave 0's observe scratch */) {
+    constexpr int a = 0;
+    MD_AHEAD_STAMP(lane_id == 0, 2);
+    // volatile: one load per word, never made again
+    const volatile int32_t* nv = reinterpret_cast<const volatile int32_t*>(&s.nav[a]);
+    MdObsKey q;
+    q.lane = __builtin_amdgcn_readfirstlane(nv[offsetof(MdNav, lane) / 4]);
+    q.road0 = __builtin_amdgcn_readfirstlane(nv[offsetof(MdNav, road0) / 4]);
+    q.road1 = __builtin_amdgcn_readfirstlane(nv[offsetof(MdNav, road1) / 4]);
+    q.ck0 = __builtin_amdgcn_readfirstlane(nv[offsetof(MdNav, ck0) / 4]);
+    q.ck1 = __builtin_amdgcn_readfirstlane(nv[offsetof(MdNav, ck1) / 4]);
+    MdObsCtx k;
+    md_observe_ctx_of(lanes, roads, &s, a, &q, &k);
+    if (lane_id < MD_OBS_TASKS * 5) scratch0[lane_id] = 0.0f;
+    md_observe_lane(lane_id, &k, &s, &c, a, scratch0);
+    if (lane_id == 0) {   // behind the lanes' results (an LDS unit runs a wave's writes in order)
+        int* w = reinterpret_cast<int*>(scratch0);
+        w[kAhLane] = q.lane;
+        w[kAhRoad0] = q.road0;
+        w[kAhRoad1] = q.road1;
+        w[kAhCk0] = q.ck0;
+        w[kAhCk1] = q.ck1;
+        w[kAhValid] = k.valid;
+        scratch0[kAhCurW] = k.cur_w;
+        scratch0[kAhCurN] = k.cur_n;
+        scratch0[kAhPosRoad] = k.positive_road;
+        scratch0[kAhFinLen] = k.fin->length;
+        w[kAhMark] = 1;
+    }
+    MD_AHEAD_COUNT(lane_id == 0, MD_AHEAD_EVALUATED);
+    MD_AHEAD_STAMP(lane_id == 0, 5);
+}
+
+// kAhead: agent 0's results may stand in the scratch already (above)
+template <bool kLockstep = false, bool kAhead = false>
 __device__ __forceinline__ void observe_agent_wave1(const MdLane* lanes, const MdRoad* roads, const MdState& s, const MdConfig& c, int a,
                                     int just_reset, int lane_id, float* wave_scratch /* LDS, MD_OBS_TASKS*5 floats */) {
     MdObsCtx k;
     MD_FINE_STAMP(a == 0 && lane_id == 0, 8);
+    if constexpr (kAhead) {
+        if (a == 0) {
+            const int* w = reinterpret_cast<const int*>(wave_scratch);
+            const MdObsKey q = {w[kAhLane], w[kAhRoad0], w[kAhRoad1], w[kAhCk0], w[kAhCk1]};
+            const int hit = w[kAhMark] != 0 && md_obs_key_same(&q, &s.nav[a]);
+            if (__builtin_amdgcn_readfirstlane(hit)) {
+                MD_AHEAD_COUNT(lane_id == 0, MD_AHEAD_HIT);
+                MD_FINE_STAMP(lane_id == 0, 9);
+                MD_FINE_STAMP(lane_id == 0, 10);
+                if (lane_id == 0) {
+                    const MdObsHand h = {w[kAhValid], wave_scratch[kAhCurW], wave_scratch[kAhCurN], wave_scratch[kAhPosRoad], 0,
+                                         &wave_scratch[kAhFinLen], nullptr};
+                    md_observe_combine_of(&h, &s, &c, a, just_reset, (const float (*)[5])wave_scratch);
+                }
+                __builtin_amdgcn_wave_barrier();
+                MD_FINE_STAMP(lane_id == 0, 11);
+                return;
+            }
+            MD_AHEAD_COUNT(lane_id == 0, MD_AHEAD_MISS);
+        }
+    }
     md_observe_ctx(lanes, roads, &s, a, &k);
     MD_FINE_STAMP(a == 0 && lane_id == 0, 9);
     if constexpr (kLockstep) {
@@ -2042,6 +2131,7 @@ __host__ __device__ inline EnvLds env_lds(int cap, int agents, int n_lanes, int 
     L.lanes = align_up(L.flags + (uint32_t)cap * sizeof(uint32_t), 16);  // map tables: copy16
     L.roads = L.lanes + (uint32_t)n_lanes * sizeof(MdLane);
     L.scratch = L.roads + (uint32_t)n_roads * sizeof(MdRoad);         // [waves][kObsScratch or 48] floats: per-wave observe results
+                                                                     // (lean kernel: wave 0's 48 also carry the observation ahead's hand-over, ObsAheadWord)
     L.param = L.scratch + (uint32_t)waves * (multi ? kObsScratch : 48) * sizeof(float);   // 16-B aligned like the map tables
     L.final_lane = L.param + (uint32_t)cap * sizeof(MdParam);
     L.det = L.final_lane + align_up(cap, 2) * sizeof(int32_t);      // [agents][2] detected sets (8-B aligned)
@@ -2072,6 +2162,8 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     constexpr bool kLocRoadFirst = PH == PH_ALL ? kIdmKeys : PH == PH_LOCALIZE_ROAD_FIRST;
     // the agent's observation tasks in lock-step (md_observe_lane): the lean kernel only
     constexpr bool kObsLockstep = MD_OBS_LOCKSTEP && PH == PH_ALL && kIdmKeys;
+    // ... and ahead, by a wave that the locate stage leaves without an item (observe_ahead_wave): the lean kernel only
+    constexpr bool kObsAhead = MD_OBS_AHEAD && kObsLockstep && kWaves > 1;
     // The lean launch: variant<PH_ALL>() guarantees the pins.  Not in the staged-map kernel: folded, its scratch grows from 16 to
     // 80 B per lane (EXPERIMENTS.md, "Lean kernels fold what their launch pins"), so it keeps reading the fields.
     if constexpr (PH == PH_ALL && !RESPAWN && !MULTI && !STAGE_MAP) lean_pins_fold(g, c);
@@ -2241,6 +2333,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         s.shape = l_shape;
     }
     if ((MULTI || PH == PH_ALL) && tid == 0) l_tk[0] = l_tk[1] = l_tk[2] = 0;
+    if (kObsAhead && tid == 0) reinterpret_cast<int*>(smem + L.scratch)[kAhMark] = 0;   // wave 0's scratch: nothing evaluated ahead yet
     __syncthreads();
     MD_STAMP_AT(1);
     // Lean kernel: the search half of the next step's trigger runs here, on the last wave, which owns no slot of the integrate
@@ -2337,6 +2430,12 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
                     if (!(MD_ENV_SKIP & 4)) localize_vehicle<kLocRoadFirst>(w, lanes, roads, s, e, kth_bit(drv_lo, drv_hi, item), lane, l_onlane);
                 } else if (!(MD_ENV_SKIP & 8)) contacts_vehicle(w, s, c, e, kth_bit(adrv_lo, adrv_hi, item - nd), lane, l_cfl);
             }
+            // the first wave without an item: agent 0's observation context and tasks from the navigation words as they stand,
+            // into wave 0's scratch (the last wave is free here too: its trigger fires behind this stage's barrier)
+            if constexpr (kObsAhead) {
+                if (nd + na < kWaves && wave == nd + na && !(MD_ENV_SKIP & 16))
+                    observe_ahead_wave(lanes, roads, s, c, lane, reinterpret_cast<float*>(smem + L.scratch));
+            }
         } else {
             // many vehicles awake: two localisations per wave (32 lanes each), halving the rounds
             const int npair = (nd + 1) >> 1;
@@ -2398,7 +2497,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         // disjoint from what observe writes -- obs, reward, the agent's flags / steps / energy).
         if (wave == 0) {
             if (!(MD_ENV_SKIP & 16))
-                for (int a = 0; a < c.agents_per_env; ++a) observe_agent_wave1<kObsLockstep>(lanes, roads, s, c, a, just_reset, lane, l_scratch);
+                for (int a = 0; a < c.agents_per_env; ++a) observe_agent_wave1<kObsLockstep, kObsAhead>(lanes, roads, s, c, a, just_reset, lane, l_scratch);
         } else if (!(MD_ENV_SKIP & 2)) {
             // the driving traffic vehicles by RANK, not by slot: dealt by slot (j = A + wave - 1, + kWaves - 1, ...) two of an env's
             // two or three vehicles meet on one wave in every third env while another wave idles

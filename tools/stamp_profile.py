@@ -77,6 +77,12 @@ def main():
     torch.cuda.synchronize()
     raw = buf.cpu().numpy().reshape(E, 32)
     st = raw[:, :12].astype(np.int64)
+    # the lean workgroup kernel never writes stamps 2 and 5; its ahead evaluation of the agent's observation (locate stage) leaves
+    # its start / end there.  Told apart from the idm-first variants' stamp 2 by its place: after stamp 4, not before stamp 3.
+    ahead = (st[:, 2] > st[:, 4]) & (st[:, 5] > st[:, 2])
+    ah0, ah1 = np.where(ahead, st[:, 2], 0), np.where(ahead, st[:, 5], 0)
+    if (st[:, 2] > st[:, 4]).any():
+        st[:, 2] = st[:, 5] = 0
     for i in range(1, 11):                          # a stamp that was not written takes the one before it
         st[:, i] = np.where(st[:, i] == 0, st[:, i - 1], st[:, i])
     fine = raw[:, 16:].astype(np.int64)
@@ -97,6 +103,9 @@ def main():
       print("localize(agent) fine: grid+cell loads %.0f | items+AABB %.0f | hull tests+frenet %.0f  (p50 cycles); candidates p50 %d, cell items p50 %d" % (
         np.median(lf[:, 1] - lf[:, 0]), np.median(lf[:, 2] - lf[:, 1]), np.median(lf[:, 3] - lf[:, 2]),
         np.median(lf[:, 15] & 0xffffffff), np.median(lf[:, 15] >> 32)))
+    # fine slot 12: the localisations in its low half; above them the ahead evaluation's counts (evaluated, hit, miss: a byte each)
+    ah_eval, ah_hit, ah_miss = (fine[:, 12] >> 32) & 0xff, (fine[:, 12] >> 40) & 0xff, (fine[:, 12] >> 48) & 0xff
+    fine[:, 12] &= 0xffffffff
     if fine[:, 12].sum():
         print("localisations of the stamped step: %d, answered by the road-first path: %d (%.1f %%)" % (
             fine[:, 12].sum(), fine[:, 13].sum(), 100.0 * fine[:, 13].sum() / fine[:, 12].sum()))
@@ -141,6 +150,26 @@ def main():
         if m_.sum() >= 5:
             print("driving %2d: %5d envs  life %.1f us | locate %6.0f | observe||idm %6.0f | wait idm %6.0f | total %6.0f cycles (means)" % (
                 k_, m_.sum(), life[m_].mean(), d[m_, 5].mean(), d[m_, 7].mean(), d[m_, 9].mean(), tot[m_].mean()))
+    # the agent's observation against its localisation, per class: what an evaluation beside the localisation has to fit into
+    obs_ok = (fine[:, 8] > 0) & (fine[:, 11] > fine[:, 8])
+    loc_ok = (fine[:, 0] > 0) & (fine[:, 3] > fine[:, 0])
+    if ah_eval.sum() or ah_miss.sum():
+        print("observation ahead: evaluated in %d envs (%.1f %%), kept (hit) in %d (%.1f %%), evaluated by wave 0 (miss) in %d (%.1f %%)" % (
+            ah_eval.sum(), 100.0 * ah_eval.sum() / E, ah_hit.sum(), 100.0 * ah_hit.sum() / E, ah_miss.sum(), 100.0 * ah_miss.sum() / E))
+    for k_ in range(1, int(drv.max()) + 1):
+        m_ = (drv == k_) & obs_ok & loc_ok
+        if m_.sum() < 5:
+            continue
+        ct, ob_ = (fine[:, 10] - fine[:, 8])[m_], (fine[:, 11] - fine[:, 8])[m_]
+        print("driving %2d: context + tasks p50 %6.0f p99 %6.0f | observe(agent) p50 %6.0f p99 %6.0f | localize(agent) p50 %6.0f | locate stage p50 %6.0f | observe||idm stage p50 %6.0f p99 %6.0f" % (
+            k_, np.median(ct), np.percentile(ct, 99), np.median(ob_), np.percentile(ob_, 99), np.median((fine[:, 3] - fine[:, 0])[m_]),
+            np.median(d[m_, 5]), np.median(d[m_, 7]), np.percentile(d[m_, 7], 99)))
+        a_ = m_ & ahead
+        if a_.sum() >= 5:
+            ln = (ah1 - ah0)[a_]
+            print("            ahead evaluation in %5d envs: p50 %6.0f p99 %6.0f cycles; ends after wave 0's localisation in %d, after the locate barrier (stamp 6) in %d; hit %d  miss %d" % (
+                a_.sum(), np.median(ln), np.percentile(ln, 99), (ah1[a_] > fine[a_, 3]).sum(), (ah1[a_] > st[a_, 6]).sum(),
+                ah_hit[m_].sum(), ah_miss[m_].sum()))
     idx = np.argsort(tot)[-3:]
     for i in idx:
         print("slow env", i, "drv", drv[i], "phases", d[i].tolist())
