@@ -178,6 +178,21 @@ MD_HD int md_obb_quad(float ax, float ay, float ac, float as, float ahl, float a
     return 1;
 }
 
+/* Flat pass over the items of up to four grid cells (the lean step kernel's contacts): item `flat` of the cells' ranges laid
+ * end to end, n0 .. n3 items in cells 0 .. 3 (each >= 0; cells past the last one hold 0) -> the cell it lies in, its offset there
+ * in *off.  Walking flat = 0 .. n0 + n1 + n2 + n3 - 1 visits (cell, offset) as the nested loops do: cell by cell, offsets
+ * ascending, empty cells passed over.  Past the total: -1. */
+MD_HD int md_flat_cell_item(int n0, int n1, int n2, int n3, int flat, int* off) {
+    int cell = 0, o = flat;
+    if (o >= n0) { o -= n0; cell = 1;
+        if (o >= n1) { o -= n1; cell = 2;
+            if (o >= n2) { o -= n2; cell = 3;
+                if (o >= n3) { o -= n3; cell = -1; } } } }
+    if (flat < 0) cell = -1;
+    *off = o;
+    return cell;
+}
+
 /* point in convex polygon (CCW), boundary inclusive.  Stands in for Bullet's vertical rayTestAll
  * against the lane's BulletConvexHullShape (utils/pg/utils.py:174, block/base_block.py:431-468). */
 MD_HD int md_point_in_hull(float x, float y, const float* xy, int n) {

@@ -106,7 +106,24 @@ enum : int { MD_AHEAD_EVALUATED = 32, MD_AHEAD_HIT = 40, MD_AHEAD_MISS = 48 };
     do {                                                                                       \
         if ((cond) && g_stamp_buf) atomicAdd(&g_stamp_buf[(size_t)blockIdx.x * 32 + 16 + 12], 1ull << (what)); \
     } while (0)
+// the contacts of the agent in slot 0 (contacts_vehicle), in a buffer of their own (md_debug_set_contacts_buffer: 8 words per env; the 32
+// above are all taken; zeroed by the caller before the stamped step): 0 / 1 start / end of the mover loop, 2 the end of the quads part
+// (grid header to the last cell's items), 4 the grid cells under the chassis, 5 the cell items read (both added up, by one lane)
+__device__ unsigned long long* g_contacts_buf = nullptr;
+#define MD_CONTACTS_STAMP(cond, i)                                                             \
+    do {                                                                                       \
+        if ((cond) && g_contacts_buf) g_contacts_buf[(size_t)blockIdx.x * 8 + (i)] = __builtin_readcyclecounter(); \
+    } while (0)
+#define MD_CONTACTS_COUNT(cond, cells, items)                                                  \
+    do {                                                                                       \
+        if ((cond) && g_contacts_buf) {                                                        \
+            g_contacts_buf[(size_t)blockIdx.x * 8 + 4] += (unsigned long long)(cells);         \
+            g_contacts_buf[(size_t)blockIdx.x * 8 + 5] += (unsigned long long)(items);         \
+        }                                                                                      \
+    } while (0)
 #else
+#define MD_CONTACTS_STAMP(cond, i) do { } while (0)
+#define MD_CONTACTS_COUNT(cond, cells, items) do { } while (0)
 #define MD_STAMP_AT(i) do { } while (0)
 #define MD_FINE_STAMP(cond, i) do { } while (0)
 #define MD_LOC_COUNT(cond, hit) do { } while (0)
@@ -1117,6 +1134,29 @@ __device__ __forceinline__ void localize_pair(const MdWorld& w, const MdLane* la
 // ------------------------------------------------------------------------------------------------
 // Contacts, one wave per vehicle.
 // ------------------------------------------------------------------------------------------------
+// Two jobs, one after the other: the movers in LDS, then the static quads through the grid.  The flag word is an OR over the hits.
+// kFlat (the lean kernel only; -DMD_CONTACTS_FLAT=0 compiles it out): the quads of the up to four cells under the chassis in ONE
+// pass -- lanes 0 .. 3 fetch their cell's cell_start pair in one trip, then wave lane t takes item t of the ranges laid end to end
+// (md_flat_cell_item), so the cell_items / quad / kind loads are made once for the whole set: four dependent round trips where
+// the nested loops make three or four per cell, each cell's behind the one before.  A box of more than four cells (no vehicle of
+// the reference's sizes on the 8 m grid) takes the nested loops.
+#ifndef MD_CONTACTS_FLAT
+#define MD_CONTACTS_FLAT 1
+#endif
+// the flag a static quad raises under the chassis `me` (0: clear of it, or a kind without a flag)
+__device__ __forceinline__ uint32_t contacts_quad_bits(const MdShape& me, const float* quads, const int32_t* qkind, int q) {
+    if (!md_obb_quad(me.cx, me.cy, me.c, me.s, me.hl, me.hw, quads + 8 * (size_t)q)) return 0u;
+    switch (qkind[q]) {
+        case MD_Q_LINE_WHITE_CONT: return MD_FL_ON_WHITE_CONT;
+        case MD_Q_LINE_YELLOW_CONT: return MD_FL_ON_YELLOW_CONT;
+        case MD_Q_LINE_BROKEN: return MD_FL_ON_BROKEN;
+        case MD_Q_SIDEWALK: return MD_FL_CRASH_SIDEWALK;
+        case MD_Q_CROSSWALK: return MD_FL_ON_CROSSWALK;
+        default: return 0u;
+    }
+}
+
+template <bool kFlat = false>
 __device__ __forceinline__ void contacts_vehicle(const MdWorld& w, const MdState& s, const MdConfig& c, int e, int slot, int lane_id,
                                  uint32_t* cfl_out = nullptr) {
     const int base = 0;  // env-local view
@@ -1131,6 +1171,7 @@ __device__ __forceinline__ void contacts_vehicle(const MdWorld& w, const MdState
         return;
     }
     uint32_t fl = 0;
+    MD_CONTACTS_STAMP(n == 0 && lane_id == 0, 0);
     for (int j0 = 0; j0 < c.cap; j0 += 64) {
         const int j = j0 + lane_id;
         if (j >= c.cap || j == slot) continue;
@@ -1146,6 +1187,7 @@ __device__ __forceinline__ void contacts_vehicle(const MdWorld& w, const MdState
         else if (k == MD_KIND_PEDESTRIAN || k == MD_KIND_CYCLIST) fl |= MD_FL_CRASH_HUMAN;
         else if (k == MD_KIND_BUILDING) fl |= MD_FL_CRASH_BUILDING;
     }
+    MD_CONTACTS_STAMP(n == 0 && lane_id == 0, 1);
     // static quads through the grid: cells under the chassis AABB (+ margin)
     const int m = w.env_map[e];
     const MdGrid g = w.grid[m];
@@ -1162,16 +1204,41 @@ __device__ __forceinline__ void contacts_vehicle(const MdWorld& w, const MdState
         gy1 = grid_clampi(gy1, 0, g.ny - 1);
         const float* quads = w.quads + 8 * (size_t)w.quad_off[m];
         const int32_t* qkind = w.quad_kind + w.quad_off[m];
+        const int ncx = gx1 - gx0 + 1, n_cells = ncx * (gy1 - gy0 + 1);
+        if (kFlat && n_cells <= 4) {
+            // lanes 0 .. n_cells - 1: their cell's range, the cells in the nested loops' order (the box row by row, gx ascending)
+            int my0 = 0, myn = 0;
+            if (lane_id < n_cells) {
+                const int cell = g.cell_base + (gy0 + lane_id / ncx) * g.nx + gx0 + lane_id % ncx;
+                my0 = w.cell_start[cell];
+                myn = w.cell_start[cell + 1] - my0;
+                if (myn < 0) myn = 0;
+            }
+            const int s0 = __builtin_amdgcn_readlane(my0, 0), s1 = __builtin_amdgcn_readlane(my0, 1);
+            const int s2 = __builtin_amdgcn_readlane(my0, 2), s3 = __builtin_amdgcn_readlane(my0, 3);
+            const int n0 = __builtin_amdgcn_readlane(myn, 0), n1 = __builtin_amdgcn_readlane(myn, 1);
+            const int n2 = __builtin_amdgcn_readlane(myn, 2), n3 = __builtin_amdgcn_readlane(myn, 3);
+            const int total = n0 + n1 + n2 + n3;   // the loop's bound: wave-uniform, known before it starts
+            MD_CONTACTS_COUNT(n == 0 && lane_id == 0, n_cells, total);
+            for (int t = lane_id; t < total; t += 64) {
+                int off;
+                const int k = md_flat_cell_item(n0, n1, n2, n3, t, &off);
+                const int item = w.cell_items[(k == 0 ? s0 : k == 1 ? s1 : k == 2 ? s2 : s3) + off];
+                if (item >= 0) continue;  // lane item
+                fl |= contacts_quad_bits(me, quads, qkind, ~item);
+            }
+        } else
         for (int gy = gy0; gy <= gy1; ++gy)
             for (int gx = gx0; gx <= gx1; ++gx) {
                 const int cell = g.cell_base + gy * g.nx + gx;
                 const int it0 = w.cell_start[cell], it1 = w.cell_start[cell + 1];
+                MD_CONTACTS_COUNT(n == 0 && lane_id == 0, 1, it1 > it0 ? it1 - it0 : 0);
                 for (int it = it0 + lane_id; it < it1; it += 64) {
                     const int item = w.cell_items[it];
                     if (item >= 0) continue;  // lane item
                     const int q = ~item;
                     if (!md_obb_quad(me.cx, me.cy, me.c, me.s, me.hl, me.hw, quads + 8 * (size_t)q)) continue;
-                    switch (qkind[q]) {
+                    switch (qkind[q]) {   // (contacts_quad_bits in words: through the helper, seven other kernels' register lines move)
                         case MD_Q_LINE_WHITE_CONT: fl |= MD_FL_ON_WHITE_CONT; break;
                         case MD_Q_LINE_YELLOW_CONT: fl |= MD_FL_ON_YELLOW_CONT; break;
                         case MD_Q_LINE_BROKEN: fl |= MD_FL_ON_BROKEN; break;
@@ -1182,6 +1249,7 @@ __device__ __forceinline__ void contacts_vehicle(const MdWorld& w, const MdState
                 }
             }
     }
+    MD_CONTACTS_STAMP(n == 0 && lane_id == 0, 2);
     // wave OR-reduce of the flag word: one ballot per flag bit that can be set here
     uint32_t all = 0;
 #pragma unroll
@@ -2164,6 +2232,8 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     constexpr bool kObsLockstep = MD_OBS_LOCKSTEP && PH == PH_ALL && kIdmKeys;
     // ... and ahead, by a wave that the locate stage leaves without an item (observe_ahead_wave): the lean kernel only
     constexpr bool kObsAhead = MD_OBS_AHEAD && kObsLockstep && kWaves > 1;
+    // the agent's contacts with the quads in one flat pass over the cells under the chassis (contacts_vehicle): the lean kernel only
+    constexpr bool kContactsFlat = MD_CONTACTS_FLAT && PH == PH_ALL && kIdmKeys;
     // The lean launch: variant<PH_ALL>() guarantees the pins.  Not in the staged-map kernel: folded, its scratch grows from 16 to
     // 80 B per lane (EXPERIMENTS.md, "Lean kernels fold what their launch pins"), so it keeps reading the fields.
     if constexpr (PH == PH_ALL && !RESPAWN && !MULTI && !STAGE_MAP) lean_pins_fold(g, c);
@@ -2428,7 +2498,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
             for (int item = wave; item < nd + na; item += kWaves) {
                 if (item < nd) {
                     if (!(MD_ENV_SKIP & 4)) localize_vehicle<kLocRoadFirst>(w, lanes, roads, s, e, kth_bit(drv_lo, drv_hi, item), lane, l_onlane);
-                } else if (!(MD_ENV_SKIP & 8)) contacts_vehicle(w, s, c, e, kth_bit(adrv_lo, adrv_hi, item - nd), lane, l_cfl);
+                } else if (!(MD_ENV_SKIP & 8)) contacts_vehicle<kContactsFlat>(w, s, c, e, kth_bit(adrv_lo, adrv_hi, item - nd), lane, l_cfl);
             }
             // the first wave without an item: agent 0's observation context and tasks from the navigation words as they stand,
             // into wave 0's scratch (the last wave is free here too: its trigger fires behind this stage's barrier)
@@ -2443,7 +2513,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
                 if (item < npair) {
                     if (!(MD_ENV_SKIP & 4)) localize_pair<kLocRoadFirst>(w, lanes, roads, s, e, kth_bit(drv_lo, drv_hi, 2 * item), kth_bit(drv_lo, drv_hi, 2 * item + 1), lane, l_onlane);
                 } else if (!(MD_ENV_SKIP & 8))
-                    contacts_vehicle(w, s, c, e, kth_bit(adrv_lo, adrv_hi, item - npair), lane, l_cfl);
+                    contacts_vehicle<kContactsFlat>(w, s, c, e, kth_bit(adrv_lo, adrv_hi, item - npair), lane, l_cfl);
             }
         }
         __syncthreads();
@@ -4048,6 +4118,12 @@ __attribute__((visibility("default"))) const char* md_last_error(void) { return 
 __attribute__((visibility("default"))) int md_debug_set_stamp_buffer(void* dev_ptr) {
     unsigned long long* p = (unsigned long long*)dev_ptr;
     return hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf), &p, sizeof(p)) == hipSuccess ? MD_OK : MD_ELAUNCH;
+}
+// diagnostic build only: buffer of n_envs * 8 uint64 device words for the agent's contacts (the workgroup kernels: one env per
+// workgroup), or NULL
+__attribute__((visibility("default"))) int md_debug_set_contacts_buffer(void* dev_ptr) {
+    unsigned long long* p = (unsigned long long*)dev_ptr;
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_contacts_buf), &p, sizeof(p)) == hipSuccess ? MD_OK : MD_ELAUNCH;
 }
 // diagnostic build only: a permutation of the envs (workgroup b steps env order[b]), or NULL
 __attribute__((visibility("default"))) int md_debug_set_env_order(const void* dev_ptr) {

@@ -73,9 +73,15 @@ def main():
     buf = torch.zeros(E * 32, dtype=torch.int64, device="cuda")
     eng.lib.md_debug_set_stamp_buffer.argtypes = [C.c_void_p]
     assert eng.lib.md_debug_set_stamp_buffer(buf.data_ptr()) == 0
+    # the agent's contacts have a buffer of their own (8 words per env), indexed by workgroup: the workgroup kernels only
+    cbuf = torch.zeros(E * 8, dtype=torch.int64, device="cuda")
+    if os.environ.get("MD_STEP_KERNEL", "wg") == "wg" and hasattr(eng.lib, "md_debug_set_contacts_buffer"):
+        eng.lib.md_debug_set_contacts_buffer.argtypes = [C.c_void_p]
+        assert eng.lib.md_debug_set_contacts_buffer(cbuf.data_ptr()) == 0
     eng.step(next_action(0))
     torch.cuda.synchronize()
     raw = buf.cpu().numpy().reshape(E, 32)
+    con = cbuf.cpu().numpy().reshape(E, 8).astype(np.int64)
     st = raw[:, :12].astype(np.int64)
     # the lean workgroup kernel never writes stamps 2 and 5; its ahead evaluation of the agent's observation (locate stage) leaves
     # its start / end there.  Told apart from the idm-first variants' stamp 2 by its place: after stamp 4, not before stamp 3.
@@ -170,6 +176,26 @@ def main():
             print("            ahead evaluation in %5d envs: p50 %6.0f p99 %6.0f cycles; ends after wave 0's localisation in %d, after the locate barrier (stamp 6) in %d; hit %d  miss %d" % (
                 a_.sum(), np.median(ln), np.percentile(ln, 99), (ah1[a_] > fine[a_, 3]).sum(), (ah1[a_] > st[a_, 6]).sum(),
                 ah_hit[m_].sum(), ah_miss[m_].sum()))
+    # the agent's contacts (contacts_vehicle, slot 0) per class: the whole, its movers | quads parts, the grid cells under the chassis
+    # and the cell items read, beside what they share the locate stage with
+    con_ok = (con[:, 0] > 0) & (con[:, 1] >= con[:, 0]) & (con[:, 2] >= con[:, 1])
+    if con_ok.any():
+        whole, mv, qd, cells, items = con[:, 2] - con[:, 0], con[:, 1] - con[:, 0], con[:, 2] - con[:, 1], con[:, 4], con[:, 5]
+        p = lambda x, q: np.percentile(x, q) if len(x) else float("nan")
+        for k_ in range(1, int(drv.max()) + 1):
+            m_ = (drv == k_) & con_ok
+            if m_.sum() < 5:
+                continue
+            print("driving %2d: contacts(agent) p50 %6.0f p99 %6.0f | movers p50 %6.0f p99 %6.0f | quads p50 %6.0f p99 %6.0f | localize(agent) p50 %6.0f | locate stage p50 %6.0f p99 %6.0f | total p50 %6.0f" % (
+                k_, p(whole[m_], 50), p(whole[m_], 99), p(mv[m_], 50), p(mv[m_], 99), p(qd[m_], 50), p(qd[m_], 99),
+                p((fine[:, 3] - fine[:, 0])[m_ & loc_ok], 50), p(d[m_, 5], 50), p(d[m_, 5], 99), p(tot[m_], 50)))
+            print("            cells under the chassis: " + "  ".join(
+                "%d: %d envs, quads p50 %.0f, items p50 %.0f" % (n_, (m_ & (cells == n_)).sum(), p(qd[m_ & (cells == n_)], 50), p(items[m_ & (cells == n_)], 50))
+                for n_ in sorted(set(cells[m_].tolist()))))
+        for lo_, hi_, name in ((1, 1, "one cell"), (2, 1 << 30, "two or more cells")):
+            m_ = con_ok & (cells >= lo_) & (cells <= hi_)
+            if m_.any():
+                print("contacts(agent) quads part, %s: %d envs, p50 %.0f  p99 %.0f cycles" % (name, m_.sum(), p(qd[m_], 50), p(qd[m_], 99)))
     idx = np.argsort(tot)[-3:]
     for i in idx:
         print("slow env", i, "drv", drv[i], "phases", d[i].tolist())
