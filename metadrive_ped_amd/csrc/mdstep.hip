@@ -40,6 +40,7 @@
 #include "md_branch.h"
 #include "md_ped.h"
 #include "md_vector_obs.h"
+#include "md_lean_pins.h"
 
 namespace {
 
@@ -2155,27 +2156,35 @@ __device__ __forceinline__ int popc(SlotMask m) { return __popcll(m.lo) + __popc
 #endif
 // ---- what a lean launch pins ----
 // The lean kernels of md_step -- env_kernel<PH_ALL, *, false, false> and wave_step_kernel<false> -- are launched only while every
-// field listed here has its pinned value: variant<PH_ALL>() (the launch predicate) asks lean_pins_hold(), and the kernels overwrite
-// their by-value copies of the arguments with the same list (lean_pins_fold; all but the staged-map env_kernel, see there), so the
-// branches on these fields fold away instead of riding along in SGPRs.  ONE list for both sides: a field taken out of the predicate
-// is no longer folded.  Only fields the predicate itself tests belong here; a field that merely happens to be unused in these
-// configs does not.
-//   zero(int32 MdConfig field): the field is 0;  null(MdState pointer): the pointer is null
-template <class Config, class State, class Zero, class Null>
-__host__ __device__ inline void lean_pins(Config& c, State& s, Zero zero, Null null) {
-    zero(c.is_multi_agent);   // the multi-agent envs have their own variant (MULTI)
-    zero(c.traffic_mode);     // trigger mode; respawn / hybrid / replay: the RESPAWN variant (scenario mode: its own kernel)
-    zero(c.agent_idm);        // the caller's actions; IDMPolicy / LaneChangePolicy agents: the RESPAWN variant
-    zero(c.num_others);       // the `others` block needs the detected sets
-    null(s.detected);         // tracked by the RESPAWN / MULTI variants only
+// field of MD_LEAN_PINS (include/md_lean_pins.h) has its pinned value: variant<PH_ALL>() (the launch predicate) asks
+// md_lean_pins_hold(), and the kernels overwrite their by-value copies of the arguments from the same list (lean_pins_fold; all but
+// the staged-map env_kernel, see there), so the branches on these fields fold away instead of riding along in SGPRs.  ONE list for
+// both sides: a field taken out of the predicate is no longer folded.
+__device__ __forceinline__ void lean_pins_fold(MdState& s, MdConfig& c) {
+#define MD_PIN_ZERO(f) c.f = 0;
+#define MD_PIN_NUL(p) s.p = nullptr;
+    MD_LEAN_PINS(MD_PIN_ZERO, MD_PIN_NUL)
+#undef MD_PIN_ZERO
+#undef MD_PIN_NUL
 }
-__host__ __device__ inline bool lean_pins_hold(const MdState& s, const MdConfig& c) {
-    bool ok = true;
-    lean_pins(c, s, [&ok](const int32_t& v) { ok = ok && v == 0; }, [&ok](const void* p) { ok = ok && p == nullptr; });
-    return ok;
-}
-__host__ __device__ inline void lean_pins_fold(MdState& s, MdConfig& c) {
-    lean_pins(c, s, [](int32_t& v) { v = 0; }, [](auto*& p) { p = nullptr; });
+// The size pins (MD_LEAN_SIZE_PINS, same header): variant<PH_ALL>() sends a lean batch to the NARROW instantiation of the
+// non-staged env_kernel only while md_lean_size_pins_hold(), and that instantiation alone folds them.  A pinned value overwrites
+// the argument in `c`.  A bound goes into `c_scan`, the copy that the whole-wave slot scans read (lidar, IDM candidates and gap
+// keys, trigger search and fire), as min(field, bound): a no-op under the predicate that tells the compiler the scan is one pass.
+// `c` itself keeps the field as it came: with the bound on the contacts' mover loop, the mask scans or the per-thread loops the
+// kernel breaks the register rule (EXPERIMENTS.md, "Size pins"); the masks drop their second word in the kernel itself.
+__device__ __forceinline__ void lean_size_pins_fold(MdConfig& c, MdConfig& c_scan) {
+#define MD_PIN_EQUALS(f, v) c.f = (v);
+#define MD_PIN_AT_MOST(f, v)
+    MD_LEAN_SIZE_PINS(MD_PIN_EQUALS, MD_PIN_AT_MOST)
+#undef MD_PIN_EQUALS
+#undef MD_PIN_AT_MOST
+    c_scan = c;
+#define MD_PIN_EQUALS(f, v)
+#define MD_PIN_AT_MOST(f, v) c_scan.f = min(c.f, (v));
+    MD_LEAN_SIZE_PINS(MD_PIN_EQUALS, MD_PIN_AT_MOST)
+#undef MD_PIN_EQUALS
+#undef MD_PIN_AT_MOST
 }
 
 // MULTI: multi-agent envs (lifecycle phase, reference order of the IDM); single-agent envs plan the traffic ahead.
@@ -2215,7 +2224,8 @@ __host__ __device__ inline EnvLds env_lds(int cap, int agents, int n_lanes, int 
 
 // BLK: threads of the workgroup (MD_ENV_BLOCK; multi-agent batches small enough to stay resident are also instantiated with 512:
 // eight waves share an env's 20-40 agents -- lifecycle search, contacts, observe groups, lidar sectors -- instead of four).
-template <int PH, bool STAGE_MAP, bool RESPAWN = false, bool MULTI = false, int BLK = MD_ENV_BLOCK>
+// NARROW: the lean non-staged kernel of a batch that holds the size pins too (lean_size_pins_fold): one agent, at most 64 slots.
+template <int PH, bool STAGE_MAP, bool RESPAWN = false, bool MULTI = false, int BLK = MD_ENV_BLOCK, bool NARROW = false>
 __global__ __launch_bounds__(BLK)
 __attribute__((amdgpu_waves_per_eu(env_waves_per_eu<PH, RESPAWN, MULTI>() ? env_waves_per_eu<PH, RESPAWN, MULTI>() : 1,
                                    env_waves_per_eu<PH, RESPAWN, MULTI>() ? env_waves_per_eu<PH, RESPAWN, MULTI>() : 8)))
@@ -2237,6 +2247,9 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     // The lean launch: variant<PH_ALL>() guarantees the pins.  Not in the staged-map kernel: folded, its scratch grows from 16 to
     // 80 B per lane (EXPERIMENTS.md, "Lean kernels fold what their launch pins"), so it keeps reading the fields.
     if constexpr (PH == PH_ALL && !RESPAWN && !MULTI && !STAGE_MAP) lean_pins_fold(g, c);
+    static_assert(!NARROW || (PH == PH_ALL && !RESPAWN && !MULTI && !STAGE_MAP), "NARROW: a form of the lean non-staged kernel only");
+    MdConfig c_scan = c;   // what the whole-wave slot scans read: `c`, but for the NARROW kernel's bounds
+    if constexpr (NARROW) lean_size_pins_fold(c, c_scan);   // variant<PH_ALL>() guarantees them
     if ((int)blockIdx.x >= c.n_envs) return;
 #ifdef MD_STAMP
     const int e = g_env_order ? g_env_order[blockIdx.x] : (int)blockIdx.x;   // diagnostic: launch-order experiments
@@ -2416,7 +2429,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     constexpr int kTrigWord = (kWaves - 1) * 48 + 46;
     if (kTriggerEarly && wave == kWaves - 1) {
         int min_order, trig_road;
-        trigger_search_wave(s, c, lane, &min_order, &trig_road);
+        trigger_search_wave(s, c_scan, lane, &min_order, &trig_road);
         if (lane == 0) {
             int* l_trig = reinterpret_cast<int*>(smem + L.scratch) + kTrigWord;
             l_trig[0] = min_order;
@@ -2475,11 +2488,11 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         // vehicles per env everything fits one round instead of two phases behind two barriers.
         const SlotMask drv = drive_mask(s.shape, cap, lane);
         drv_lo = drv.lo;
-        drv_hi = drv.hi;
+        drv_hi = NARROW ? 0ull : drv.hi;   // NARROW: at most 64 slots, every mask is its low word (the k-th-bit walks and the flag merge fold)
         // contacts only for agents (traffic's crash flags are never read): their slots are the first A
         const SlotMask adrv = agent_share(drv, c.agents_per_env);
-        const unsigned long long adrv_lo = adrv.lo, adrv_hi = adrv.hi;
-        const int nd = popc(drv), na = popc(adrv);
+        const unsigned long long adrv_lo = adrv.lo, adrv_hi = NARROW ? 0ull : adrv.hi;
+        const int nd = NARROW ? __popcll(drv_lo) : popc(drv), na = NARROW ? __popcll(adrv_lo) : popc(adrv);
         if (MULTI) {
             // every workgroup of a multi-agent batch is resident at once: the launch lasts as long as its slowest env, and inside
             // an env as long as the wave with the most expensive items -- the waves take the items by ticket, contacts (the
@@ -2551,8 +2564,8 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         if (plan_ahead && wave == kWaves - 1) {
             if (kTriggerEarly) {   // searched beside the integration
                 const int* l_trig = reinterpret_cast<const int*>(smem + L.scratch) + kTrigWord;
-                trigger_fire_wave(lanes, s, c, lane, __builtin_amdgcn_readfirstlane(l_trig[0]), __builtin_amdgcn_readfirstlane(l_trig[1]));
-            } else trigger_env(lanes, s, c, lane);
+                trigger_fire_wave(lanes, s, c_scan, lane, __builtin_amdgcn_readfirstlane(l_trig[0]), __builtin_amdgcn_readfirstlane(l_trig[1]));
+            } else trigger_env(lanes, s, c_scan, lane);
         }
         __syncthreads();
         if (RESPAWN) {  // respawn / hybrid: the removed vehicle re-enters on a respawn lane (rare; serial)
@@ -2579,7 +2592,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
                 while (mk) {
                     const int j = j0 + __ffsll((long long)mk) - 1;
                     mk &= mk - 1;
-                    if (rank % (kWaves - 1) == wave - 1) idm_vehicle_wave<kIdmKeys>(w, lanes, roads, s, c, w.env_map[e], j, lane, reinterpret_cast<int*>(l_scratch));
+                    if (rank % (kWaves - 1) == wave - 1) idm_vehicle_wave<kIdmKeys>(w, lanes, roads, s, c_scan, w.env_map[e], j, lane, reinterpret_cast<int*>(l_scratch));
                     ++rank;
                 }
             }
@@ -2602,7 +2615,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         // lidar only reads shapes; observe writes obs[0:19] / flags / nav / pid -- no barrier needed in between
     }
     if ((PH & PH_LIDAR) && !(PH == PH_ALL && (MD_ENV_SKIP & 1))) {
-        if (c.n_beams > 0) phase_lidar(w, s, c, e, tid, kWaves, lidar_out, lidar_stride, lidar_offset, track_det ? l_det : nullptr, PH == PH_ALL ? &l_tk[2] : nullptr);
+        if (c.n_beams > 0) phase_lidar(w, s, c_scan, e, tid, kWaves, lidar_out, lidar_stride, lidar_offset, track_det ? l_det : nullptr, PH == PH_ALL ? &l_tk[2] : nullptr);
     }
 
     MD_STAMP_AT(9);
@@ -4037,7 +4050,7 @@ int check_phase(int ph, const MdWorld* w, const MdState* s, const MdConfig* c) {
 // library reads no environment variable.  The wave kernel is wave_step_kernel<respawn>; the workgroup kernel is
 // env_kernel<PH, stage, respawn, multi>, or <PH_ALL, stage, false, true, 512> when wide.
 struct Variant {
-    bool wave, stage, respawn, multi, wide;
+    bool wave, stage, respawn, multi, wide, narrow;
 };
 
 template <int PH>
@@ -4050,11 +4063,14 @@ Variant variant(const MdWorld* w, const MdState* s, const MdConfig* c) {
     // md_step (PH_ALL): whatever breaks one of the lean pins (lean_pins: the list the lean kernels fold) -- so does num_others > 0,
     // which md_step accepts with the detected sets only.  The phase entry points track no detected sets.
     v.respawn = !v.multi && (PH & (PH_TRAFFIC | PH_RESET | PH_INTEGRATE)) &&
-                (PH == PH_ALL ? !lean_pins_hold(*s, *c) : (c->traffic_mode != 0 || c->agent_idm != 0));
+                (PH == PH_ALL ? !md_lean_pins_hold(s, c) : (c->traffic_mode != 0 || c->agent_idm != 0));
     // Multi-agent md_step: eight waves per env while every workgroup of the batch is resident at once at that size (the MULTI
     // kernel's 92 VGPRs allow 5 waves per SIMD = 640 eight-wave workgroups on the 256 CUs); larger batches keep four, which
     // then fill the chip by themselves.  Measured: 512 tollgate envs x 40 agents, 1024 roundabout envs (profiles/r03_*).
     v.wide = PH == PH_ALL && v.multi && c->n_envs <= kWideMaxEnvs && MD_ENV_BLOCK == 256 && c->agents_per_env > 8;
+    // the lean non-staged workgroup kernel has a narrow form for the batches that hold the size pins as well; a lean batch that
+    // does not keeps the lean kernel itself (never the RESPAWN variant: no gap keys, no road-first localisation there)
+    v.narrow = PH == PH_ALL && !v.wave && !v.stage && !v.multi && !v.respawn && md_lean_size_pins_hold(c);
     return v;
 }
 
@@ -4063,6 +4079,13 @@ void launch_env(bool stage, size_t lds, hipStream_t st, const MdWorld* w, const 
                 int stride, int offset) {
     if (stage) hipLaunchKernelGGL((env_kernel<PH, true, RESPAWN, MULTI, BLK>), dim3(c->n_envs), dim3(BLK), lds, st, *w, *s, *c, lidar_out, stride, offset);
     else hipLaunchKernelGGL((env_kernel<PH, false, RESPAWN, MULTI, BLK>), dim3(c->n_envs), dim3(BLK), lds, st, *w, *s, *c, lidar_out, stride, offset);
+}
+
+// md_step alone has the narrow form (variant<PH>().narrow is false for every other PH)
+template <int PH>
+void launch_narrow(size_t lds, hipStream_t st, const MdWorld* w, const MdState* s, const MdConfig* c, float* lidar_out, int stride, int offset) {
+    if constexpr (PH == PH_ALL)
+        hipLaunchKernelGGL((env_kernel<PH_ALL, false, false, false, MD_ENV_BLOCK, true>), dim3(c->n_envs), dim3(MD_ENV_BLOCK), lds, st, *w, *s, *c, lidar_out, stride, offset);
 }
 
 template <int PH>
@@ -4096,6 +4119,7 @@ int launch(const MdWorld* w, const MdState* s, const MdConfig* c, float* lidar_o
     if (v.wide) launch_env<PH, false, kAll, kAll ? 512 : MD_ENV_BLOCK>(v.stage, lds, st, w, s, c, lidar_out, stride, offset);
     else if (v.multi) launch_env<PH, false, kMulti>(v.stage, lds, st, w, s, c, lidar_out, stride, offset);
     else if (v.respawn) launch_env<PH, kRespawn, false>(v.stage, lds, st, w, s, c, lidar_out, stride, offset);
+    else if (kAll && v.narrow) launch_narrow<PH>(lds, st, w, s, c, lidar_out, stride, offset);
     else launch_env<PH, false, false>(v.stage, lds, st, w, s, c, lidar_out, stride, offset);
     return launch_status();
 }
