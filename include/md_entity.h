@@ -6,7 +6,7 @@
  * The phases whose GPU form is genuinely different -- lidar (wave per agent-sector with ballot
  * culling), lane localisation and contact tests (wave per vehicle over grid cells), traffic
  * trigger (wave min-reduce) -- are written twice: brute force in oracle/md_oracle.c, wave-parallel
- * in metadrive_ped_amd/csrc/mdstep.hip.
+ * in metadrive_ped_amd/csrc/ (mdstep.hip: lidar; parts/localize.inc, contacts.inc, trigger.inc).
  *
  * Indexing convention: every routine here receives an ENV-LOCAL view of MdState (md_env_view): the
  * pointers are already advanced to the env's first mover / first agent, so slot j is s->shape[j],
@@ -223,7 +223,7 @@ typedef struct MdObsCtx {
 /* What the context reads of the vehicle's MdNav, as a copy: the context (and with it the nine task results) is a function of
  * these five words, the slot's shape flags and final lane, the pose and the map.  The lean step kernel evaluates context and
  * tasks from such a copy while the localisation may still commit, and keeps the result iff the committed words equal the
- * copy (md_obs_key_same): csrc/mdstep.hip, the locate stage. */
+ * copy (md_obs_key_same): csrc/parts/observe.inc (observe_ahead_wave), in the locate stage of env_kernel. */
 typedef struct MdObsKey {
     int32_t lane, road0, road1, ck0, ck1;
 } MdObsKey;

@@ -691,1375 +691,18 @@ __global__ __launch_bounds__(kBlock) void line_detector_kernel(MdWorld w, MdStat
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// Grid helpers
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int grid_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+}  // namespace
 
-// ------------------------------------------------------------------------------------------------
-// Localisation, one wave per vehicle.
-// ------------------------------------------------------------------------------------------------
-// pass B for one candidate lane L that contains the point (cx, cy; heading c, s): Frenet coordinates, heading filter, L1
-// distance.  dist / road stay as the caller set them (3.0e38f / -1) for a lane that fails the heading filter.
-__device__ __forceinline__ void localize_candidate(const MdLane* L, float cx, float cy, float c, float s, float& dist, float& ls,
-                                                   int& road) {
-    float llat;
-    md_lane_local(L, cx, cy, &ls, &llat);
-    if (md_lane_heading_dot(L, cx, cy, c, s) > 0.0f) {
-        dist = md_lane_distance(L, ls, llat);
-        road = L->road;
-    }
-}
+// The wave-level stages of the step, one part each: a part is included here and not compiled on its own, opens its own namespace
+// and names what it provides and relies on in its first lines.  Cuts of this file's text, in its order.
+#include "parts/localize.inc"     // grid_clampi, localize_*, hull_*; MD_LOC_ROAD_FIRST
+#include "parts/contacts.inc"     // contacts_quad_bits, contacts_vehicle; MD_CONTACTS_FLAT
+#include "parts/idm.inc"          // gap keys, wave_argmin, idm_*
+#include "parts/observe.inc"      // observe_*; MD_OBS_LOCKSTEP, MD_OBS_AHEAD
+#include "parts/trigger.inc"      // trigger_*; MD_TRIGGER_EARLY
+#include "parts/lifecycle.inc"    // lifecycle_block (multi-agent envs)
 
-// Commit of vehicle n by ONE lane: its lane (the caller's choice by preference, ls the longitudinal on it; -1: the previous lane
-// stays) and the route cursors' advance within the first 5 m of a lane whose road starts at a later route node.  nav_*: the
-// vehicle's MdNav fields before the step; rroads / rnodes: its route (global: read only when the cursors advance).
-__device__ __forceinline__ void localize_commit(const MdLane* lanes, const MdRoad* roads, const MdState& s, int n, int lane, float ls,
-                                                float cx, float cy, int nav_lane, int nav_ck0, int nav_ck1,
-                                                int nav_route_len, const int32_t* rroads, const int32_t* rnodes) {
-    const bool kept = lane < 0;  // found nothing: the previous lane stays, its longitudinal was not evaluated above
-    if (kept) lane = nav_lane;
-    s.nav[n].lane = lane;
-    if (lane < 0) return;
-    if (nav_ck0 == nav_ck1) return;
-    if (kept) {
-        float llat;
-        md_lane_local(&lanes[lane], cx, cy, &ls, &llat);
-    }
-    if (!(ls < 5.0f)) return;
-    const int start_node = roads[lanes[lane].road].start_node;
-    const int k = nav_route_len;
-    int idx = -1;
-    for (int j = nav_ck1; j < k - 1; ++j) {
-        if (rnodes[j] == start_node) { idx = j; break; }
-    }
-    if (idx < 0) return;
-    const int nck1 = (idx + 1 == k - 1) ? idx : idx + 1;
-    s.nav[n].ck0 = idx;
-    s.nav[n].ck1 = nck1;
-    s.nav[n].road0 = rroads[idx];
-    s.nav[n].road1 = rroads[nck1];
-}
-
-// pass A for one candidate lane L, the share of lane hl of the GW lanes that test it: the hull's edges hl, hl + GW, ... (4-vertex
-// hulls come inline from the lane record).  true: (cx, cy) is outside one of them; hn: the hull's vertex count.
-template <int GW>
-__device__ __forceinline__ bool hull_edges_outside(const MdLane* L, const float* hull_xy, float cx, float cy, int hl, int& hn) {
-    hn = L->hull_n;
-    const float* xy = md_lane_hull(L, hull_xy);
-    bool outside = false;
-    for (int i = hl; i < hn; i += GW) {
-        const int j = (i + 1 == hn) ? 0 : i + 1;
-        const float ex = xy[2 * j] - xy[2 * i], ey = xy[2 * j + 1] - xy[2 * i + 1];
-        const float cr = ex * (cy - xy[2 * i + 1]) - ey * (cx - xy[2 * i]);
-        if (cr < 0.0f) outside = true;
-    }
-    return outside;
-}
-
-// pass A by the whole wave, ballot vote.  Wave-uniform result: L's hull contains (cx, cy).
-__device__ __forceinline__ bool hull_contains_wave(const MdLane* L, const float* hull_xy, float cx, float cy, int lane_id) {
-    int hn;
-    const bool outside = hull_edges_outside<64>(L, hull_xy, cx, cy, lane_id, hn);
-    return __ballot(outside) == 0ull && hn >= 3;
-}
-
-// A/B builds: -DMD_LOC_ROAD_FIRST=0 compiles every kernel without the road-first localisation below
-#ifndef MD_LOC_ROAD_FIRST
-#define MD_LOC_ROAD_FIRST 1
-#endif
-// The road-first window: the lane records nav_lane - kLocWindow .. nav_lane + kLocWindow, one per wave lane.  A road's lanes are
-// contiguous (first = lane - idx), so 3 covers every road of up to four lanes wherever in it the vehicle was; PG roads have 1-4.
-constexpr int kLocWindow = 3;
-
-// Localisation on the lanes of the vehicle's CURRENT road, before any table: the wave loads the records around the previous lane
-// in one trip (no grid header, cell range or item list), the lanes of road cur_road test their own record in parallel (box, hull,
-// Frenet + heading filter: localize_vehicle's predicates in its order) and the nearest one wins, the lowest lane id on ties.
-// A lane of the current road that contains the point and passes the heading filter is what localize_vehicle's selection takes
-// whenever there is one (best_cur), and the grid cell's list holds every lane whose box contains the point, so a hit here is the
-// walk's result.  false (nothing written): no previous lane, the previous lane is not on cur_road, the road does not fit the
-// window, or none of its lanes qualifies -- the caller runs the grid walk as if nothing had happened.
-__device__ __forceinline__ bool localize_road_first(const MdLane* lanes, int n_lanes, const float* hull_xy, int nav_lane, int cur_road,
-                                                    float cx, float cy, float c, float s, int lane_id, int& best, float& best_ls) {
-    if (nav_lane < 0 || nav_lane >= n_lanes) return false;
-    const int li = nav_lane - kLocWindow + lane_id;
-    const bool valid = lane_id <= 2 * kLocWindow && li >= 0 && li < n_lanes;   // no load leaves the map's slice
-    const MdLane* L = &lanes[valid ? li : nav_lane];
-    int road = -1, idx = 0, nr = 0, hn = 0;
-    float x0 = 0.0f, y0 = 0.0f, x1 = 0.0f, y1 = 0.0f;
-    float h[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (valid) {
-        road = L->road; idx = L->idx; nr = L->n_in_road;
-        x0 = L->x0; y0 = L->y0; x1 = L->x1; y1 = L->y1;
-        hn = L->hull_n;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) h[i] = L->hull4[i];
-    }
-    // the previous lane's record is in wave lane kLocWindow
-    const int first = nav_lane - bcast_i(idx, kLocWindow), n_road = bcast_i(nr, kLocWindow);
-    if (bcast_i(road, kLocWindow) != cur_road || first < nav_lane - kLocWindow || first + n_road > nav_lane + kLocWindow + 1) return false;
-    const bool mine = valid && road == cur_road && li >= first && li < first + n_road;
-    const bool pass = mine && !(cx < x0 || cx > x1 || cy < y0 || cy > y1);
-    bool contains = false;
-    if (pass && hn == 4) {   // straight lanes: the four edges in this lane
-        bool outside = false;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int j = (i + 1) & 3;
-            const float ex = h[2 * j] - h[2 * i], ey = h[2 * j + 1] - h[2 * i + 1];
-            const float cr = ex * (cy - h[2 * i + 1]) - ey * (cx - h[2 * i]);
-            if (cr < 0.0f) outside = true;
-        }
-        contains = !outside;
-    }
-    unsigned long long wide = __ballot(pass && hn != 4);   // other hulls (circular lanes): the wave's vote, one candidate at a time
-    while (wide) {
-        const int k = __ffsll((long long)wide) - 1;
-        wide &= wide - 1;
-        const bool in = hull_contains_wave(&lanes[nav_lane - kLocWindow + k], hull_xy, cx, cy, lane_id);
-        if (k == lane_id) contains = in;
-    }
-    float my_dist = 3.0e38f, my_ls = 0.0f;
-    int my_road = -1;
-    if (contains) localize_candidate(L, cx, cy, c, s, my_dist, my_ls, my_road);
-    unsigned long long sel = __ballot(my_road >= 0);   // contained and past the heading filter
-    float d = 3.0e38f;
-    int k_best = -1;
-    while (sel) {   // ascending lane id, strict <: the first minimum
-        const int k = __ffsll((long long)sel) - 1;
-        sel &= sel - 1;
-        const float dist = bcast_f(my_dist, k);
-        if (dist < d) { d = dist; k_best = k; }
-    }
-    if (k_best < 0) return false;
-    best = nav_lane - kLocWindow + k_best;
-    best_ls = bcast_f(my_ls, k_best);
-    return true;
-}
-
-// onlane_out: nullptr = write the ON_LANE bit into s.flags[n] (stand-alone phase); otherwise store the bare
-// decision there and leave s.flags alone (fused step: contacts run concurrently and own the other bits).
-// kRoadFirst: try localize_road_first before the grid walk (the lean fused step; the other kernels keep the walk alone).
-template <bool kRoadFirst = false>
-__device__ __forceinline__ void localize_vehicle(const MdWorld& w, const MdLane* lanes, const MdRoad* roads, const MdState& s, int e,
-                                 int n, int lane_id, uint32_t* onlane_out = nullptr) {
-    // n = slot inside the env-local view; lanes / roads = this env's map tables (LDS copies)
-    const MdShape sh = s.shape[n];
-    if (!md_drives(sh.flags)) return;
-    MdNav nav = s.nav[n];
-    const int m = w.env_map[e];
-    const int32_t* rroads = s.route_roads + (size_t)n * MD_ROUTE_LEN;   // global: read only when the cursors advance
-    const int32_t* rnodes = s.route_nodes + (size_t)n * MD_ROUTE_LEN;
-    const int cur_road = nav.road0;
-    const bool has_next = nav.ck1 != nav.ck0;
-    const int next_road = has_next ? nav.road1 : -1;
-
-    MD_FINE_STAMP(n == 0 && lane_id == 0, 0);
-    int on_lane = 0;
-    int best_any = -1, best_cur = -1, best_next = -1;
-    float d_any = 3.0e38f, d_cur = 3.0e38f, d_next = 3.0e38f;
-    float ls_any = 0.0f, ls_cur = 0.0f, ls_next = 0.0f;
-    if (MD_LOC_ROAD_FIRST && kRoadFirst &&
-        localize_road_first(lanes, w.lane_off[m + 1] - w.lane_off[m], w.hull_xy, nav.lane, cur_road, sh.cx, sh.cy, sh.c, sh.s, lane_id,
-                            best_cur, ls_cur))
-        on_lane = 1;
-    MD_LOC_COUNT(lane_id == 0, on_lane);
-    // a hit leaves the walk nothing to do: the grid header and the cell's range are loaded behind the miss
-    int it0 = 0, it1 = 0;
-    if (!on_lane) {
-        const MdGrid g = w.grid[m];
-        const int gx = (int)md_floor((sh.cx - g.x0) * g.inv_cell);
-        const int gy = (int)md_floor((sh.cy - g.y0) * g.inv_cell);
-        if (gx >= 0 && gx < g.nx && gy >= 0 && gy < g.ny) {
-            const int cell = g.cell_base + gy * g.nx + gx;
-            it0 = w.cell_start[cell];
-            it1 = w.cell_start[cell + 1];
-        }
-    }
-    MD_FINE_STAMP(n == 0 && lane_id == 0 && it1 >= 0, 1);
-    // Candidate lanes of the cell: each LANE fetches one cell item and tests its lane record's hull
-    // AABB (records are in LDS); survivors are visited in ascending lane id through the ballot mask
-    // (ties in distance resolve to the lowest lane id, like the oracle's ascending scan).
-    //   pass A  hull containment of every surviving candidate (edges spread over the 64 lanes, ballot
-    //           vote; 4-vertex hulls come inline from the lane record, no second lookup)
-    //   pass B  ONE batched Frenet evaluation: lane k evaluates the k-th contained candidate
-    //   pass C  uniform selection over the (few) contained candidates
-    for (int itb = it0; itb < it1; itb += 64) {
-        const int it = itb + lane_id;
-        int l = -1;
-        bool pass = false;
-        if (it < it1) {
-            l = w.cell_items[it];
-            if (l >= 0) {
-                const MdLane* L = &lanes[l];
-                pass = !(sh.cx < L->x0 || sh.cx > L->x1 || sh.cy < L->y0 || sh.cy > L->y1);
-            }
-        }
-        unsigned long long mask = __ballot(pass);
-        MD_FINE_STAMP(n == 0 && lane_id == 0, 2);
-#ifdef MD_STAMP
-        if (n == 0 && lane_id == 0 && g_stamp_buf)
-            g_stamp_buf[(size_t)blockIdx.x * 32 + 16 + 15] = (unsigned long long)__popcll(mask) | ((unsigned long long)(it1 - it0) << 32);
-#endif
-        unsigned long long inside = 0ull;  // bit k: candidate held by lane k contains the point
-        while (mask) {
-            const int k = __ffsll((long long)mask) - 1;
-            mask &= mask - 1;
-            if (hull_contains_wave(&lanes[bcast_i(l, k)], w.hull_xy, sh.cx, sh.cy, lane_id)) inside |= 1ull << k;
-        }
-        if (inside == 0ull) continue;
-        on_lane = 1;
-        // pass B: my lane's candidate (if contained): Frenet coordinates, heading filter, L1 distance
-        float my_dist = 3.0e38f, my_ls = 0.0f;
-        int my_road = -1;
-        if ((inside >> lane_id) & 1ull) localize_candidate(&lanes[l], sh.cx, sh.cy, sh.c, sh.s, my_dist, my_ls, my_road);
-        // pass C (the winner's longitudinal is kept: the checkpoint update below needs it)
-        while (inside) {
-            const int k = __ffsll((long long)inside) - 1;
-            inside &= inside - 1;
-            const float dist = bcast_f(my_dist, k);
-            const int road = bcast_i(my_road, k);
-            const int lk = bcast_i(l, k);
-            if (road < 0) continue;  // failed the heading filter
-            const float lsk = bcast_f(my_ls, k);
-            if (dist < d_any) { d_any = dist; best_any = lk; ls_any = lsk; }
-            if (road == cur_road && dist < d_cur) { d_cur = dist; best_cur = lk; ls_cur = lsk; }
-            if (has_next && road == next_road && dist < d_next) { d_next = dist; best_next = lk; ls_next = lsk; }
-        }
-    }
-    MD_FINE_STAMP(n == 0 && lane_id == 0, 3);
-    if (lane_id != 0) return;  // everything below is wave-uniform; lane 0 commits
-    int lane = -1;
-    float ls = 0.0f;
-    if (best_cur >= 0) { lane = best_cur; ls = ls_cur; }
-    else if (!has_next) { lane = best_any; ls = ls_any; }
-    else if (best_next >= 0) { lane = best_next; ls = ls_next; }
-    else { lane = best_any; ls = ls_any; }
-    if (onlane_out) {
-        onlane_out[n] = on_lane ? MD_FL_ON_LANE : 0u;
-    } else {
-        uint32_t fl = s.flags[n] & ~(uint32_t)MD_FL_ON_LANE;
-        if (on_lane) fl |= MD_FL_ON_LANE;
-        s.flags[n] = fl;
-    }
-    localize_commit(lanes, roads, s, n, lane, ls, sh.cx, sh.cy, nav.lane, nav.ck0, nav.ck1, nav.route_len, rroads, rnodes);
-}
-
-// localize_road_first for the groups of localize_group<GW> (one vehicle per GW lanes; every argument but lanes / n_lanes / hull_xy is
-// uniform within a group): the same window, predicates, order and tie-break, votes through the group's part of the ballot.
-// true in the lanes of a group whose vehicle was found (best / best_ls set there).
-template <int GW>
-__device__ __forceinline__ bool localize_road_first_group(const MdLane* lanes, int n_lanes, const float* hull_xy, bool act, int nav_lane,
-                                                          int cur_road, float cx, float cy, float c, float s, int lane_id, int& best,
-                                                          float& best_ls) {
-    constexpr unsigned kGroupMask = (GW == 32) ? 0xFFFFFFFFu : 0xFFFFu;
-    const int hl = lane_id & (GW - 1), hbase = lane_id - hl;
-    const auto part_of = [&](unsigned long long b) { return (unsigned)(b >> hbase) & kGroupMask; };
-    const bool any = act && nav_lane >= 0 && nav_lane < n_lanes;
-    const int li = nav_lane - kLocWindow + hl;
-    const bool valid = any && hl <= 2 * kLocWindow && li >= 0 && li < n_lanes;   // no load leaves the map's slice
-    const MdLane* L = &lanes[valid ? li : 0];
-    int road = -1, idx = 0, nr = 0, hn = 0;
-    float x0 = 0.0f, y0 = 0.0f, x1 = 0.0f, y1 = 0.0f;
-    float h[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (valid) {
-        road = L->road; idx = L->idx; nr = L->n_in_road;
-        x0 = L->x0; y0 = L->y0; x1 = L->x1; y1 = L->y1;
-        hn = L->hull_n;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) h[i] = L->hull4[i];
-    }
-    const int first = nav_lane - __shfl(idx, hbase + kLocWindow, 64), n_road = __shfl(nr, hbase + kLocWindow, 64);
-    const bool elig = any && __shfl(road, hbase + kLocWindow, 64) == cur_road && first >= nav_lane - kLocWindow &&
-                      first + n_road <= nav_lane + kLocWindow + 1;
-    const bool mine = elig && valid && road == cur_road && li >= first && li < first + n_road;
-    const bool pass = mine && !(cx < x0 || cx > x1 || cy < y0 || cy > y1);
-    bool contains = false;
-    if (pass && hn == 4) {
-        bool outside = false;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int j = (i + 1) & 3;
-            const float ex = h[2 * j] - h[2 * i], ey = h[2 * j + 1] - h[2 * i + 1];
-            const float cr = ex * (cy - h[2 * i + 1]) - ey * (cx - h[2 * i]);
-            if (cr < 0.0f) outside = true;
-        }
-        contains = !outside;
-    }
-    unsigned wide = part_of(__ballot(pass && hn != 4));   // other hulls: the group's vote, one candidate at a time
-    while (__ballot(wide != 0u) != 0ull) {
-        const bool on = wide != 0u;
-        const int k = on ? (__ffs((int)wide) - 1) : 0;
-        if (on) wide &= wide - 1;
-        bool outside = false;
-        int hk = 0;
-        if (on) outside = hull_edges_outside<GW>(&lanes[nav_lane - kLocWindow + k], hull_xy, cx, cy, hl, hk);
-        const unsigned out_h = part_of(__ballot(outside));
-        if (on && k == hl) contains = out_h == 0u && hk >= 3;
-    }
-    float my_dist = 3.0e38f, my_ls = 0.0f;
-    int my_road = -1;
-    if (contains) localize_candidate(L, cx, cy, c, s, my_dist, my_ls, my_road);
-    unsigned sel = part_of(__ballot(my_road >= 0));
-    float d = 3.0e38f;
-    int k_best = -1;
-    while (__ballot(sel != 0u) != 0ull) {   // ascending lane id, strict <: the first minimum
-        const bool on = sel != 0u;
-        const int k = on ? (__ffs((int)sel) - 1) : 0;
-        if (on) sel &= sel - 1;
-        const float dist = __shfl(my_dist, hbase + k, 64);
-        if (on && dist < d) { d = dist; k_best = k; }
-    }
-    const float ls = __shfl(my_ls, hbase + (k_best < 0 ? 0 : k_best), 64);
-    if (k_best < 0) return false;
-    best = nav_lane - kLocWindow + k_best;
-    best_ls = ls;
-    return true;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Localisation of TWO vehicles by one wave (lanes 0-31: slot_a, lanes 32-63: slot_b; -1 = half idle): the form the
-// fused step uses when more vehicles drive than the workgroup has waves.  Same arithmetic, same candidate order and
-// tie-breaks as localize_vehicle; the per-vehicle data are per-lane values here (uniform within a half), cross-lane
-// reads go through __shfl, votes through the matching half of a 64-bit ballot.  Results go to onlane_out.
-// ------------------------------------------------------------------------------------------------
-// GW = lanes per vehicle: 32 (two vehicles per wave) or 16 (four; the one-wave-per-env kernel's form when three or more
-// vehicles drive).  slot_c / slot_d are only read with GW == 16.
-template <int GW, bool kRoadFirst = false>
-__device__ __forceinline__ void localize_group(const MdWorld& w, const MdLane* lanes, const MdRoad* roads, const MdState& s, int e,
-                              int slot_a, int slot_b, int slot_c, int slot_d, int lane_id, uint32_t* onlane_out) {
-    constexpr unsigned kGroupMask = (GW == 32) ? 0xFFFFFFFFu : 0xFFFFu;
-    const int h = lane_id / GW, hl = lane_id & (GW - 1), hbase = h * GW;
-    const int n = (h == 0) ? slot_a : ((h == 1) ? slot_b : ((h == 2) ? slot_c : slot_d));
-    const bool act = n >= 0;  // (slots handed in always drive)
-    const int nn = act ? n : 0;
-    struct { float cx, cy, c, s; } sh;   // only what the search needs, per lane
-    sh.cx = s.shape[nn].cx;
-    sh.cy = s.shape[nn].cy;
-    sh.c = s.shape[nn].c;
-    sh.s = s.shape[nn].s;
-    struct { int lane, ck0, ck1, route_len; } nav;
-    nav.lane = s.nav[nn].lane;
-    nav.ck0 = s.nav[nn].ck0;
-    nav.ck1 = s.nav[nn].ck1;
-    nav.route_len = s.nav[nn].route_len;
-    const int m = w.env_map[e];
-    const int32_t* rroads = s.route_roads + (size_t)nn * MD_ROUTE_LEN;   // global: read only when the cursors advance
-    const int32_t* rnodes = s.route_nodes + (size_t)nn * MD_ROUTE_LEN;
-    const int cur_road = s.nav[nn].road0;
-    const bool has_next = nav.ck1 != nav.ck0;
-    const int next_road = has_next ? s.nav[nn].road1 : -1;
-    int on_lane = 0;
-    int best_any = -1, best_cur = -1, best_next = -1;
-    float d_any = 3.0e38f, d_cur = 3.0e38f, d_next = 3.0e38f;
-    float ls_any = 0.0f, ls_cur = 0.0f, ls_next = 0.0f;
-    if (MD_LOC_ROAD_FIRST && kRoadFirst &&
-        localize_road_first_group<GW>(lanes, w.lane_off[m + 1] - w.lane_off[m], w.hull_xy, act, nav.lane, cur_road, sh.cx, sh.cy, sh.c,
-                                      sh.s, lane_id, best_cur, ls_cur))
-        on_lane = 1;
-    const bool road_first_hit = on_lane != 0;
-    (void)road_first_hit;
-    // a group that was answered above leaves the walk nothing to do; the grid header is loaded only if some group walks
-    int it0 = 0, it1 = 0;
-    if (!(MD_LOC_ROAD_FIRST && kRoadFirst) || __ballot(act && !on_lane) != 0ull) {
-        const MdGrid g = w.grid[m];
-        const int gx = (int)md_floor((sh.cx - g.x0) * g.inv_cell);
-        const int gy = (int)md_floor((sh.cy - g.y0) * g.inv_cell);
-        if (act && !on_lane && gx >= 0 && gx < g.nx && gy >= 0 && gy < g.ny) {
-            const int cell = g.cell_base + gy * g.nx + gx;
-            it0 = w.cell_start[cell];
-            it1 = w.cell_start[cell + 1];
-        }
-    }
-    const auto part_of = [&](unsigned long long b) { return (unsigned)(b >> hbase) & kGroupMask; };
-    for (int itb = it0; __ballot(itb < it1) != 0ull; itb += GW) {
-        const int it = itb + hl;
-        int l = -1;
-        bool pass = false;
-        if (it < it1) {
-            l = w.cell_items[it];
-            if (l >= 0) {
-                const MdLane* L = &lanes[l];
-                pass = !(sh.cx < L->x0 || sh.cx > L->x1 || sh.cy < L->y0 || sh.cy > L->y1);
-            }
-        }
-        unsigned mask = part_of(__ballot(pass));
-        unsigned inside = 0u;  // bit k: candidate held by lane k of MY group contains the point
-        while (__ballot(mask != 0u) != 0ull) {
-            const bool mine = mask != 0u;
-            const int k = mine ? (__ffs((int)mask) - 1) : 0;
-            if (mine) mask &= mask - 1;
-            const int lk = __shfl(l, hbase + k, 64);
-            bool outside = false;
-            int hn = 0;
-            if (mine) outside = hull_edges_outside<GW>(&lanes[lk], w.hull_xy, sh.cx, sh.cy, hl, hn);
-            const unsigned out_h = part_of(__ballot(outside));
-            if (mine && out_h == 0u && hn >= 3) inside |= 1u << k;
-        }
-        if (inside != 0u) on_lane = 1;
-        float my_dist = 3.0e38f, my_ls = 0.0f;
-        int my_road = -1;
-        if ((inside >> hl) & 1u) localize_candidate(&lanes[l], sh.cx, sh.cy, sh.c, sh.s, my_dist, my_ls, my_road);
-        while (__ballot(inside != 0u) != 0ull) {
-            const bool mine = inside != 0u;
-            const int k = mine ? (__ffs((int)inside) - 1) : 0;
-            if (mine) inside &= inside - 1;
-            const float dist = __shfl(my_dist, hbase + k, 64);
-            const int road = __shfl(my_road, hbase + k, 64);
-            const int lk = __shfl(l, hbase + k, 64);
-            const float lsk = __shfl(my_ls, hbase + k, 64);
-            if (!mine || road < 0) continue;
-            if (dist < d_any) { d_any = dist; best_any = lk; ls_any = lsk; }
-            if (road == cur_road && dist < d_cur) { d_cur = dist; best_cur = lk; ls_cur = lsk; }
-            if (has_next && road == next_road && dist < d_next) { d_next = dist; best_next = lk; ls_next = lsk; }
-        }
-    }
-    if (hl != 0 || !act) return;  // lane 0 of each group commits its vehicle
-    MD_LOC_COUNT(true, road_first_hit);
-    int lane = -1;
-    float ls = 0.0f;
-    if (best_cur >= 0) { lane = best_cur; ls = ls_cur; }
-    else if (!has_next) { lane = best_any; ls = ls_any; }
-    else if (best_next >= 0) { lane = best_next; ls = ls_next; }
-    else { lane = best_any; ls = ls_any; }
-    onlane_out[n] = on_lane ? MD_FL_ON_LANE : 0u;
-    localize_commit(lanes, roads, s, n, lane, ls, sh.cx, sh.cy, nav.lane, nav.ck0, nav.ck1, nav.route_len, rroads, rnodes);
-}
-
-template <bool kRoadFirst = false>
-__device__ __forceinline__ void localize_pair(const MdWorld& w, const MdLane* lanes, const MdRoad* roads, const MdState& s, int e,
-                              int slot_a, int slot_b, int lane_id, uint32_t* onlane_out) {
-    localize_group<32, kRoadFirst>(w, lanes, roads, s, e, slot_a, slot_b, -1, -1, lane_id, onlane_out);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Contacts, one wave per vehicle.
-// ------------------------------------------------------------------------------------------------
-// Two jobs, one after the other: the movers in LDS, then the static quads through the grid.  The flag word is an OR over the hits.
-// kFlat (the lean kernel only; -DMD_CONTACTS_FLAT=0 compiles it out): the quads of the up to four cells under the chassis in ONE
-// pass -- lanes 0 .. 3 fetch their cell's cell_start pair in one trip, then wave lane t takes item t of the ranges laid end to end
-// (md_flat_cell_item), so the cell_items / quad / kind loads are made once for the whole set: four dependent round trips where
-// the nested loops make three or four per cell, each cell's behind the one before.  A box of more than four cells (no vehicle of
-// the reference's sizes on the 8 m grid) takes the nested loops.
-#ifndef MD_CONTACTS_FLAT
-#define MD_CONTACTS_FLAT 1
-#endif
-// the flag a static quad raises under the chassis `me` (0: clear of it, or a kind without a flag)
-__device__ __forceinline__ uint32_t contacts_quad_bits(const MdShape& me, const float* quads, const int32_t* qkind, int q) {
-    if (!md_obb_quad(me.cx, me.cy, me.c, me.s, me.hl, me.hw, quads + 8 * (size_t)q)) return 0u;
-    switch (qkind[q]) {
-        case MD_Q_LINE_WHITE_CONT: return MD_FL_ON_WHITE_CONT;
-        case MD_Q_LINE_YELLOW_CONT: return MD_FL_ON_YELLOW_CONT;
-        case MD_Q_LINE_BROKEN: return MD_FL_ON_BROKEN;
-        case MD_Q_SIDEWALK: return MD_FL_CRASH_SIDEWALK;
-        case MD_Q_CROSSWALK: return MD_FL_ON_CROSSWALK;
-        default: return 0u;
-    }
-}
-
-template <bool kFlat = false>
-__device__ __forceinline__ void contacts_vehicle(const MdWorld& w, const MdState& s, const MdConfig& c, int e, int slot, int lane_id,
-                                 uint32_t* cfl_out = nullptr) {
-    const int base = 0;  // env-local view
-    const int n = slot;
-    const MdShape me = s.shape[n];
-    if (!md_drives(me.flags)) return;
-    if (!(me.flags & MD_F_AGENT)) {  // traffic: nothing reads its crash / line flags (see the oracle's contacts_mover)
-        if (lane_id == 0) {
-            if (cfl_out) cfl_out[n] = 0u;
-            else s.flags[n] &= MD_FL_ON_LANE;
-        }
-        return;
-    }
-    uint32_t fl = 0;
-    MD_CONTACTS_STAMP(n == 0 && lane_id == 0, 0);
-    for (int j0 = 0; j0 < c.cap; j0 += 64) {
-        const int j = j0 + lane_id;
-        if (j >= c.cap || j == slot) continue;
-        const MdShape o = s.shape[base + j];
-        if (!md_present(o.flags)) continue;
-        const int k = md_kind_of(o.flags);
-        int hit;
-        if (md_is_circle_kind(k)) hit = md_obb_circle(me.cx, me.cy, me.c, me.s, me.hl, me.hw, o.cx, o.cy, o.hl);
-        else hit = md_obb_obb(me.cx, me.cy, me.c, me.s, me.hl, me.hw, o.cx, o.cy, o.c, o.s, o.hl, o.hw);
-        if (!hit) continue;
-        if (k == MD_KIND_VEHICLE) fl |= MD_FL_CRASH_VEHICLE;
-        else if (k == MD_KIND_CONE || k == MD_KIND_WARNING || k == MD_KIND_BARRIER) fl |= MD_FL_CRASH_OBJECT;
-        else if (k == MD_KIND_PEDESTRIAN || k == MD_KIND_CYCLIST) fl |= MD_FL_CRASH_HUMAN;
-        else if (k == MD_KIND_BUILDING) fl |= MD_FL_CRASH_BUILDING;
-    }
-    MD_CONTACTS_STAMP(n == 0 && lane_id == 0, 1);
-    // static quads through the grid: cells under the chassis AABB (+ margin)
-    const int m = w.env_map[e];
-    const MdGrid g = w.grid[m];
-    const float ext_x = md_fabs(me.c) * me.hl + md_fabs(me.s) * me.hw + 0.05f;
-    const float ext_y = md_fabs(me.s) * me.hl + md_fabs(me.c) * me.hw + 0.05f;
-    int gx0 = (int)md_floor((me.cx - ext_x - g.x0) * g.inv_cell);
-    int gx1 = (int)md_floor((me.cx + ext_x - g.x0) * g.inv_cell);
-    int gy0 = (int)md_floor((me.cy - ext_y - g.y0) * g.inv_cell);
-    int gy1 = (int)md_floor((me.cy + ext_y - g.y0) * g.inv_cell);
-    if (!(gx1 < 0 || gy1 < 0 || gx0 >= g.nx || gy0 >= g.ny)) {
-        gx0 = grid_clampi(gx0, 0, g.nx - 1);
-        gx1 = grid_clampi(gx1, 0, g.nx - 1);
-        gy0 = grid_clampi(gy0, 0, g.ny - 1);
-        gy1 = grid_clampi(gy1, 0, g.ny - 1);
-        const float* quads = w.quads + 8 * (size_t)w.quad_off[m];
-        const int32_t* qkind = w.quad_kind + w.quad_off[m];
-        const int ncx = gx1 - gx0 + 1, n_cells = ncx * (gy1 - gy0 + 1);
-        if (kFlat && n_cells <= 4) {
-            // lanes 0 .. n_cells - 1: their cell's range, the cells in the nested loops' order (the box row by row, gx ascending)
-            int my0 = 0, myn = 0;
-            if (lane_id < n_cells) {
-                const int cell = g.cell_base + (gy0 + lane_id / ncx) * g.nx + gx0 + lane_id % ncx;
-                my0 = w.cell_start[cell];
-                myn = w.cell_start[cell + 1] - my0;
-                if (myn < 0) myn = 0;
-            }
-            const int s0 = __builtin_amdgcn_readlane(my0, 0), s1 = __builtin_amdgcn_readlane(my0, 1);
-            const int s2 = __builtin_amdgcn_readlane(my0, 2), s3 = __builtin_amdgcn_readlane(my0, 3);
-            const int n0 = __builtin_amdgcn_readlane(myn, 0), n1 = __builtin_amdgcn_readlane(myn, 1);
-            const int n2 = __builtin_amdgcn_readlane(myn, 2), n3 = __builtin_amdgcn_readlane(myn, 3);
-            const int total = n0 + n1 + n2 + n3;   // the loop's bound: wave-uniform, known before it starts
-            MD_CONTACTS_COUNT(n == 0 && lane_id == 0, n_cells, total);
-            for (int t = lane_id; t < total; t += 64) {
-                int off;
-                const int k = md_flat_cell_item(n0, n1, n2, n3, t, &off);
-                const int item = w.cell_items[(k == 0 ? s0 : k == 1 ? s1 : k == 2 ? s2 : s3) + off];
-                if (item >= 0) continue;  // lane item
-                fl |= contacts_quad_bits(me, quads, qkind, ~item);
-            }
-        } else
-        for (int gy = gy0; gy <= gy1; ++gy)
-            for (int gx = gx0; gx <= gx1; ++gx) {
-                const int cell = g.cell_base + gy * g.nx + gx;
-                const int it0 = w.cell_start[cell], it1 = w.cell_start[cell + 1];
-                MD_CONTACTS_COUNT(n == 0 && lane_id == 0, 1, it1 > it0 ? it1 - it0 : 0);
-                for (int it = it0 + lane_id; it < it1; it += 64) {
-                    const int item = w.cell_items[it];
-                    if (item >= 0) continue;  // lane item
-                    const int q = ~item;
-                    if (!md_obb_quad(me.cx, me.cy, me.c, me.s, me.hl, me.hw, quads + 8 * (size_t)q)) continue;
-                    switch (qkind[q]) {   // (contacts_quad_bits in words: through the helper, seven other kernels' register lines move)
-                        case MD_Q_LINE_WHITE_CONT: fl |= MD_FL_ON_WHITE_CONT; break;
-                        case MD_Q_LINE_YELLOW_CONT: fl |= MD_FL_ON_YELLOW_CONT; break;
-                        case MD_Q_LINE_BROKEN: fl |= MD_FL_ON_BROKEN; break;
-                        case MD_Q_SIDEWALK: fl |= MD_FL_CRASH_SIDEWALK; break;
-                        case MD_Q_CROSSWALK: fl |= MD_FL_ON_CROSSWALK; break;
-                        default: break;
-                    }
-                }
-            }
-    }
-    MD_CONTACTS_STAMP(n == 0 && lane_id == 0, 2);
-    // wave OR-reduce of the flag word: one ballot per flag bit that can be set here
-    uint32_t all = 0;
-#pragma unroll
-    for (int b = 0; b < 9; ++b) {
-        const uint32_t bit = 1u << b;
-        if (__ballot((fl & bit) != 0) != 0ull) all |= bit;
-    }
-    if (lane_id == 0) {
-        if (cfl_out) cfl_out[n] = all;
-        else s.flags[n] = (s.flags[n] & MD_FL_ON_LANE) | all;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// IDM for one traffic vehicle, executed by one wave: lanes = candidate objects; the lead / rear
-// vehicle gap scan is a wavefront min-reduction (key = gap, tie -> lowest slot), which is the
-// order-independent form of FrontBackObjects.get_find_front_back_objs (policy/idm_policy.py:82-132).
-// Stages A (route bookkeeping) and C (lane-change policy, PID steering, IDM acceleration) are
-// scalar and run on lane 0.
-// ------------------------------------------------------------------------------------------------
-// The scan's LDS words, after the compacted candidate list (wave_list[0..20]): the six gap minima, (scanned lane i,
-// front / back) at 64-bit word i * 2 + {0, 1}, and the ego's Frenet data on the scanned lanes for stage C.
-constexpr int kIdmKeyWord = 24;       // int index of the first 64-bit key (8-B aligned: the scratch is 16-B aligned)
-constexpr int kIdmLatWord = 40;       // + k: lateral offset on scanned lane k
-constexpr int kIdmHeadWord = 44;      // + k: the lane's heading 1 m ahead of the ego's longitudinal on it
-constexpr unsigned long long kNoGap = ~0ull;
-
-// (gap, slot) as one unsigned key: the gap's bits mapped so that unsigned order is float order across the sign (a connected
-// lane's back gap can be negative), +-0 alike, the slot in the low word so that equal gaps keep the lowest slot.
-__device__ __forceinline__ unsigned long long gap_key(float g, int slot) {
-    const unsigned u = __float_as_uint(g);
-    const unsigned o = (g == 0.0f) ? 0x80000000u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-    return ((unsigned long long)o << 32) | (unsigned)slot;
-}
-__device__ __forceinline__ float gap_of_key(unsigned long long k) {
-    const unsigned o = (unsigned)(k >> 32);
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-
-// Reads the six minima back into fb (wave-uniform); returns bit i*2 (front) / i*2+1 (back) for every bucket that holds one.
-__device__ __forceinline__ int gap_keys_read(const unsigned long long* keys, FrontBack& fb) {
-    int found = 0;
-#pragma unroll
-    for (int b = 0; b < 6; ++b) {
-        const unsigned long long k = keys[b];
-        if (k != kNoGap) {
-            found |= 1 << b;
-            if (b & 1) { fb.back_d[b >> 1] = gap_of_key(k); fb.back[b >> 1] = (int)(unsigned)k; }
-            else { fb.front_d[b >> 1] = gap_of_key(k); fb.front[b >> 1] = (int)(unsigned)k; }
-        }
-    }
-    return found;
-}
-
-// arg-min of (key, slot) over the wave; lanes holding kInf do not take part.  Ascending lane order
-// == ascending slot order, so the strict `<` keeps the lowest slot among equal keys.
-__device__ __forceinline__ void wave_argmin(float& key, int& slot) {
-    unsigned long long m = __ballot(key < 3.0e38f);
-    float bk = 3.0e38f;
-    int bs = 0x7fffffff;
-    while (m) {
-        const int l = __ffsll((long long)m) - 1;
-        m &= m - 1;
-        const float k = __shfl(key, l, 64);
-        const int sl = __shfl(slot, l, 64);
-        if (k < bk) {
-            bk = k;
-            bs = sl;
-        }
-    }
-    key = bk;
-    slot = bs;
-}
-
-// Nothing found on any scanned lane, and no lane scanned yet (the scans set exist[] from their plan).
-__device__ __forceinline__ void front_back_clear(FrontBack& fb) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        fb.front[i] = fb.back[i] = -1;
-        fb.exist[i] = 0;
-        fb.front_d[i] = fb.back_d[i] = IDM_MAX_LONG_DIST;
-    }
-}
-
-// The candidate objects of the vehicle in `slot` at (px, py) (get_surrounding_objects: within 50 m, present, not the vehicle
-// itself), compacted in ascending slot order into wave_list: usually a handful, whatever the slot capacity is.  Returns their
-// number (wave-uniform); only the first 21 are listed.  The caller syncs the wave's LDS before it reads wave_list.
-__device__ __forceinline__ int idm_candidates_wave(const MdState& s, const MdConfig& c, int slot, int lane_id, float px, float py,
-                                                   int* wave_list, MdIdmPlan& plan) {
-    int n_cand = 0;
-    bool sees_participant = false;  // a pedestrian / cyclist among them: the reference's object loop raises (md_idm_sees_participant)
-    for (int j0 = 0; j0 < c.cap; j0 += 64) {
-        const int j = j0 + lane_id;
-        const bool is_c = j < c.cap && j != slot && md_idm_is_candidate(&s.shape[j < c.cap ? j : 0], px, py);
-        const unsigned long long mk = __ballot(is_c);
-        if (__ballot(is_c && md_is_participant_kind(md_kind_of(s.shape[j < c.cap ? j : 0].flags))) != 0ull) sees_participant = true;
-        const int rank = n_cand + __popcll(mk & ((1ull << lane_id) - 1ull));
-        if (is_c && rank < 21) wave_list[rank] = j;
-        n_cand += __popcll(mk);
-    }
-    if (sees_participant) {  // wave-uniform: bare-except fallback, nothing is scanned
-        plan.fail = 1;
-        n_cand = 0;
-    }
-    return n_cand;
-}
-
-// More than 21 candidates (three pairs each no longer fit the wave), the general capacity: per scanned lane, lanes = objects
-// (two passes, chunks of 64 objects), arg-min walks.
-__device__ __forceinline__ void idm_scan_walks(const MdLane* lanes, const MdState& s, const MdConfig& c, int slot, int lane_id, float px,
-                                               float py, const MdIdmPlan& plan, const float (&cur_long)[3],
-                                               const float (&left_long)[3], FrontBack& fb) {
-    constexpr float kInf = 3.0e38f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        if (plan.ids[i] < 0) continue;  // wave-uniform
-        const MdLane* L = &lanes[plan.ids[i]];
-        int found_front = 0, found_back = 0;
-        for (int j0 = 0; j0 < c.cap; j0 += 64) {
-            const int j = j0 + lane_id;
-            float kf = kInf, kb = kInf;
-            if (j < c.cap && j != slot && md_idm_is_candidate(&s.shape[j], px, py) &&
-                md_obj_lane_of(&s, j) == plan.ids[i]) {
-                const float lg = md_fb_same_lane_gap(L, cur_long[i], &s.shape[j]);
-                if (lg > 0.0f && lg < IDM_MAX_LONG_DIST) kf = lg;
-                if (lg < 0.0f && md_fabs(lg) < IDM_MAX_LONG_DIST) kb = md_fabs(lg);
-            }
-            int jf = j, jb = j;
-            wave_argmin(kf, jf);
-            wave_argmin(kb, jb);
-            if (kf < fb.front_d[i]) { fb.front_d[i] = kf; fb.front[i] = jf; found_front = 1; }
-            if (kb < fb.back_d[i]) { fb.back_d[i] = kb; fb.back[i] = jb; found_back = 1; }
-        }
-        if (found_front && found_back) continue;
-        for (int j0 = 0; j0 < c.cap; j0 += 64) {
-            const int j = j0 + lane_id;
-            float kf = kInf, kb = kInf;
-            if (j < c.cap && j != slot && md_idm_is_candidate(&s.shape[j], px, py)) {
-                const int ol = md_obj_lane_of(&s, j);
-                if (ol >= 0 && ol != plan.ids[i]) {
-                    float lg;
-                    const int cls = md_fb_neighbour(L, &lanes[ol], cur_long[i], left_long[i], &s.shape[j],
-                                                    !found_front, !found_back, &lg);
-                    if (cls == 1 && lg > 0.0f && lg < IDM_MAX_LONG_DIST) kf = lg;
-                    if (cls == 2 && lg < IDM_MAX_LONG_DIST) kb = lg;
-                }
-            }
-            int jf = j, jb = j;
-            wave_argmin(kf, jf);
-            wave_argmin(kb, jb);
-            if (kf < fb.front_d[i]) { fb.front_d[i] = kf; fb.front[i] = jf; }
-            if (kb < fb.back_d[i]) { fb.back_d[i] = kb; fb.back[i] = jb; }
-        }
-    }
-}
-
-// The object scan of one vehicle by the whole wave.  `plan` is wave-uniform (may come back with fail = 1: a traffic
-// participant among the candidates), `fb` is the wave-uniform result.
-// wave_list: >= 24 ints of LDS private to this wave (the compacted candidate list)
-__device__ __forceinline__ void idm_scan_wave(const MdLane* lanes, const MdState& s, const MdConfig& c, int slot, int lane_id,
-                              int* wave_list, MdIdmPlan& plan, FrontBack& fb) {
-    constexpr float kInf = 3.0e38f;
-    front_back_clear(fb);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) fb.exist[i] = plan.ids[i] >= 0 && !plan.fail;
-    if (!plan.fail) {
-        const float px = s.shape[slot].cx, py = s.shape[slot].cy;
-        // (1) ego longitudinal on the three scanned lanes: lanes 0..2 evaluate one each, then broadcast
-        float my_cur = 0.0f;
-        {
-            const int my_id = (lane_id == 0) ? plan.ids[0] : ((lane_id == 1) ? plan.ids[1] : ((lane_id == 2) ? plan.ids[2] : -1));
-            if (my_id >= 0) {
-                float tmp;
-                md_lane_local(&lanes[my_id], px, py, &my_cur, &tmp);
-            }
-        }
-        float cur_long[3], left_long[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            cur_long[i] = bcast_f(my_cur, i);
-            left_long[i] = (plan.ids[i] >= 0) ? lanes[plan.ids[i]].length - cur_long[i] : 0.0f;
-        }
-        const int n_cand = idm_candidates_wave(s, c, slot, lane_id, px, py, wave_list, plan);
-        wave_lds_sync();
-        const int npairs = n_cand * 3;
-        if (npairs <= 63) {
-            // (2) every (scanned lane i, candidate j) pair on its own lane of the wave: ONE Frenet evaluation
-            //     per pair (on lane i for a same-lane object, on the object's lane for a connected one)
-            float val = 0.0f;
-            int meta = 0;  // bit0 same-lane, bit1 lane i precedes obj lane, bit2 obj lane precedes lane i, bits 4-5 i, bits 8.. j
-            if (n_cand > 0) {
-                const int p = lane_id;
-                const int i = p / n_cand;
-                const int j = (p < npairs) ? wave_list[p - i * n_cand] : 0;
-                const int id_i = (i == 0) ? plan.ids[0] : ((i == 1) ? plan.ids[1] : plan.ids[2]);
-                const float cur_i = (i == 0) ? cur_long[0] : ((i == 1) ? cur_long[1] : cur_long[2]);
-                if (p < npairs && id_i >= 0) {
-                    const int ol = md_obj_lane_of(&s, j);
-                    const MdLane* L = &lanes[id_i];
-                    int mt = (i << 4) | (j << 8);
-                    // one Frenet evaluation per pair: on lane i for a same-lane object, else on the object's lane
-                    const MdLane* EL = L;
-                    if (ol == id_i) mt |= 1;
-                    else if (ol >= 0) {
-                        EL = &lanes[ol];
-                        mt |= (md_lane_is_previous_of(L, EL) ? 2 : 0) | (md_lane_is_previous_of(EL, L) ? 4 : 0);
-                    }
-                    if (mt & 7) {
-                        float os, ot;
-                        md_lane_local(EL, s.shape[j].cx, s.shape[j].cy, &os, &ot);
-                        val = (mt & 1) ? os - cur_i : os;
-                    }
-                    meta = mt;
-                }
-            }
-            // (3) per scanned lane: arg-min reductions (same-lane objects first, connected lanes only if none)
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                if (plan.ids[i] < 0) continue;  // wave-uniform
-                int found_front = 0, found_back = 0;
-                const bool mine = ((meta >> 4) & 3) == i;
-                {
-                    const bool same = mine && (meta & 1);
-                    float kf = (same && val > 0.0f && val < IDM_MAX_LONG_DIST) ? val : kInf;
-                    float kb = (same && val < 0.0f && md_fabs(val) < IDM_MAX_LONG_DIST) ? md_fabs(val) : kInf;
-                    int jf = meta >> 8, jb = meta >> 8;
-                    wave_argmin(kf, jf);
-                    wave_argmin(kb, jb);
-                    if (kf < fb.front_d[i]) { fb.front_d[i] = kf; fb.front[i] = jf; found_front = 1; }
-                    if (kb < fb.back_d[i]) { fb.back_d[i] = kb; fb.back[i] = jb; found_back = 1; }
-                }
-                if (found_front && found_back) continue;
-                float kf = kInf, kb = kInf;
-                if (mine && !(meta & 1) && (meta & 6)) {
-                    // md_fb_neighbour's choice: front if (need_front && L precedes OL), else back if (need_back && OL precedes L)
-                    if (!found_front && (meta & 2)) {
-                        const float lg = val + left_long[i];
-                        if (lg > 0.0f && lg < IDM_MAX_LONG_DIST) kf = lg;
-                    } else if (!found_back && (meta & 4)) {
-                        const float lg = lanes[md_obj_lane_of(&s, meta >> 8)].length - val + cur_long[i];
-                        if (lg < IDM_MAX_LONG_DIST) kb = lg;
-                    }
-                }
-                int jf = meta >> 8, jb = meta >> 8;
-                wave_argmin(kf, jf);
-                wave_argmin(kb, jb);
-                if (kf < fb.front_d[i]) { fb.front_d[i] = kf; fb.front[i] = jf; }
-                if (kb < fb.back_d[i]) { fb.back_d[i] = kb; fb.back[i] = jb; }
-            }
-        } else {
-            idm_scan_walks(lanes, s, c, slot, lane_id, px, py, plan, cur_long, left_long, fb);   // more than 21 candidates
-        }
-    }
-}
-
-// The same scan in the one-vehicle form (idm_vehicle_wave of the lean single-agent kernel): the minima of each round
-// (same-lane objects, then connected-lane objects for the buckets left empty) are LDS atomic mins of gap_key, one per wave
-// lane at most, instead of arg-min walks; and the ego's lateral offset and the lane heading 1 m ahead on each scanned lane
-// are left at kIdmLatWord / kIdmHeadWord for stage C (its steering lane is one of them), evaluated before the participant
-// check so that the fallback has them.  More than 21 candidates (three pairs each no longer fit the wave): the walks.
-// wave_list: >= 48 ints of LDS private to this wave (the compacted candidate list, the keys, the carried Frenet data)
-__device__ __forceinline__ void idm_scan_wave_keys(const MdLane* lanes, const MdState& s, const MdConfig& c, int slot, int lane_id,
-                                   int* wave_list, MdIdmPlan& plan, FrontBack& fb) {
-    unsigned long long* keys = reinterpret_cast<unsigned long long*>(wave_list + kIdmKeyWord);
-    front_back_clear(fb);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) fb.exist[i] = plan.ids[i] >= 0 && !plan.fail;
-    if (!plan.fail) {
-        const float px = s.shape[slot].cx, py = s.shape[slot].cy;
-        // (1) ego Frenet coordinates on the three scanned lanes: lanes 0..2 evaluate one each, then broadcast
-        float my_cur = 0.0f, my_left = 0.0f;
-        {
-            const int my_id = (lane_id == 0) ? plan.ids[0] : ((lane_id == 1) ? plan.ids[1] : ((lane_id == 2) ? plan.ids[2] : -1));
-            if (my_id >= 0) {
-                const MdLane* L = &lanes[my_id];
-                float lat;
-                md_lane_local(L, px, py, &my_cur, &lat);
-                my_left = L->length - my_cur;
-                reinterpret_cast<float*>(wave_list)[kIdmLatWord + lane_id] = lat;
-                reinterpret_cast<float*>(wave_list)[kIdmHeadWord + lane_id] = md_lane_heading_at(L, my_cur + 1.0f);
-            }
-            if (lane_id < 6) keys[lane_id] = kNoGap;
-        }
-        float cur_long[3], left_long[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            cur_long[i] = bcast_f(my_cur, i);
-            left_long[i] = (plan.ids[i] >= 0) ? bcast_f(my_left, i) : 0.0f;
-        }
-        const int n_cand = idm_candidates_wave(s, c, slot, lane_id, px, py, wave_list, plan);
-        wave_lds_sync();
-        if (n_cand == 0) return;
-        const int npairs = n_cand * 3;
-        if (npairs <= 63) {
-            // (2) every (scanned lane i, candidate j) pair on its own lane of the wave: ONE Frenet evaluation
-            //     per pair (on lane i for a same-lane object, on the object's lane for a connected one).  va: the
-            //     same-lane gap, or the connected lane's front gap; vb: the connected lane's back gap.
-            float va = 0.0f, vb = 0.0f;
-            int meta = 0;  // bit0 same-lane, bit1 lane i precedes obj lane, bit2 obj lane precedes lane i, bits 4-5 i, bits 8.. j
-            {
-                const int p = lane_id;
-                const int i = p / n_cand;
-                const int j = (p < npairs) ? wave_list[p - i * n_cand] : 0;
-                const int id_i = (i == 0) ? plan.ids[0] : ((i == 1) ? plan.ids[1] : plan.ids[2]);
-                const float cur_i = (i == 0) ? cur_long[0] : ((i == 1) ? cur_long[1] : cur_long[2]);
-                const float left_i = (i == 0) ? left_long[0] : ((i == 1) ? left_long[1] : left_long[2]);
-                if (p < npairs && id_i >= 0) {
-                    const int ol = md_obj_lane_of(&s, j);
-                    const MdLane* L = &lanes[id_i];
-                    int mt = (i << 4) | (j << 8);
-                    const MdLane* EL = L;
-                    if (ol == id_i) mt |= 1;
-                    else if (ol >= 0) {
-                        EL = &lanes[ol];
-                        mt |= (md_lane_is_previous_of(L, EL) ? 2 : 0) | (md_lane_is_previous_of(EL, L) ? 4 : 0);
-                    }
-                    if (mt & 7) {
-                        float os, ot;
-                        md_lane_local(EL, s.shape[j].cx, s.shape[j].cy, &os, &ot);
-                        if (mt & 1) va = os - cur_i;
-                        else {
-                            va = os + left_i;                 // md_fb_neighbour's front gap
-                            vb = EL->length - os + cur_i;     // and its back gap
-                        }
-                    }
-                    meta = mt;
-                }
-            }
-            {
-                const int b0 = ((meta >> 4) & 3) * 2;  // this pair's front bucket; + 1: back
-                // (3) round 1: same-lane objects, one gap per pair
-                if (meta & 1) {
-                    if (va > 0.0f && va < IDM_MAX_LONG_DIST) atomicMin(&keys[b0], gap_key(va, meta >> 8));
-                    else if (va < 0.0f && md_fabs(va) < IDM_MAX_LONG_DIST) atomicMin(&keys[b0 + 1], gap_key(md_fabs(va), meta >> 8));
-                }
-                wave_lds_sync();
-                const int found = gap_keys_read(keys, fb);
-                // round 2: connected-lane objects, for the buckets of a scanned lane that round 1 did not fill both of
-                // (md_fb_neighbour's choice: front if (need_front && L precedes OL), else back if (need_back && OL precedes L))
-                bool more = false;
-                if (!(meta & 1) && (meta & 6)) {
-                    const bool ff = (found >> b0) & 1, fbk = (found >> (b0 + 1)) & 1;
-                    if (!(ff && fbk)) {
-                        if (!ff && (meta & 2)) {
-                            if (va > 0.0f && va < IDM_MAX_LONG_DIST) { atomicMin(&keys[b0], gap_key(va, meta >> 8)); more = true; }
-                        } else if (!fbk && (meta & 4)) {
-                            if (vb < IDM_MAX_LONG_DIST) { atomicMin(&keys[b0 + 1], gap_key(vb, meta >> 8)); more = true; }
-                        }
-                    }
-                }
-                if (__ballot(more) != 0ull) {
-                    wave_lds_sync();
-                    gap_keys_read(keys, fb);
-                }
-            }
-        } else {
-            idm_scan_walks(lanes, s, c, slot, lane_id, px, py, plan, cur_long, left_long, fb);   // more than 21 candidates
-        }
-    }
-}
-
-// One vehicle at a time: plan on lane 0, scan by the wave, decide on lane 0 (the workgroup-per-env kernels' form).
-// kKeys (the lean single-agent kernel; the other variants keep the walk form, which their registers prefer): the scan is
-// idm_scan_wave_keys and stage C steers by the ego's Frenet data that it carried for the scanned lanes, with no lane record
-// load or projection of its own.
-template <bool kKeys>
-__device__ __forceinline__ void idm_vehicle_wave(const MdWorld& w, const MdLane* lanes, const MdRoad* roads, const MdState& s,
-                                 const MdConfig& c, int m, int slot, int lane_id, int* wave_list) {
-    MdIdmPlan plan;
-    plan.success = plan.use_ref = plan.fail = 0;
-    plan.ids[0] = plan.ids[1] = plan.ids[2] = -1;
-    const bool st_ = (slot == c.agents_per_env) && lane_id == 0;
-    (void)st_;
-    MD_FINE_STAMP(st_, 4);
-    if (lane_id == 0) md_idm_plan(&w, lanes, roads, &s, &c, m, slot, &plan);
-    if constexpr (!kKeys) {
-        plan.success = bcast_i(plan.success, 0);
-        plan.use_ref = bcast_i(plan.use_ref, 0);
-        plan.fail = bcast_i(plan.fail, 0);
-        plan.ids[0] = bcast_i(plan.ids[0], 0);
-        plan.ids[1] = bcast_i(plan.ids[1], 0);
-        plan.ids[2] = bcast_i(plan.ids[2], 0);
-        MD_FINE_STAMP(st_, 5);
-        FrontBack fb;
-        idm_scan_wave(lanes, s, c, slot, lane_id, wave_list, plan, fb);
-        MD_FINE_STAMP(st_, 6);
-        if (lane_id == 0) md_idm_decide(lanes, roads, &s, slot, &plan, &fb);
-    } else {
-        plan.success = __builtin_amdgcn_readlane(plan.success, 0);
-        plan.use_ref = __builtin_amdgcn_readlane(plan.use_ref, 0);
-        plan.fail = __builtin_amdgcn_readlane(plan.fail, 0);
-        plan.ids[0] = __builtin_amdgcn_readlane(plan.ids[0], 0);
-        plan.ids[1] = __builtin_amdgcn_readlane(plan.ids[1], 0);
-        plan.ids[2] = __builtin_amdgcn_readlane(plan.ids[2], 0);
-        MD_FINE_STAMP(st_, 5);
-        FrontBack fb;
-        idm_scan_wave_keys(lanes, s, c, slot, lane_id, wave_list, plan, fb);
-        MD_FINE_STAMP(st_, 6);
-        if (lane_id == 0) {
-            int front_obj;
-            float front_dist;
-            const float speed_kmh = md_fabs(s.dyn[slot].speed) * 3.6f;
-            const int steer = md_idm_policy(lanes, roads, &s, slot, &plan, &fb, &front_obj, &front_dist);
-            if (steer < 0) {  // never localised: coast straight
-                s.action[2 * slot] = 0.0f;
-                s.action[2 * slot + 1] = 0.0f;
-            } else {
-                // md_idm_policy steers on one of the scanned lanes, so k = 2 below stands for ids[2]: every branch that steers
-                // to tidx -/+ 1 needs fb.exist[0 / 2], or a lane inside [avail_lo, avail_hi] with avail_lo >= 0 and
-                // avail_hi <= ncur - 1, which md_idm_plan scanned.  A policy that steered anywhere else would need the
-                // projection of md_idm_decide here (it costs this kernel 8 more spilled SGPRs, so it is not kept as a fallback).
-                const int k = (steer == plan.ids[0]) ? 0 : ((steer == plan.ids[1]) ? 1 : 2);
-                const float* wf = reinterpret_cast<const float*>(wave_list);
-                md_idm_act(&s, slot, speed_kmh, front_obj, front_dist, wf[kIdmLatWord + k], wf[kIdmHeadWord + k]);
-            }
-        }
-    }
-    MD_FINE_STAMP(st_, 7);
-}
-
-// All vehicles of `mask` (bit j = slot j0 + j; <= 64 of them): stage A (route bookkeeping) and stage C (lane-change
-// policy, PID steering, IDM acceleration) are per-vehicle scalar code, so every vehicle runs them on ITS OWN lane, all
-// at once; only the object scans in between go vehicle by vehicle, each by the whole wave.  Same arithmetic per
-// vehicle; the decisions do not depend on each other (a decision reads poses / speeds / lanes, and writes only its
-// own action, PID and lane-change state).  The one-wave-per-env kernel's form.
-__device__ __forceinline__ void idm_group_wave(const MdWorld& w, const MdLane* lanes, const MdRoad* roads, const MdState& s,
-                               const MdConfig& c, int m, int j0, unsigned long long mask, int lane_id, int* wave_list) {
-    const int my_slot = j0 + lane_id;
-    const bool mine = (mask >> lane_id) & 1ull;
-    MdIdmPlan plan;
-    plan.success = plan.use_ref = plan.fail = 0;
-    plan.ids[0] = plan.ids[1] = plan.ids[2] = -1;
-    if (mine) md_idm_plan(&w, lanes, roads, &s, &c, m, my_slot, &plan);
-    FrontBack fb;
-    front_back_clear(fb);
-    unsigned long long todo = mask;
-    while (todo) {
-        const int v = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        MdIdmPlan up;   // vehicle v's plan, wave-uniform
-        up.success = bcast_i(plan.success, v);
-        up.use_ref = bcast_i(plan.use_ref, v);
-        up.fail = bcast_i(plan.fail, v);
-        up.ids[0] = bcast_i(plan.ids[0], v);
-        up.ids[1] = bcast_i(plan.ids[1], v);
-        up.ids[2] = bcast_i(plan.ids[2], v);
-        FrontBack ufb;
-        idm_scan_wave(lanes, s, c, j0 + v, lane_id, wave_list, up, ufb);
-        wave_lds_sync();   // the next scan reuses wave_list
-        if (lane_id == v) {
-            plan.fail = up.fail;
-            fb = ufb;
-        }
-    }
-    if (mine) md_idm_decide(lanes, roads, &s, my_slot, &plan, &fb);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Observation / reward / done of one agent by one wave: the nine independent geometric evaluations
-// (md_observe_task) run on lanes 0..8 at once, lane 0 gathers them with v_readlane and combines.
-// ------------------------------------------------------------------------------------------------
-// A/B builds: -DMD_OBS_LOCKSTEP=0 compiles the lean kernel with the serial tasks (md_observe_task) like every other kernel
-#ifndef MD_OBS_LOCKSTEP
-#define MD_OBS_LOCKSTEP 1
-#endif
-// One agent per wave (`a` wave-uniform: its context lives in scalar registers) -- the single-agent envs' form.
-// kLockstep (the lean kernel): the tasks as md_observe_lane, sixteen lanes on one straight-line sequence of three square
-// roots and three quotients instead of nine lanes on four bodies run one after the other; same 45 words in the scratch.
-//
-// The observation AHEAD (the lean kernel; -DMD_OBS_AHEAD=0 compiles it out).  In an env whose locate stage leaves a wave without an item
-// (one or two driving vehicles: localisations + the agent's contacts < the waves), that wave evaluates agent 0's context and tasks
-// DURING the locate stage (observe_ahead_wave) into wave 0's observe scratch, which nothing touches before the observe stage.  All
-// they read is final by then but five words of the agent's MdNav (MdObsKey), which the localisation on wave 0 may be committing at
-// that moment.  The ahead wave reads each of the five ONCE into registers, evaluates from those registers and stores the same
-// registers beside the results; wave 0, behind the stage barriers, keeps the results iff the stored words equal the committed
-// ones.  A torn read is harmless: every word read is the old or the new value of that word (valid indices both), context and
-// results are a pure function of the words read, and a mix of old and new that differs from the committed key is a miss like any
-// other.  On a hit wave 0 goes straight to the combine, with the few context words it needs (MdObsHand) from the scratch too.
-// The hand-over's words in wave 0's 48-word scratch: 45 .. 47 and result slots that md_observe_combine_of never reads (tasks 0 and 2
-// have two results, task 1 one; md_observe_lane writes only the words that are results):
-enum ObsAheadWord : int {
-    kAhMark = 45,                                                          // evaluated in this step (zeroed at stage-in)
-    kAhLane = 46, kAhRoad0 = 47, kAhRoad1 = 2, kAhCk0 = 3, kAhCk1 = 4,     // the MdObsKey the evaluation used
-    kAhValid = 6, kAhCurW = 7, kAhCurN = 8, kAhPosRoad = 9, kAhFinLen = 12 // MdObsHand (cur_block, the speed limit: tollgate envs only)
-};
-#ifndef MD_OBS_AHEAD
-#define MD_OBS_AHEAD 1
-#endif
-__device__ __forceinline__ void observe_ahead_wave(const MdLane* lanes, const MdRoad* roads, const MdState& s, const MdConfig& c, int lane_id,
-                                                   float* scratch0 /* wave 0's observe scratch */) {
-    constexpr int a = 0;
-    MD_AHEAD_STAMP(lane_id == 0, 2);
-    // volatile: one load per word, never made again
-    const volatile int32_t* nv = reinterpret_cast<const volatile int32_t*>(&s.nav[a]);
-    MdObsKey q;
-    q.lane = __builtin_amdgcn_readfirstlane(nv[offsetof(MdNav, lane) / 4]);
-    q.road0 = __builtin_amdgcn_readfirstlane(nv[offsetof(MdNav, road0) / 4]);
-    q.road1 = __builtin_amdgcn_readfirstlane(nv[offsetof(MdNav, road1) / 4]);
-    q.ck0 = __builtin_amdgcn_readfirstlane(nv[offsetof(MdNav, ck0) / 4]);
-    q.ck1 = __builtin_amdgcn_readfirstlane(nv[offsetof(MdNav, ck1) / 4]);
-    MdObsCtx k;
-    md_observe_ctx_of(lanes, roads, &s, a, &q, &k);
-    if (lane_id < MD_OBS_TASKS * 5) scratch0[lane_id] = 0.0f;
-    md_observe_lane(lane_id, &k, &s, &c, a, scratch0);
-    if (lane_id == 0) {   // behind the lanes' results (an LDS unit runs a wave's writes in order)
-        int* w = reinterpret_cast<int*>(scratch0);
-        w[kAhLane] = q.lane;
-        w[kAhRoad0] = q.road0;
-        w[kAhRoad1] = q.road1;
-        w[kAhCk0] = q.ck0;
-        w[kAhCk1] = q.ck1;
-        w[kAhValid] = k.valid;
-        scratch0[kAhCurW] = k.cur_w;
-        scratch0[kAhCurN] = k.cur_n;
-        scratch0[kAhPosRoad] = k.positive_road;
-        scratch0[kAhFinLen] = k.fin->length;
-        w[kAhMark] = 1;
-    }
-    MD_AHEAD_COUNT(lane_id == 0, MD_AHEAD_EVALUATED);
-    MD_AHEAD_STAMP(lane_id == 0, 5);
-}
-
-// kAhead: agent 0's results may stand in the scratch already (above)
-template <bool kLockstep = false, bool kAhead = false>
-__device__ __forceinline__ void observe_agent_wave1(const MdLane* lanes, const MdRoad* roads, const MdState& s, const MdConfig& c, int a,
-                                    int just_reset, int lane_id, float* wave_scratch /* LDS, MD_OBS_TASKS*5 floats */) {
-    MdObsCtx k;
-    MD_FINE_STAMP(a == 0 && lane_id == 0, 8);
-    if constexpr (kAhead) {
-        if (a == 0) {
-            const int* w = reinterpret_cast<const int*>(wave_scratch);
-            const MdObsKey q = {w[kAhLane], w[kAhRoad0], w[kAhRoad1], w[kAhCk0], w[kAhCk1]};
-            const int hit = w[kAhMark] != 0 && md_obs_key_same(&q, &s.nav[a]);
-            if (__builtin_amdgcn_readfirstlane(hit)) {
-                MD_AHEAD_COUNT(lane_id == 0, MD_AHEAD_HIT);
-                MD_FINE_STAMP(lane_id == 0, 9);
-                MD_FINE_STAMP(lane_id == 0, 10);
-                if (lane_id == 0) {
-                    const MdObsHand h = {w[kAhValid], wave_scratch[kAhCurW], wave_scratch[kAhCurN], wave_scratch[kAhPosRoad], 0,
-                                         &wave_scratch[kAhFinLen], nullptr};
-                    md_observe_combine_of(&h, &s, &c, a, just_reset, (const float (*)[5])wave_scratch);
-                }
-                __builtin_amdgcn_wave_barrier();
-                MD_FINE_STAMP(lane_id == 0, 11);
-                return;
-            }
-            MD_AHEAD_COUNT(lane_id == 0, MD_AHEAD_MISS);
-        }
-    }
-    md_observe_ctx(lanes, roads, &s, a, &k);
-    MD_FINE_STAMP(a == 0 && lane_id == 0, 9);
-    if constexpr (kLockstep) {
-        // the lanes write one or two words each: the rest of the 45 are zeros (an LDS unit runs a wave's writes in order)
-        if (lane_id < MD_OBS_TASKS * 5) wave_scratch[lane_id] = 0.0f;
-        md_observe_lane(lane_id, &k, &s, &c, a, wave_scratch);   // lanes 0 .. MD_OBS_LANES - 1 write
-    } else if (lane_id < MD_OBS_TASKS) {
-        float mine[5];
-        md_observe_task(lane_id, &k, &s, &c, a, mine);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) wave_scratch[lane_id * 5 + i] = mine[i];
-    }
-    wave_lds_sync();
-    MD_FINE_STAMP(a == 0 && lane_id == 0, 10);
-    if (lane_id == 0) md_observe_combine(&k, &s, &c, a, just_reset, (const float (*)[5])wave_scratch);
-    __builtin_amdgcn_wave_barrier();
-    MD_FINE_STAMP(a == 0 && lane_id == 0, 11);
-}
-
-// Up to FOUR agents per wave: 16-lane group g serves agent a_base + g (tasks on its lanes 0..8, combine on its
-// lane 0): a 40-agent env finishes in 3 rounds of 4 waves instead of 10 (multi-agent kernels only).
-constexpr int kObsGroups = 4;
-constexpr int kObsScratch = kObsGroups * 48;  // floats of LDS per wave: MD_OBS_TASKS * 5 (= 45) per group, padded
-
-__device__ __forceinline__ void observe_agent_wave(const MdLane* lanes, const MdRoad* roads, const MdState& s, const MdConfig& c, int a_base,
-                                   int just_reset, int lane_id, float* wave_scratch /* LDS, kObsScratch floats */) {
-    const int g = lane_id >> 4, sub = lane_id & 15;
-    const int a = a_base + g;
-    const bool live = a < c.agents_per_env;
-    float* scratch = wave_scratch + g * 48;
-    MdObsCtx k;
-    if (live) md_observe_ctx(lanes, roads, &s, a, &k);
-    if (live && sub < MD_OBS_TASKS) {
-        float mine[5];
-        md_observe_task(sub, &k, &s, &c, a, mine);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) scratch[sub * 5 + i] = mine[i];
-    }
-    // same wave: the LDS unit executes a wave's ds_write / ds_read in order; the fence keeps the
-    // compiler from moving the combining lanes' reads above the other lanes' writes
-    wave_lds_sync();
-    if (live && sub == 0) md_observe_combine(&k, &s, &c, a, just_reset, (const float (*)[5])scratch);
-    __builtin_amdgcn_wave_barrier();
-}
-
-// ------------------------------------------------------------------------------------------------
-// Traffic trigger (one wave) -- PGTrafficManager.before_step, manager/traffic_manager.py:80-88
-// In two halves: the lean kernel runs the search beside the integration and only the fire in its traffic stage.
-// ------------------------------------------------------------------------------------------------
-// A/B builds: -DMD_TRIGGER_EARLY=0 compiles the lean kernel with both halves in its traffic stage (trigger_env)
-#ifndef MD_TRIGGER_EARLY
-#define MD_TRIGGER_EARLY 1
-#endif
-// The search: the lowest pending trigger_order of the env and the trigger road of its block (0x7fffffff: nothing is pending).
-// Reads only the PENDING / ALIVE bits and trigger_order / trigger_road of slots that do not drive: nothing a step computes.
-constexpr int kNoTrigger = 0x7fffffff;
-__device__ __forceinline__ void trigger_search_wave(const MdState& s, const MdConfig& c, int lane_id, int* min_order_out, int* trig_road_out) {
-    const int base = 0;  // env-local view
-    MD_FINE_STAMP(lane_id == 0, -1);
-    *min_order_out = kNoTrigger;
-    *trig_road_out = -1;
-    int my_min = 0x7fffffff;
-    for (int j = lane_id; j < c.cap; j += 64) {
-        const int f = s.shape[base + j].flags;
-        if ((f & MD_F_PENDING) && (f & MD_F_ALIVE)) {
-            const int o = s.nav[base + j].trigger_order;
-            my_min = o < my_min ? o : my_min;
-        }
-    }
-    const int min_order = wave_min_i(my_min, my_min != 0x7fffffff, 0x7fffffff);  // wavefront min-reduce
-    if (min_order == 0x7fffffff) return;
-    // trigger road of that block: lowest slot carrying min_order
-    int my_slot = 0x7fffffff;
-    for (int j = lane_id; j < c.cap; j += 64) {
-        const int f = s.shape[base + j].flags;
-        if ((f & MD_F_PENDING) && (f & MD_F_ALIVE) && s.nav[base + j].trigger_order == min_order)
-            my_slot = j < my_slot ? j : my_slot;
-    }
-    const int first_slot = wave_min_i(my_slot, my_slot != 0x7fffffff, 0x7fffffff);
-    *min_order_out = min_order;
-    *trig_road_out = s.nav[base + first_slot].trigger_road;
-    MD_FINE_STAMP(lane_id == 0, 14);
-}
-
-// The fire: an agent on the trigger road wakes the block's vehicles (clears their PENDING bits)
-__device__ __forceinline__ void trigger_fire_wave(const MdLane* lanes, const MdState& s, const MdConfig& c, int lane_id, int min_order, int trig_road) {
-    const int base = 0;  // env-local view
-    if (min_order == kNoTrigger) return;
-    bool fire = false;
-    for (int a = lane_id; a < c.agents_per_env; a += 64) {
-        if (!md_drives(s.shape[base + a].flags)) continue;
-        const int al = s.nav[base + a].lane;
-        if (al >= 0 && lanes[al].road == trig_road) fire = true;
-    }
-    if (__ballot(fire) == 0ull) return;
-    for (int j = lane_id; j < c.cap; j += 64) {
-        const int f = s.shape[base + j].flags;
-        if ((f & MD_F_PENDING) && (f & MD_F_ALIVE) && s.nav[base + j].trigger_order == min_order)
-            s.shape[base + j].flags = f & ~MD_F_PENDING;
-    }
-}
-
-__device__ __forceinline__ void trigger_env(const MdLane* lanes, const MdState& s, const MdConfig& c, int lane_id) {
-    int min_order, trig_road;
-    trigger_search_wave(s, c, lane_id, &min_order, &trig_road);
-    trigger_fire_wave(lanes, s, c, lane_id, min_order, trig_road);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Multi-agent lifecycle of one env by the whole workgroup: the block-parallel form of md_lifecycle_env
-// (include/md_entity.h, which the oracle runs serially).  Per-agent state machine: one thread per agent; the
-// search for a safe spawn place -- (place, vehicle) overlap tests, 8 x 40 of them -- spread over all threads with
-// an LDS OR per place; the respawn itself (RNG draws, slot rewrite) on thread 0.  md_lifecycle_env re-scans
-// after a respawn; that second scan can never find a place (every safe place of the first scan is marked used,
-// the unsafe ones are still occupied), so one scan is exact.  scratch: >= 4 ints of LDS.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void lifecycle_block(const MdWorld& w, const MdState& s, const MdConfig& c, int m, int tid, int nthreads,
-                                int* scratch) {
-    const int A = c.agents_per_env;
-    int* cnt_active = scratch;      // agents that keep driving
-    int* cnt_dying = scratch + 1;   // bodies waiting out delay_done
-    int* hit_mask = scratch + 2;    // bit p: spawn place p is occupied
-    int* reserved = scratch + 3;    // parking lot env: bit d: an active agent holds parking space d (md_lifecycle_env)
-    int* new_slot = scratch + 4;    // slot refilled in this step (-1: none) and its row of the spawn-route table: the
-    int* new_ri = scratch + 5;      //   96 words of its route are copied by the whole workgroup, not by the one thread
-    const bool parking = c.ma_kind == MD_MA_PARKING_LOT;
-    if (tid == 0) {
-        s.env_steps[0] += 1;
-        *cnt_active = 0;
-        *cnt_dying = 0;
-        *hit_mask = 0;
-        *reserved = 0;
-        *new_slot = -1;
-    }
-    __syncthreads();
-    for (int a = tid; a < A; a += nthreads) {
-        MdShape* sh = &s.shape[a];
-        MdNav* nav = &s.nav[a];
-        if (!(sh->flags & MD_F_ALIVE)) continue;
-        bool count_down = true;
-        if (!(sh->flags & MD_F_STATIC)) {
-            const uint32_t fl = s.flags[a];
-            if (nav->done || (fl & MD_FL_TRUNCATED)) {
-                if ((fl & MD_FL_ARRIVE_DEST) || c.delay_done <= 0) {
-                    sh->flags &= ~MD_F_ALIVE;
-                    count_down = false;
-                } else {
-                    sh->flags |= MD_F_STATIC;
-                    nav->timer = c.delay_done;
-                    s.dyn[a].speed = 0.0f;
-                }
-            } else {
-                atomicAdd(cnt_active, 1);
-                if (parking && nav->toll_entry > 0) atomicOr(reserved, 1 << (nav->toll_entry - 1));
-                count_down = false;
-            }
-        }
-        if (count_down) {
-            nav->timer -= 1;
-            if (nav->timer <= 0) sh->flags &= ~MD_F_ALIVE;
-            else atomicAdd(cnt_dying, 1);
-        }
-    }
-    __syncthreads();
-    const bool horizon_open = !(c.horizon > 0 && s.env_steps[0] >= c.horizon);
-    const bool may_respawn = c.allow_respawn && horizon_open && w.spawn_off != nullptr && (*cnt_active + *cnt_dying < A);
-    if (may_respawn) {  // block-uniform
-        const int p0 = w.spawn_off[m];
-        const int np_ = min(w.spawn_off[m + 1] - p0, 32);
-        for (int idx = tid; idx < np_ * c.cap; idx += nthreads) {
-            const int p = idx / c.cap, j = idx - p * c.cap;
-            const MdShape o = s.shape[j];
-            if (!md_present(o.flags) || md_kind_of(o.flags) != MD_KIND_VEHICLE) continue;
-            const float* pl = w.spawn_place + 8 * (size_t)(p0 + p);
-            if (md_obb_obb(pl[0], pl[1], pl[2], pl[3], MD_RESPAWN_HALF_LEN, MD_RESPAWN_HALF_WID, o.cx, o.cy, o.c, o.s, o.hl, o.hw))
-                atomicOr(hit_mask, 1 << p);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const uint32_t all = np_ >= 32 ? 0xFFFFFFFFu : ((1u << np_) - 1u);
-            uint32_t safe = ~(uint32_t)(*hit_mask) & all;
-            const int n_in = parking ? np_ - c.n_parking : 0;
-            uint32_t avail = parking ? (((1u << c.n_parking) - 1u) & ~(uint32_t)(*reserved)) : 0u;
-            if (parking && avail == 0u) safe &= ~((1u << n_in) - 1u);   // no free space: the entrances stay shut
-            const int n_safe = __popc(safe);
-            int slot = -1;
-            for (int a = 0; a < A; ++a)
-                if (!(s.shape[a].flags & MD_F_ALIVE)) { slot = a; break; }
-            if (n_safe > 0) {
-                int k = (int)(md_rng_next(s.rng) % (uint32_t)n_safe);   // ascending place order, like the serial `safe[]`
-                while (k-- > 0) safe &= safe - 1;
-                const int p = __ffs((int)safe) - 1;
-                if (slot >= 0) {
-                    const float* pl = w.spawn_place + 8 * (size_t)(p0 + p);
-                    int dest = 0, space = 0;
-                    if (!parking) dest = (int)(md_rng_next(s.rng) % (uint32_t)w.n_dest);
-                    else if (p < n_in) {
-                        dest = md_kth_set_bit(avail, (int)(md_rng_next(s.rng) % (uint32_t)__popc(avail)));
-                        space = dest + 1;
-                    } else dest = c.n_parking + (int)(md_rng_next(s.rng) % (uint32_t)(w.n_dest - c.n_parking));
-                    const size_t ri = ((size_t)(p0 + p) * w.n_dest + dest);
-                    const int32_t* rt = w.spawn_route + ri * 2 * MD_ROUTE_LEN;
-                    MdShape* sh = &s.shape[slot];
-                    sh->cx = pl[0];
-                    sh->cy = pl[1];
-                    sh->c = pl[2];
-                    sh->s = pl[3];
-                    sh->flags = MD_KIND_VEHICLE | MD_F_ALIVE | MD_F_AGENT | MD_F_SPAWNED;
-                    sh->aux = -1;
-                    MdDyn* d = &s.dyn[slot];
-                    d->heading = pl[4];
-                    d->speed = 0.0f;
-                    d->steering = 0.0f;
-                    d->throttle = 0.0f;
-                    d->last_x = pl[0];
-                    d->last_y = pl[1];
-                    d->last_c = pl[2];
-                    d->last_s = pl[3];
-                    MdNav* nav = &s.nav[slot];
-                    nav->lane = w.spawn_lane[p0 + p];
-                    nav->route_len = w.spawn_route_meta[2 * ri];
-                    nav->ck0 = 0;
-                    nav->ck1 = (nav->route_len <= 2) ? 0 : 1;
-                    nav->target_lane = -1;
-                    nav->timer = 0;
-                    nav->steps = 0;
-                    nav->done = 0;
-                    nav->toll_state = nav->toll_entry = nav->toll_exit = 0;
-                    nav->toll_entry = space;
-                    md_agent_policy_init(&s, &c, slot);
-                    if (c.random_agent_model && w.n_vclass > 0) md_draw_vehicle_class(&w, &s, slot);
-                    s.final_lane[slot] = w.spawn_route_meta[2 * ri + 1];
-                    *new_slot = slot;
-                    *new_ri = (int)ri;
-                    nav->road0 = rt[MD_ROUTE_LEN + nav->ck0];
-                    nav->road1 = rt[MD_ROUTE_LEN + nav->ck1];
-                    s.pid[slot].energy = 0.0f;
-                    s.flags[slot] = 0;
-                    s.action[2 * slot] = 0.0f;
-                    s.action[2 * slot + 1] = 0.0f;
-                    s.agent_id[slot] = s.next_agent_id[0];
-                    s.next_agent_id[0] += 1;
-                    *cnt_active += 1;
-                }
-            }
-        }
-        __syncthreads();
-        if (*new_slot >= 0) {   // block-uniform
-            const int slot = *new_slot;
-            const int32_t* rt = w.spawn_route + (size_t)(*new_ri) * 2 * MD_ROUTE_LEN;
-            for (int q = tid; q < 2 * MD_ROUTE_LEN; q += nthreads) {
-                if (q < MD_ROUTE_LEN) s.route_nodes[(size_t)slot * MD_ROUTE_LEN + q] = rt[q];
-                else s.route_roads[(size_t)slot * MD_ROUTE_LEN + (q - MD_ROUTE_LEN)] = rt[q];
-            }
-        }
-    }
-    // episode over: nobody left and nobody can come back
-    if (tid == 0 && c.auto_reset && *cnt_active == 0 && !(c.allow_respawn && horizon_open)) s.need_reset[0] = 1;
-    __syncthreads();
-}
+namespace {
 
 // ------------------------------------------------------------------------------------------------
 // The per-env kernel.  PH selects the phases (a compile-time mask: the single-phase entry points

@@ -1,4 +1,4 @@
-"""Float64 reference of the contact stage (contacts_vehicle in csrc/mdstep.hip, contacts_mover in oracle/md_oracle.c) and the
+"""Float64 reference of the contact stage (contacts_vehicle in csrc/parts/contacts.inc, contacts_mover in oracle/md_oracle.c) and the
 seeded case generators its tests share.  TEST INFRASTRUCTURE, numpy only.
 
 The reference does not restate the separating-axis tests of include/md_geom.h:

@@ -1,5 +1,5 @@
 /* Host build of md_flat_cell_item (include/md_geom.h), the index mapping of the lean step kernel's flat pass over the grid cells
- * under the agent's chassis (csrc/mdstep.hip: contacts_vehicle, kFlat), loaded by tests/test_contacts_flat_host.py through
+ * under the agent's chassis (csrc/parts/contacts.inc: contacts_vehicle, kFlat), loaded by tests/test_contacts_flat_host.py through
  * tests/hostlib.py.  The same text the kernel compiles. */
 #include <stddef.h>
 

@@ -1,4 +1,4 @@
-/* Host build of the agent's observation evaluated AHEAD, as the lean step kernel does it (csrc/mdstep.hip: observe_ahead_wave and the
+/* Host build of the agent's observation evaluated AHEAD, as the lean step kernel does it (csrc/parts/observe.inc: observe_ahead_wave and the
  * hit path of observe_agent_wave1), loaded by tests/test_observe_ahead.py through tests/hostlib.py.  Per case two runs on copies of the
  * same state:
  *   direct  md_observe_ctx from the slot's MdNav, the nine tasks in lock-step, md_observe_combine;
@@ -12,7 +12,7 @@
 
 #define EXPORT __attribute__((visibility("default")))
 
-/* the scratch words of the hand-over: ObsAheadWord of csrc/mdstep.hip */
+/* the scratch words of the hand-over: ObsAheadWord of csrc/parts/observe.inc */
 enum { AH_MARK = 45, AH_LANE = 46, AH_ROAD0 = 47, AH_ROAD1 = 2, AH_CK0 = 3, AH_CK1 = 4,
        AH_VALID = 6, AH_CUR_W = 7, AH_CUR_N = 8, AH_POS_ROAD = 9, AH_FIN_LEN = 12 };
 

@@ -38,3 +38,11 @@ def test_every_part_is_included_exactly_once():
     assert parts and set(parts) <= set(entry.hip_sources())
     included = [hit for _, hit in reachable_includes() if os.path.dirname(hit) == parts_dir]
     assert sorted(included) == parts
+
+
+def test_every_part_names_itself_in_its_first_line():
+    parts = [s for s in entry.hip_sources() if s.endswith(".inc")]
+    assert parts
+    for p in parts:
+        first = open(p).readline()
+        assert first.startswith("// parts/%s -- part of mdstep.hip" % os.path.basename(p)), p

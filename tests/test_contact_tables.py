@@ -1,6 +1,6 @@
 """The static tables the contact stage walks (mapgen/tables.py: quads + grid), CPU only:
   (a) every quad is what md_obb_quad is right for: counter-clockwise, convex, no degenerate edge;
-  (b) the premise of the device's cull (contacts_vehicle, csrc/mdstep.hip: the cells under the chassis AABB + 0.05 m): every quad
+  (b) the premise of the device's cull (contacts_vehicle, csrc/parts/contacts.inc: the cells under the chassis AABB + 0.05 m): every quad
       the chassis touches is listed in a cell of that range -- the range restated in float32 exactly as the kernel computes it;
   (c) ref_contacts on placed agents against the float64 reference of tests/contact_ref.py, per flag bit where decided;
   (d) the dense scenario scene whose cells list more than 64 quads (the second trip of the device's 64-strided cell loop), which

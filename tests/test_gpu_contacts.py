@@ -1,4 +1,4 @@
-"""The device's contact walk (contacts_vehicle, csrc/mdstep.hip) on PLACED states: the grid cull under the chassis AABB, the
+"""The device's contact walk (contacts_vehicle, csrc/parts/contacts.inc) on PLACED states: the grid cull under the chassis AABB, the
 64-strided cell loop, the two 64-wide mover chunks, the nine-ballot OR and the flag merge of the lean step kernels.  After every
 launch the whole state equals the oracle bit for bit, and bits 0x1FF of every agent's flag word equal the float64 reference of
 tests/contact_ref.py wherever that is decided, evaluated on the downloaded shapes.  Each named case asserts from the host tables,

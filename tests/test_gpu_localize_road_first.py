@@ -1,4 +1,4 @@
-"""The road-first localisation of the lean step kernel (csrc/mdstep.hip, localize_road_first): a vehicle is first looked for on
+"""The road-first localisation of the lean step kernel (csrc/parts/localize.inc, localize_road_first): a vehicle is first looked for on
 the lanes of its route's current road, read straight from the lane table around its previous lane, and only then through the
 grid.  Both ways must name the same lane, bit for bit with the oracle's scan over all lanes:
   (a) md_localize_road_first (the stand-alone localisation with the path on) against ref_localize on placed states,

@@ -1,5 +1,5 @@
 """The lean step kernel's locate stage with the agent's contacts as one flat pass over the quads of the up to four grid cells under
-the chassis (csrc/mdstep.hip: contacts_vehicle<true>, include/md_geom.h: md_flat_cell_item) behind the mover loop.  md_step on PLACED
+the chassis (csrc/parts/contacts.inc: contacts_vehicle<true>, include/md_geom.h: md_flat_cell_item) behind the mover loop.  md_step on PLACED
 states of 8 envs on one 3-block map, mover capacity 8 and 24, against the oracle bit for bit (the whole state: flags, obs, reward,
 cost, step_info, and the done words), placed as tests/test_gpu_contacts.py places them.  The cases are named after the grid cells
 under the chassis and what lies in them; each runs with 1, 2, 3 and 5 driving vehicles in its env (two waves of the locate stage

@@ -1,4 +1,4 @@
-"""The lean step kernel with the agent's observation evaluated ahead (csrc/mdstep.hip: observe_ahead_wave beside the localisation, the hit
+"""The lean step kernel with the agent's observation evaluated ahead (csrc/parts/observe.inc: observe_ahead_wave beside the localisation, the hit
 path of observe_agent_wave1) against the oracle, which evaluates it after the localisation like every other kernel: md_step rollouts of
 8 envs x 120 steps with auto_reset and horizon 60, every step's whole state bit for bit.  Traffic densities: none (every env has one driving
 vehicle), 0.1, 0.3, and 0.8, at which most envs have three and more driving vehicles, so that no wave is left without an item.

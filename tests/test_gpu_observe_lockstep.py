@@ -1,4 +1,4 @@
-"""The agent's observation of the lean step kernel with its nine tasks in lock-step (csrc/mdstep.hip: observe_agent_wave1<true>,
+"""The agent's observation of the lean step kernel with its nine tasks in lock-step (csrc/parts/observe.inc: observe_agent_wave1<true>,
 include/md_entity.h: md_observe_lane) against the oracle, which runs the serial tasks (md_observe_task): md_step rollouts with
 resets, horizon truncations, out-of-road terminations, both directions of circular lanes and road boundaries, every step's
 observation row before the cloud, reward, cost, terminated / truncated, step flags and step_info bit for bit."""

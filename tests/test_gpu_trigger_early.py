@@ -1,4 +1,4 @@
-"""The traffic trigger of the lean step kernel in two halves (csrc/mdstep.hip: trigger_search_wave beside the integration,
+"""The traffic trigger of the lean step kernel in two halves (csrc/parts/trigger.inc: trigger_search_wave beside the integration,
 trigger_fire_wave in the traffic stage).  The search reads the waiting slots at the start of the step, the fire the agent's lane
 after localisation; together they must clear exactly the blocks the oracle's trigger clears, bit for bit:
   rollouts: md_step against OracleWorld.step with fires, resets and several pending orders (and with none at all),

@@ -1,4 +1,4 @@
-"""The premise of the road-first localisation (csrc/mdstep.hip, localize_road_first): the grid cell of a point lists EVERY
+"""The premise of the road-first localisation (csrc/parts/localize.inc, localize_road_first): the grid cell of a point lists EVERY
 lane whose float32 box contains the point, so the lanes of one road taken straight from the lane table are the lanes the
 grid walk would have found.  CPU only: the tables of a few small PG maps, the cell computed exactly as the kernel does."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""The agent's observation evaluated ahead, as the lean step kernel does beside the localisation (csrc/mdstep.hip: observe_ahead_wave, the
+"""The agent's observation evaluated ahead, as the lean step kernel does beside the localisation (csrc/parts/observe.inc: observe_ahead_wave, the
 hit path of observe_agent_wave1): on the host (tests/observe_ahead_host.c), md_observe_ctx_of on a COPY of the five navigation words,
 with the MdNav's own words poisoned meanwhile, gives the 45 task words and, through the hand-over words laid out as in wave 0's scratch,
 md_observe_combine_of's outputs bit for bit as md_observe_ctx and md_observe_combine give them.  The cases are the lock-step test's
