@@ -41,6 +41,7 @@
 #include "md_ped.h"
 #include "md_vector_obs.h"
 #include "md_lean_pins.h"
+#include "md_lean_view.h"
 
 namespace {
 
@@ -701,6 +702,7 @@ __global__ __launch_bounds__(kBlock) void line_detector_kernel(MdWorld w, MdStat
 #include "parts/observe.inc"      // observe_*; MD_OBS_LOCKSTEP, MD_OBS_AHEAD
 #include "parts/trigger.inc"      // trigger_*; MD_TRIGGER_EARLY
 #include "parts/lifecycle.inc"    // lifecycle_block (multi-agent envs)
+#include "parts/lean_view.inc"    // lean_args_here, LEAN_ARG, lean_view_*; MD_LEAN_VIEW
 
 namespace {
 
@@ -887,6 +889,20 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     constexpr bool kObsAhead = MD_OBS_AHEAD && kObsLockstep && kWaves > 1;
     // the agent's contacts with the quads in one flat pass over the cells under the chassis (contacts_vehicle): the lean kernel only
     constexpr bool kContactsFlat = MD_CONTACTS_FLAT && PH == PH_ALL && kIdmKeys;
+    // the env's pointers derived where they are used, from the kernel-argument segment (parts/lean_view.inc): the lean kernel only.
+    // It reads NOTHING from its by-value arguments: they are cleared here and refilled, the stage-in's few fields now, the rest of
+    // `w` and `c` behind the stage-in's loads, each cold group of `g` at the head of its stage.
+    constexpr bool kLeanView = MD_LEAN_VIEW && PH == PH_ALL && kIdmKeys && BLK >= 256;
+    LeanStageIn lean_in;
+    if constexpr (kLeanView) {
+        lean_in = lean_stage_in_args(lean_args_entry());
+        w = MdWorld{};
+        g = MdState{};
+        c = MdConfig{};
+        c.n_envs = lean_in.n_envs;
+        c.cap = lean_in.cap;
+        c.agents_per_env = lean_in.agents;
+    }
     // The lean launch: variant<PH_ALL>() guarantees the pins.  Not in the staged-map kernel: folded, its scratch grows from 16 to
     // 80 B per lane (EXPERIMENTS.md, "Lean kernels fold what their launch pins"), so it keeps reading the fields.
     if constexpr (PH == PH_ALL && !RESPAWN && !MULTI && !STAGE_MAP) lean_pins_fold(g, c);
@@ -931,19 +947,20 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     // one of them whenever MdState.detected is set, so the lean trigger-mode kernel pays nothing for it
     const bool track_det = (PH == PH_ALL) && (RESPAWN || MULTI) && g.detected != nullptr;
 
-    const MdState gv = md_env_view(&g, &c, e);  // this env's slices of the global arrays
+    MdState gv = md_env_view(&g, &c, e);  // this env's slices of the global arrays (kLeanView: all null here)
+    const MdLane* lanes;
+    const MdRoad* roads;
+    if constexpr (kLeanView) lean_view_stage_in(gv, lean_in, e, cap, c.agents_per_env);
     // The reset flag is loaded first but nothing below waits for it: the live state is staged
     // unconditionally (one round trip) and only a resetting env re-stages from the snapshot.
     const int reset_flag = (PH & PH_RESET) ? gv.need_reset[0] : 0;
 
     MD_STAMP_AT(0);
     const bool kFusedAct = (PH == PH_ALL) && gv.agent_action != nullptr;  // md_step only: agents' actions from the caller's buffer
-    const MdLane* lanes;
-    const MdRoad* roads;
     if (STAGE_MAP) {
         lanes = l_lanes;
         roads = l_roads;
-    } else {
+    } else if constexpr (!kLeanView) {
         lanes = w.lanes + w.lane_off[w.env_map[e]];
         roads = w.roads + w.road_off[w.env_map[e]];
     }
@@ -978,21 +995,41 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
             r_fl = gv.flags[tid];
             r_fin = gv.final_lane ? gv.final_lane[tid] : 0;
         }
+        if constexpr (kLeanView) {
+            // behind the stage-in's loads, while they are in flight: what the stages below read of `w` and `c` (the three fields
+            // above stay the values the image was laid out with), the env's map tables and the routes, which the locate stage may follow at once
+            lean_view_map(&lanes, &roads, lean_args_entry(), e);   // before the asm below, or its loads could not be scalar ones
+            const LeanArgs kb = lean_args_here();
+            const int n_envs = c.n_envs, agents = c.agents_per_env;
+            lean_arg_copy(w, kb, offsetof(MdStepArgs, w));
+            lean_arg_copy(c, kb, offsetof(MdStepArgs, c));
+            c.n_envs = n_envs;
+            c.cap = cap;
+            c.agents_per_env = agents;
+            lean_pins_fold(g, c);
+            c_scan = c;
+            if constexpr (NARROW) lean_size_pins_fold(c, c_scan);
+            lean_view_routes(gv, kb, e, cap);
+        }
         if (STAGE_MAP) {
             const int m = w.env_map[e];
             const int lo = w.lane_off[m], ro = w.road_off[m];
             copy16(l_lanes, w.lanes + lo, (w.lane_off[m + 1] - lo) * (int)sizeof(MdLane), tid, kBlock);
             copy16(l_roads, w.roads + ro, (w.road_off[m + 1] - ro) * (int)sizeof(MdRoad), tid, kBlock);
         }
-        if (p32) {
+        // kLeanView: the stores' predicates are made again from an opaque copy of tid (a v_cmp each), not carried from the loads
+        // in SGPR pairs that the argument copy above pushes into VGPR lanes ahead of the first load
+        int tid_st = tid;
+        if constexpr (kLeanView) asm("" : "+v"(tid_st));
+        if (tid_st < n32) {
             reinterpret_cast<uint4*>(l_shape)[tid] = r_shape;
             reinterpret_cast<uint4*>(l_dyn)[tid] = r_dyn;
             reinterpret_cast<uint4*>(l_pid)[tid] = r_pid;
             reinterpret_cast<uint4*>(l_param)[tid] = r_param;
         }
-        if (tid < n64) reinterpret_cast<uint4*>(l_nav)[tid] = r_nav0;
+        if (tid_st < n64) reinterpret_cast<uint4*>(l_nav)[tid] = r_nav0;
         for (int i = tid + kBlock; i < n64; i += kBlock) reinterpret_cast<uint4*>(l_nav)[i] = g_nav[i];
-        if (pc) {
+        if (tid_st < cap) {
             reinterpret_cast<float2*>(l_action)[tid] = r_act;
             l_flags[tid] = r_fl;
             l_final[tid] = r_fin;
@@ -1025,6 +1062,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     const int just_reset = do_reset ? 1 : 0;
     if (do_reset && !kLidarOnly) {
         __syncthreads();
+        if constexpr (kLeanView) lean_view_reset(gv, e, cap);
         copy16(l_shape, gv.shape0, cap * (int)sizeof(MdShape), tid, kBlock);
         copy16(l_dyn, gv.dyn0, cap * (int)sizeof(MdDyn), tid, kBlock);
         copy16(l_nav, gv.nav0, cap * (int)sizeof(MdNav), tid, kBlock);
@@ -1222,7 +1260,22 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         // (reads poses / lanes / speeds, writes the traffic slots' action, IDM timer / target lane and PID state:
         // disjoint from what observe writes -- obs, reward, the agent's flags / steps / energy).
         if (wave == 0) {
-            if (!(MD_ENV_SKIP & 16))
+            if constexpr (kLeanView) {
+                // wave 0 alone reads the outputs and the reward / cost / done scheme: both from the argument segment, here
+                const LeanArgs ko = lean_args_here();
+                MdConfig co;
+                lean_arg_copy(co, ko, offsetof(MdStepArgs, c));
+                co.n_envs = c.n_envs;
+                co.cap = cap;
+                co.agents_per_env = c.agents_per_env;
+                MdConfig co_scan;
+                lean_pins_fold(g, co);
+                if constexpr (NARROW) lean_size_pins_fold(co, co_scan);
+                MdState so = s;
+                lean_view_observe(so, ko, e, co.agents_per_env, co.obs_dim);
+                if (!(MD_ENV_SKIP & 16))
+                    for (int a = 0; a < co.agents_per_env; ++a) observe_agent_wave1<kObsLockstep, kObsAhead>(lanes, roads, so, co, a, just_reset, lane, l_scratch);
+            } else if (!(MD_ENV_SKIP & 16))
                 for (int a = 0; a < c.agents_per_env; ++a) observe_agent_wave1<kObsLockstep, kObsAhead>(lanes, roads, s, c, a, just_reset, lane, l_scratch);
         } else if (!(MD_ENV_SKIP & 2)) {
             // the driving traffic vehicles by RANK, not by slot: dealt by slot (j = A + wave - 1, + kWaves - 1, ...) two of an env's
@@ -1258,6 +1311,12 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         // lidar only reads shapes; observe writes obs[0:19] / flags / nav / pid -- no barrier needed in between
     }
     if ((PH & PH_LIDAR) && !(PH == PH_ALL && (MD_ENV_SKIP & 1))) {
+        if constexpr (kLeanView) {   // where the cloud goes: read here
+            const LeanArgs kl = lean_args_here();
+            lidar_out = LEAN_ARG(kl, lidar_out);
+            lidar_stride = LEAN_ARG(kl, lidar_stride);
+            lidar_offset = LEAN_ARG(kl, lidar_offset);
+        }
         if (c.n_beams > 0) phase_lidar(w, s, c_scan, e, tid, kWaves, lidar_out, lidar_stride, lidar_offset, track_det ? l_det : nullptr, PH == PH_ALL ? &l_tk[2] : nullptr);
     }
 
@@ -1267,6 +1326,7 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
         __syncthreads();
         MD_STAMP_AT(10);
         constexpr bool respawns = (PH & PH_TRAFFIC) && RESPAWN;  // traffic respawn rewrites a whole slot
+        if constexpr (kLeanView) lean_view_write_back(gv, e, cap);   // its targets: derived again here, not carried from the entry
         if (kFused && !MULTI && !do_reset) {
             // Single-agent fused step: only slots that drive now (agents, traffic incl. the just triggered /
             // respawned) or were removed this step can differ from what HBM already holds -- props, waiting and
