@@ -42,6 +42,7 @@
 #include "md_vector_obs.h"
 #include "md_lean_pins.h"
 #include "md_lean_view.h"
+#include "md_write_back_own.h"
 
 namespace {
 
@@ -83,6 +84,14 @@ __device__ const int* g_env_order = nullptr;
                           ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);        \
             }                                                                                  \
             if ((i) == 11) sb_[13] = __builtin_amdgcn_s_memrealtime();                         \
+        }                                                                                      \
+    } while (0)
+// a wave's end where the waves of an env end apart (the lean kernels' own write-back): slot 11 / 13 keep the LATEST wave's
+#define MD_STAMP_WAVE_END(cond)                                                                \
+    do {                                                                                       \
+        if ((cond) && g_stamp_buf) {                                                           \
+            atomicMax(&g_stamp_buf[(size_t)blockIdx.x * 32 + 11], (unsigned long long)__builtin_readcyclecounter()); \
+            atomicMax(&g_stamp_buf[(size_t)blockIdx.x * 32 + 13], (unsigned long long)__builtin_amdgcn_s_memrealtime()); \
         }                                                                                      \
     } while (0)
 #define MD_FINE_STAMP(cond, i)                                                                 \
@@ -127,6 +136,7 @@ __device__ unsigned long long* g_contacts_buf = nullptr;
 #define MD_CONTACTS_STAMP(cond, i) do { } while (0)
 #define MD_CONTACTS_COUNT(cond, cells, items) do { } while (0)
 #define MD_STAMP_AT(i) do { } while (0)
+#define MD_STAMP_WAVE_END(cond) do { } while (0)
 #define MD_FINE_STAMP(cond, i) do { } while (0)
 #define MD_LOC_COUNT(cond, hit) do { } while (0)
 #define MD_AHEAD_STAMP(cond, i) do { } while (0)
@@ -893,6 +903,9 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     // It reads NOTHING from its by-value arguments: they are cleared here and refilled, the stage-in's few fields now, the rest of
     // `w` and `c` behind the stage-in's loads, each cold group of `g` at the head of its stage.
     constexpr bool kLeanView = MD_LEAN_VIEW && PH == PH_ALL && kIdmKeys && BLK >= 256;
+    // each wave stores the slots it finished and leaves; no last barrier but in a reset step (parts/lean_view.inc, include/
+    // md_write_back_own.h): the same two kernels.  Not in a knockout build, where a stage that owns slots is compiled out.
+    constexpr bool kWriteBackOwn = MD_WRITE_BACK_OWN && kLeanView && MD_ENV_SKIP == 0;
     LeanStageIn lean_in;
     if constexpr (kLeanView) {
         lean_in = lean_stage_in_args(lean_args_entry());
@@ -1274,7 +1287,15 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
                 MdState so = s;
                 lean_view_observe(so, ko, e, co.agents_per_env, co.obs_dim);
                 if (!(MD_ENV_SKIP & 16))
-                    for (int a = 0; a < co.agents_per_env; ++a) observe_agent_wave1<kObsLockstep, kObsAhead>(lanes, roads, so, co, a, just_reset, lane, l_scratch);
+                    for (int a = 0; a < co.agents_per_env; ++a) {
+                        observe_agent_wave1<kObsLockstep, kObsAhead>(lanes, roads, so, co, a, just_reset, lane, l_scratch);
+                        if (kWriteBackOwn && !do_reset) {   // the agent's slot is final: nothing but this observe writes it behind the traffic stage
+                            wave_lds_sync();
+                            const int fa = l_shape[a].flags;
+                            if (md_wb_owner(fa, fa & MD_F_AGENT, l_cfl[a] == kRemovedMark) == MD_WB_WAVE0)
+                                lean_store_slot(l_shape, l_dyn, l_pid, l_nav, l_action, l_flags, e, cap, a, lane);
+                        }
+                    }
             } else if (!(MD_ENV_SKIP & 16))
                 for (int a = 0; a < c.agents_per_env; ++a) observe_agent_wave1<kObsLockstep, kObsAhead>(lanes, roads, s, c, a, just_reset, lane, l_scratch);
         } else if (!(MD_ENV_SKIP & 2)) {
@@ -1285,10 +1306,27 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
                 const int jl = j0 + lane;
                 const int fl = (jl < cap) ? s.shape[jl].flags : 0;
                 unsigned long long mk = __ballot(jl < cap && md_drives(fl) && !(fl & MD_F_AGENT));
+                if (kWriteBackOwn && !do_reset && wave == kWaves - 1) {
+                    // the rest pass: slots that no wave writes behind the traffic stage's barrier (removed in this step, walkers).
+                    // An agent's slot beyond the agents that wave 0 observes is nobody's to write either: taken here too.
+                    const int own = jl < cap ? md_wb_owner(fl, fl & MD_F_AGENT, l_cfl[jl] == kRemovedMark) : MD_WB_NOBODY;
+                    unsigned long long rest = __ballot(own == MD_WB_REST || (own == MD_WB_WAVE0 && jl >= c.agents_per_env));
+                    while (rest) {   // usually none
+                        const int j = j0 + __ffsll((long long)rest) - 1;
+                        rest &= rest - 1;
+                        lean_store_slot(l_shape, l_dyn, l_pid, l_nav, l_action, l_flags, e, cap, j, lane);
+                    }
+                }
                 while (mk) {
                     const int j = j0 + __ffsll((long long)mk) - 1;
                     mk &= mk - 1;
-                    if (rank % (kWaves - 1) == wave - 1) idm_vehicle_wave<kIdmKeys>(w, lanes, roads, s, c_scan, w.env_map[e], j, lane, reinterpret_cast<int*>(l_scratch));
+                    if (rank % (kWaves - 1) == wave - 1) {
+                        idm_vehicle_wave<kIdmKeys>(w, lanes, roads, s, c_scan, w.env_map[e], j, lane, reinterpret_cast<int*>(l_scratch));
+                        if (kWriteBackOwn && !do_reset) {   // the vehicle's slot is final: other vehicles' IDM only read it
+                            wave_lds_sync();
+                            lean_store_slot(l_shape, l_dyn, l_pid, l_nav, l_action, l_flags, e, cap, j, lane);
+                        }
+                    }
                     ++rank;
                 }
             }
@@ -1323,6 +1361,13 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
     MD_STAMP_AT(9);
     // ---- write the modified arrays back (coalesced 16-byte stores) ----
     if (!kLidarOnly) {
+        if constexpr (kWriteBackOwn) {
+            if (!do_reset) {   // every slot is stored by the wave that finished it (see the observe || IDM stage): the waves end apart
+                MD_STAMP_AT(10);
+                MD_STAMP_WAVE_END(lane == 0);
+                return;
+            }
+        }
         __syncthreads();
         MD_STAMP_AT(10);
         constexpr bool respawns = (PH & PH_TRAFFIC) && RESPAWN;  // traffic respawn rewrites a whole slot

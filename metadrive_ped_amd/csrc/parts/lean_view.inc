@@ -1,6 +1,7 @@
 // parts/lean_view.inc -- part of mdstep.hip, included there and not compiled on its own.
-// Provides: MD_LEAN_VIEW, LeanArgs, lean_args_entry, lean_args_here, LEAN_ARG, lean_arg_copy and the lean_view_* groups.
-// Relies on: include/md_lean_view.h (MdStepArgs, the MD_LEAN_ARGS_* lists).
+// Provides: MD_LEAN_VIEW, LeanArgs, lean_args_entry, lean_args_here, LEAN_ARG, lean_arg_copy and the lean_view_* groups;
+// MD_WRITE_BACK_OWN and lean_store_slot.
+// Relies on: include/md_lean_view.h (MdStepArgs, the MD_LEAN_ARGS_* lists); mdstep.hip (st_stream).
 
 namespace {
 
@@ -113,6 +114,37 @@ __device__ __forceinline__ void lean_view_write_back(MdState& v, int e, int cap)
     v.action = LEAN_ARG(p, g.action) + 2 * b;
     v.flags = LEAN_ARG(p, g.flags) + b;
     v.need_reset = LEAN_ARG(p, g.need_reset) + e;
+}
+// ------------------------------------------------------------------------------------------------
+// Each wave writes back its own slots (the two lean non-staged workgroup kernels that use this part; include/md_write_back_own.h
+// says who owns a slot).  A step that does not reset ends without the last barrier and the dirty-slot loops behind it: wave 0
+// stores an agent's slot behind its observe, an IDM wave a traffic vehicle's behind its decision, the last wave the removed slots
+// and the walkers behind the traffic stage's barrier.  A reset step keeps the barrier and the full write-back.
+// ------------------------------------------------------------------------------------------------
+// A/B builds: -DMD_WRITE_BACK_OWN=0 compiles the write-back behind the last barrier as before
+#ifndef MD_WRITE_BACK_OWN
+#define MD_WRITE_BACK_OWN 1
+#endif
+// One slot of the env, from the LDS image to HBM, by the whole wave (`j` wave-uniform; call it in wave-uniform code only): the
+// slot's units of shape, dyn, pid (two each) and nav (four), its action and flag word, with the stores of the dirty-slot
+// write-back.  The targets are derived here from the argument segment, like lean_view_write_back's; the caller orders the wave's
+// LDS writes before this (wave_lds_sync).
+static_assert(sizeof(MdShape) == 32 && sizeof(MdDyn) == 32 && sizeof(MdPid) == 32 && sizeof(MdNav) == 64, "lean_store_slot: units per record");
+__device__ __forceinline__ void lean_store_slot(const MdShape* l_shape, const MdDyn* l_dyn, const MdPid* l_pid, const MdNav* l_nav,
+                                                const float* l_action, const uint32_t* l_flags, int e, int cap, int j, int lane_id) {
+    const LeanArgs p = lean_args_here();
+    e = lean_here(e);
+    const size_t n = (size_t)e * (size_t)cap + (size_t)j;
+    if (lane_id < 2) {
+        st_stream(reinterpret_cast<uint4*>(LEAN_ARG(p, g.shape) + n) + lane_id, reinterpret_cast<const uint4*>(l_shape + j)[lane_id]);
+        st_stream(reinterpret_cast<uint4*>(LEAN_ARG(p, g.dyn) + n) + lane_id, reinterpret_cast<const uint4*>(l_dyn + j)[lane_id]);
+        st_stream(reinterpret_cast<uint4*>(LEAN_ARG(p, g.pid) + n) + lane_id, reinterpret_cast<const uint4*>(l_pid + j)[lane_id]);
+    }
+    if (lane_id < 4) st_stream(reinterpret_cast<uint4*>(LEAN_ARG(p, g.nav) + n) + lane_id, reinterpret_cast<const uint4*>(l_nav + j)[lane_id]);
+    if (lane_id == 0) {
+        reinterpret_cast<float2*>(LEAN_ARG(p, g.action))[n] = reinterpret_cast<const float2*>(l_action)[j];
+        LEAN_ARG(p, g.flags)[n] = l_flags[j];
+    }
 }
 // Reset: the snapshots
 __device__ __forceinline__ void lean_view_reset(MdState& v, int e, int cap) {

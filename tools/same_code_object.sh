@@ -23,7 +23,7 @@ REV=${1:-HEAD}
 [ $# -gt 0 ] && shift
 if [ $# -eq 0 ]; then
     set -- plain -DMD_STAMP -DMD_ENV_SKIP=1 -DMD_SC_SKIP=1 -DMD_TD_SKIP=1 -DMD_ENV_BLOCK=128 -DMD_WAVE_ENVS=1 \
-        -DMD_LOC_ROAD_FIRST=0 -DMD_OBS_LOCKSTEP=0 -DMD_OBS_AHEAD=0 -DMD_CONTACTS_FLAT=0 -DMD_TRIGGER_EARLY=0 -DMD_NT_STAGE=0 -DMD_LEAN_VIEW=0
+        -DMD_LOC_ROAD_FIRST=0 -DMD_OBS_LOCKSTEP=0 -DMD_OBS_AHEAD=0 -DMD_CONTACTS_FLAT=0 -DMD_TRIGGER_EARLY=0 -DMD_NT_STAGE=0 -DMD_LEAN_VIEW=0 -DMD_WRITE_BACK_OWN=0
 fi
 SETS=("$@")
 

@@ -1,6 +1,14 @@
 """In-kernel phase stamps of the fused step kernel (diagnostic build, -DMD_STAMP).  Builds a separate
 library, runs the bench workload, prints per-phase cycle shares (mean / p50 / max over envs).  Read
-SHARES from it, never the run time of this build."""
+SHARES from it, never the run time of this build.
+
+Stamps 10 and 11 of the two lean non-staged workgroup kernels (each wave writes back its own slots, MD_WRITE_BACK_OWN): in a step
+that does not reset, the waves of an env no longer meet at a last barrier and END APART; a wave's stores stand inside its observe
+|| IDM stage, behind the slot's last write.  Stamp 10 is then wave 0's end (thread 0, behind its lidar tickets: nothing is waited
+for, so 9 -> 10 reads ~0), and stamp 11 (with the real-time word 13) is the LATEST wave's end, kept by every wave's lane 0 with an
+atomic max: the env's end.  10 -> 11 is how long the env outlives wave 0 (the IDM waves' decisions and stores), no longer a
+write-back, and the whole chain 0 -> 11 compares with other builds as before.  A reset step, a -DMD_WRITE_BACK_OWN=0 build and
+every other kernel stamp the barrier and the write-back as they did."""
 import ctypes as C
 import os
 import sys
@@ -12,7 +20,7 @@ sys.path.insert(0, ROOT)
 # the contacts (multi-agent order); where a stamp was not written its phase reads 0 and the next one gets the interval
 PHASES = ["stage-in", "trigger (idm-first variants)", "idm before integrate", "integrate", "localize (own stage)",
           "locate: localize + contacts", "traffic + next trigger", "observe || idm for the next step", "lidar",
-          "wait for the idm waves", "write-back"]
+          "wait for the idm waves", "write-back (own: the env after wave 0's end)"]
 
 
 WAVE_PHASES = ["stage-in", "trigger + idm (idm-first variants)", "-", "integrate", "-", "locate: localize + contacts",
