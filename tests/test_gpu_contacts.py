@@ -247,6 +247,10 @@ class Rig:
                     d["heading"], d["speed"] = math.atan2(float(rec["s"]), float(rec["c"])), 0.0
                     d["last_x"], d["last_y"], d["last_c"], d["last_s"] = rec["cx"], rec["cy"], rec["c"], rec["s"]
                     st["dyn"][e * self.cap + slot] = d
+            for k, rows in getattr(case, "rows", {}).items():      # whole records of other state arrays (tests/idm_ref.py: dyn, nav, pid)
+                assert k in keys
+                for slot, rec in rows:
+                    st[k][e * self.cap + slot] = rec
         self.eng.upload_state({k: st[k] for k in keys})
 
     def check(self, per_env, where, agent_slots=(0, )):
