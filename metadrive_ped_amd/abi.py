@@ -176,6 +176,18 @@ def make_md_ped(pedestrian_config):
     return p
 
 
+class MdContactResponse(C.Structure):
+    """include/md_contact_response.h: the two lengths of the contact response rule (config contact_response_config)"""
+    _fields_ = [("struct_size", C.c_int32), ("skin", C.c_float), ("max_push", C.c_float), ("reserved", C.c_int32)]
+
+
+def make_md_contact_response(contact_response_config):
+    cr = MdContactResponse()
+    cr.struct_size = C.sizeof(MdContactResponse)
+    cr.skin, cr.max_push = float(contact_response_config["skin"]), float(contact_response_config["max_push"])
+    return cr
+
+
 # include/md_vector_obs.h: the ceilings MD_VO_MAX_*, and md_vector_obs's argument block
 MD_VO_MAX_AGENTS, MD_VO_MAX_HISTORY, MD_VO_MAX_ROUTE_POINTS, MD_VO_MAX_LANES, MD_VO_MAX_LANE_POINTS = 16, 8, 32, 16, 16
 VECTOR_OBS_OUTPUTS = ("agents", "agents_mask", "agents_meta", "ego", "ego_mask", "route", "route_mask", "lanes", "lanes_meta", "lanes_mask")
@@ -325,6 +337,8 @@ RENDER_ENTRY_POINTS = {"md_render": (_i, [_W, _S, _K, C.POINTER(MdRender), P])}
 BRANCH_ENTRY_POINTS = {"md_branch": (_i, [_S, _S, _K, C.POINTER(MdBranch), P])}
 # include/md_ped.h: (s, c, p, stream)
 PED_ENTRY_POINTS = {"md_ped": (_i, [_S, _K, C.POINTER(MdPed), P])}
+# include/md_contact_response.h: (s, c, cr, stream)
+CONTACT_RESPONSE_ENTRY_POINTS = {"md_contact_response": (_i, [_S, _K, C.POINTER(MdContactResponse), P])}
 # include/md_vector_obs.h: (w, s, c, vo, stream)
 VECTOR_OBS_ENTRY_POINTS = {"md_vector_obs": (_i, [_W, _S, _K, C.POINTER(MdVectorObs), P])}
 # declared in no header: the hooks of diagnostic (-DMD_STAMP) builds, and md_localize through the lean step's road-first path

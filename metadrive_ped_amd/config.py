@@ -151,6 +151,13 @@ BATCH_DEFAULT_CONFIG = dict(
         kerb_offset=1.0,        # m: the end points lie this far outside the outermost lanes' edges
         min_road_length=20.0,   # m: shorter roads hold no crossing
         spawn_clearance=15.0),  # m: no crossing closer than this to the agent's spawn position
+    # contact response (include/md_contact_response.h; no key of the reference's, the numbers are a design choice): True = a driving
+    # vehicle that overlaps another body is pushed out of it and loses the speed that closes on it, one md_contact_response launch
+    # before every md_step (and before md_ped); False = no launch: vehicles pass through what they hit, as before
+    contact_response=False,
+    contact_response_config=dict(
+        skin=0.01,              # m: the gap a resolved pair is left with
+        max_push=0.5),          # m: the longest displacement of a vehicle in one step
     # the vector scene observation (include/md_vector_obs.h; no key of the reference's, the numbers are a design choice): None = off,
     # no launch and no array; a dict (an empty one too) is laid over VECTOR_OBS_DEFAULT_CONFIG and env.vector_obs() returns the blocks
     vector_obs=None,
@@ -439,6 +446,12 @@ def make_config(user=None, top_down=False):
         if pc["min_road_length"] < 10:
             raise ValueError("pedestrian_config['min_road_length']={!r}: at least 10 m (a crossing keeps 5 m from both road ends)".format(
                 pc["min_road_length"]))
+    if not isinstance(cfg["contact_response"], bool):
+        raise ValueError("contact_response={!r}: True or False".format(cfg["contact_response"]))
+    rc = cfg["contact_response_config"]
+    for k, ok, what in (("skin", lambda v: v >= 0, "must not be negative"), ("max_push", lambda v: v > 0, "a positive number")):
+        if isinstance(rc[k], bool) or not isinstance(rc[k], (int, float)) or not ok(rc[k]):
+            raise ValueError("contact_response_config['{}']={!r}: {}".format(k, rc[k], what))
     if cfg["vector_obs"] is not None:
         cfg["vector_obs"] = check_vector_obs(cfg["vector_obs"])
     if cfg["step_kernel"] not in ("auto", "wg", "wave"):

@@ -39,6 +39,7 @@
 #include "md_render.h"
 #include "md_branch.h"
 #include "md_ped.h"
+#include "md_contact_response.h"
 #include "md_vector_obs.h"
 #include "md_lean_pins.h"
 #include "md_lean_view.h"
@@ -2752,6 +2753,7 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
 #include "parts/draws.inc"        // lidar_detect_kernel, swap_draw_kernel, curriculum_kernel; md_swap_draw, md_curriculum
 #include "parts/branch.inc"       // branch_kernel; md_branch (env snapshots)
 #include "parts/ped.inc"          // ped_kernel; md_ped (crossing pedestrians)
+#include "parts/contact_response.inc" // contact_response_kernel; md_contact_response
 #include "parts/vector_obs.inc"   // vector_obs_kernel; md_vector_obs
 #include "parts/others.inc"       // others_kernel: the observation's "others" block, launched by md_step
 #include "parts/expert.inc"       // expert_kernel, expert_sense_kernel, ai_protect_kernel; md_expert, md_ai_protect, md_expert_sense

@@ -63,7 +63,8 @@ enum When : unsigned {
     SCENARIO = 64, ROUTE = 128, OTHERS = 256,            // md_step, each after the config checks of its branch
 };
 constexpr int kLidarEntry = 1 << 9, kDetectorEntry = 1 << 10, kExpertEntry = 1 << 11, kPgWalkEntry = 1 << 12, kProtectEntry = 1 << 13,
-              kSenseEntry = 1 << 14, kTopDownEntry = 1 << 15, kRenderEntry = 1 << 16, kPedEntry = 1 << 17, kVectorObsEntry = 1 << 18;
+              kSenseEntry = 1 << 14, kTopDownEntry = 1 << 15, kRenderEntry = 1 << 16, kPedEntry = 1 << 17, kVectorObsEntry = 1 << 18,
+              kContactResponseEntry = 1 << 19;
 constexpr int kMapPhases = PH_LOCALIZE | PH_CONTACTS | PH_OBSERVE | PH_IDM | PH_LIFECYCLE;
 constexpr int kTrafficPhases = PH_INTEGRATE | PH_TRAFFIC;
 
@@ -110,6 +111,7 @@ const Need kNeeds[] = {
     {kVectorObsEntry, ALWAYS, {FS(shape), FS(dyn), FS(nav), FS(route_roads), FS(final_lane), FW(env_map), FW(lane_off), FW(lanes),
                                FW(road_off), FW(roads)}},
     {kVectorObsEntry, MULTI, {FS(env_steps)}},
+    {kContactResponseEntry, ALWAYS, {FS(shape), FS(dyn), FS(need_reset)}},
 };
 #undef FW
 #undef FS

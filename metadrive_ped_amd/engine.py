@@ -581,6 +581,8 @@ class BatchedEngine:
         self.nav_i = sd["nav"].view(torch.int32).view(self.E, self.cap, 16)
         # crossing pedestrians (include/md_ped.h): md_ped's argument block; None = no launch
         self._ped = abi.make_md_ped(self.cfg["pedestrian_config"]) if self.cfg.get("num_pedestrians") else None
+        # contact response (include/md_contact_response.h): md_contact_response's argument block; None = no launch
+        self._cr = abi.make_md_contact_response(self.cfg["contact_response_config"]) if self.cfg.get("contact_response") else None
         self.agent_id = sd["agent_id"].view(torch.int32).view(self.E, self.cap) if "agent_id" in sd else None
         self._topdown_setup()
         self._vector_obs_setup()
@@ -728,7 +730,9 @@ class BatchedEngine:
             self._step_raw()
 
     def _step_raw(self):
-        if self._ped is not None:        # the pedestrians' policy on the state the previous step left, then the world steps
+        if self._cr is not None:         # vehicles out of what the previous step drove them into; the pedestrians judge the corrected ones
+            self._check(self.lib.md_contact_response(C.byref(self.s), C.byref(self.k), C.byref(self._cr), self._stream()), "md_contact_response")
+        if self._ped is not None:       # the pedestrians' policy on the state the previous step left, then the world steps
             self._check(self.lib.md_ped(C.byref(self.s), C.byref(self.k), C.byref(self._ped), self._stream()), "md_ped")
         self._launch("md_step")
         L = self.host.layout

@@ -99,6 +99,9 @@ def make_scenario_config(user=None):
     base.setdefault("traffic_density", 0.0)
     if base.get("num_pedestrians"):
         raise NotImplementedError("num_pedestrians > 0 in BatchedScenarioEnv is not built: its pedestrians come from the scenario data")
+    if base.get("contact_response"):
+        raise NotImplementedError("contact_response=True in BatchedScenarioEnv is not built: a scenario's replayed and trajectory-bound "
+                                  "vehicles take their poses from data")
     if base.get("vector_obs") is not None:
         raise NotImplementedError("vector_obs in BatchedScenarioEnv is not built: a scenario has no lane table and its routes are "
                                   "polylines (single-agent PG envs and the multi-agent envs only)")
