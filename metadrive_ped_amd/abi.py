@@ -237,6 +237,54 @@ def make_md_vector_obs(vo_cfg, tensors):
     return v
 
 
+# include/md_scenario_vector_obs.h: the ceilings MD_SVO_MAX_*, and md_scenario_vector_obs's argument block
+MD_SVO_MAX_MAP_PIECES, MD_SVO_MAX_PIECE_POINTS, MD_SVO_MAX_PIECES = 64, 16, 4096
+SCENARIO_VECTOR_OBS_OUTPUTS = ("agents", "agents_mask", "agents_meta", "ego", "ego_mask", "route", "route_mask", "map", "map_mask", "map_meta")
+SCENARIO_VECTOR_OBS_MAP_OUTPUTS = ("map", "map_mask", "map_meta")
+SCENARIO_VECTOR_OBS_TABLES = ("map_off", "map_xy", "map_info", "map_ball")
+
+
+class MdScenarioVectorObs(C.Structure):
+    """include/md_scenario_vector_obs.h: the map block's counts and radius, md_vector_obs.h's struct (num_lanes = 0) for everything
+    the two observations share, the map outputs and the engine-owned per-scene piece table"""
+    _fields_ = [("struct_size", C.c_int32), ("num_pieces", C.c_int32), ("piece_points", C.c_int32), ("max_pieces", C.c_int32),
+                ("map_radius", C.c_float), ("reserved", C.c_int32), ("vo", MdVectorObs)] + \
+        [(k, P) for k in SCENARIO_VECTOR_OBS_MAP_OUTPUTS + SCENARIO_VECTOR_OBS_TABLES]
+
+
+def scenario_vector_obs_blocks(vo_cfg, cap):
+    """-> (outputs, output row bytes, history, history row bytes), like vector_obs_blocks: name -> (byte offset in an env's row, shape
+    after the env axis, numpy dtype).  One observer per env, so the shapes have no agent axis."""
+    K, T, M, Pn, S = (int(vo_cfg[k]) for k in ("num_agents", "history", "route_points", "num_pieces", "piece_points"))
+    u1 = np.uint8
+    outs = [("agents", (K, T, 4), f4), ("agents_mask", (K, T), u1), ("agents_meta", (K, 4), f4), ("ego", (T, 4), f4), ("ego_mask", (T, ), u1),
+            ("route", (M, 4), f4), ("route_mask", (M, ), u1), ("map", (Pn, S, 2), f4), ("map_mask", (Pn, S), u1), ("map_meta", (Pn, 4), f4)]
+    hist = [("ring_pose", (T, cap, 4), f4), ("ring_flags", (T, cap), i4), ("cursor", (4, ), i4)]
+    tables = []
+    for blocks in (outs, hist):
+        table, at = {}, 0
+        for name, shape, dt in blocks:
+            table[name] = (at, shape, np.dtype(dt))
+            at = (at + int(np.prod(shape)) * np.dtype(dt).itemsize + 15) // 16 * 16
+        tables += [table, at]
+    return tuple(tables)
+
+
+def make_md_scenario_vector_obs(vo_cfg, tensors):
+    """MdScenarioVectorObs of the finished config["scenario_vector_obs"]; `tensors`: out_stride, hist_stride, max_pieces and name ->
+    address of env 0's block / of the table (None / missing: NULL)"""
+    v = MdScenarioVectorObs()
+    v.struct_size = C.sizeof(MdScenarioVectorObs)
+    v.num_pieces, v.piece_points = int(vo_cfg["num_pieces"]), int(vo_cfg["piece_points"])
+    v.max_pieces, v.map_radius = int(tensors.get("max_pieces", 0)), float(vo_cfg["map_radius"])
+    shared = dict(vo_cfg, num_lanes=0, lane_points=2)
+    v.vo = make_md_vector_obs(shared, {k: tensors.get(k) for k in ("out_stride", "hist_stride") + VECTOR_OBS_OUTPUTS + VECTOR_OBS_HISTORY
+                                       if not k.startswith("lanes")})
+    for k in SCENARIO_VECTOR_OBS_MAP_OUTPUTS + SCENARIO_VECTOR_OBS_TABLES:
+        setattr(v, k, tensors.get(k))
+    return v
+
+
 class MdState(C.Structure):
     _fields_ = [
         ("shape", P), ("dyn", P), ("param", P), ("nav", P), ("pid", P), ("action", P), ("route_nodes", P),
@@ -341,6 +389,8 @@ PED_ENTRY_POINTS = {"md_ped": (_i, [_S, _K, C.POINTER(MdPed), P])}
 CONTACT_RESPONSE_ENTRY_POINTS = {"md_contact_response": (_i, [_S, _K, C.POINTER(MdContactResponse), P])}
 # include/md_vector_obs.h: (w, s, c, vo, stream)
 VECTOR_OBS_ENTRY_POINTS = {"md_vector_obs": (_i, [_W, _S, _K, C.POINTER(MdVectorObs), P])}
+# include/md_scenario_vector_obs.h: (w, s, c, sv, stream)
+SCENARIO_VECTOR_OBS_ENTRY_POINTS = {"md_scenario_vector_obs": (_i, [_W, _S, _K, C.POINTER(MdScenarioVectorObs), P])}
 # declared in no header: the hooks of diagnostic (-DMD_STAMP) builds, and md_localize through the lean step's road-first path
 # (the parity tests call it; a -DMD_LOC_ROAD_FIRST=0 build runs the plain walk under that name)
 OPTIONAL_ENTRY_POINTS = {"md_debug_set_stamp_buffer": (_i, [P]), "md_debug_set_env_order": (_i, [P]),

@@ -194,6 +194,44 @@ def check_vector_obs(user):
         vo[k] = float(vo[k])
     return vo
 
+
+# BatchedScenarioEnv's vector scene observation (config scenario_vector_obs; include/md_scenario_vector_obs.h).  Like the numbers
+# above, every default here is a design choice, not a value of the reference's.
+SCENARIO_VECTOR_OBS_DEFAULT_CONFIG = dict(
+    num_agents=8,           # K nearest movers, 1 .. 16
+    history=5,              # T frames of pose history, the current one included, 1 .. 8
+    radius=50.0,            # m: movers farther from the observer than this are no neighbours
+    max_jump=8.0,           # m: a displacement between two frames beyond this ends a slot's history
+    route_points=16,        # M waypoints along the recorded trajectory ahead, 0 .. 32
+    route_spacing=4.0,      # m between them
+    num_pieces=32,          # P nearest map polyline pieces, 0 .. 64
+    piece_points=8,         # S points per piece, 2 .. 16
+    map_radius=50.0,        # m: pieces without a point this close to the observer are not taken
+    map_spacing=2.0,        # m between the samples of a map polyline (the host resamples every feature once per scene)
+)
+# key -> (lowest, highest): MD_VO_MAX_* of include/md_vector_obs.h, MD_SVO_MAX_* of include/md_scenario_vector_obs.h
+SCENARIO_VECTOR_OBS_RANGES = dict(num_agents=(1, 16), history=(1, 8), route_points=(0, 32), num_pieces=(0, 64), piece_points=(2, 16))
+SCENARIO_VECTOR_OBS_LENGTHS = ("radius", "max_jump", "route_spacing", "map_radius", "map_spacing")
+
+
+def check_scenario_vector_obs(user):
+    """config["scenario_vector_obs"] (a dict) laid over its defaults -> the finished dict; a ValueError names the key at fault"""
+    known = sorted(SCENARIO_VECTOR_OBS_DEFAULT_CONFIG)
+    if not isinstance(user, dict):
+        raise ValueError("scenario_vector_obs={!r}: None (off) or a dict of {}".format(user, known))
+    unknown = sorted(set(user) - set(SCENARIO_VECTOR_OBS_DEFAULT_CONFIG))
+    if unknown:
+        raise ValueError("scenario_vector_obs: unknown key(s) {} (known: {})".format(unknown, known))
+    vo = dict(SCENARIO_VECTOR_OBS_DEFAULT_CONFIG, **user)
+    for k, (lo, hi) in SCENARIO_VECTOR_OBS_RANGES.items():
+        if isinstance(vo[k], bool) or not isinstance(vo[k], int) or not lo <= vo[k] <= hi:
+            raise ValueError("scenario_vector_obs['{}']={!r}: an int in [{}, {}]".format(k, vo[k], lo, hi))
+    for k in SCENARIO_VECTOR_OBS_LENGTHS:
+        if isinstance(vo[k], bool) or not isinstance(vo[k], (int, float)) or not 0 < vo[k] <= 1e18:
+            raise ValueError("scenario_vector_obs['{}']={!r}: a positive number of metres".format(k, vo[k]))
+        vo[k] = float(vo[k])
+    return vo
+
 # The top-down observation envs' own keys (envs/top_down_env.py:12-21,54-61 of the reference): they exist for BatchedTopDownMetaDrive /
 # BatchedTopDownMetaDriveEnvV2 only (make_config(top_down=True)); any other class given one raises KeyError, as the reference's would.
 # norm_pixel is on the cosmetic list below for every other class; for these two it decides the image's dtype.

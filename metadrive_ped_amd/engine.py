@@ -586,6 +586,7 @@ class BatchedEngine:
         self.agent_id = sd["agent_id"].view(torch.int32).view(self.E, self.cap) if "agent_id" in sd else None
         self._topdown_setup()
         self._vector_obs_setup()
+        self._scenario_vector_obs_setup()
         if getattr(h, "tracks", None) is not None:     # scenario mode: the scenes' recorded frames come with the host scene
             tr = h.tracks
             self.set_tracks(dict(shape=torch.from_numpy(np.ascontiguousarray(tr["shape"]).view(np.uint8).reshape(tr["shape"].shape[0], -1)),
@@ -641,6 +642,37 @@ class BatchedEngine:
         self.vector_obs_out = views
         self._vo_blocks = (outs, hist)
         self._vo = abi.make_md_vector_obs(vo, ptrs)
+
+    def _scenario_vector_obs_setup(self):
+        """The vector scene observation of scenario mode (config scenario_vector_obs; include/md_scenario_vector_obs.h): the same TWO
+        allocations with one row per env as _vector_obs_setup makes -- the ten output blocks (self.vector_obs_out: typed views [E, ...]),
+        and the engine-owned history -- plus the per-scene map piece table the host scene built (ScenarioHostScene.map_pieces),
+        uploaded once.  md_scenario_vector_obs's arguments, not MdState's or MdWorld's.  self._svo is None when the key is None."""
+        torch, vo = self.torch, self.cfg.get("scenario_vector_obs")
+        self._svo = self.scenario_map_dev = None
+        if vo is None:
+            return
+        outs, out_bytes, hist, hist_bytes = abi.scenario_vector_obs_blocks(vo, self.cap)
+        self.vector_obs_rows = torch.zeros((self.E, out_bytes), dtype=torch.uint8, device=self.device)
+        self.vector_obs_hist = torch.zeros((self.E, hist_bytes), dtype=torch.uint8, device=self.device)
+        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32}
+        views, ptrs = OrderedDict(), dict(out_stride=out_bytes, hist_stride=hist_bytes, max_pieces=0)
+        for table, rows, into in ((outs, self.vector_obs_rows, views), (hist, self.vector_obs_hist, None)):
+            for name, (off, shape, dt) in table.items():
+                n = int(np.prod(shape)) * dt.itemsize
+                if n:                       # a block whose count is 0 has no bytes: its pointer stays NULL, its view is empty
+                    ptrs[name] = rows.data_ptr() + off
+                if into is not None:
+                    into[name] = rows[:, off:off + n].view(tdt[dt]).view((self.E, ) + tuple(shape))
+        pieces = getattr(self.host, "map_pieces", None)
+        if int(vo["num_pieces"]) > 0:
+            if pieces is None:
+                raise RuntimeError("scenario_vector_obs: the host scene carries no map piece table (it was built without the key)")
+            self.scenario_map_dev = {k: self._to_dev(pieces[k]) for k in abi.SCENARIO_VECTOR_OBS_TABLES}
+            ptrs.update({k: t.data_ptr() for k, t in self.scenario_map_dev.items()}, max_pieces=pieces["max_pieces"])
+        self.vector_obs_out = views
+        self._vo_blocks = (outs, hist)
+        self._svo = abi.make_md_scenario_vector_obs(vo, ptrs)
 
     def vector_obs_history(self):
         """The vector observation's history as host numpy copies: ring_pose [E, T, cap, 4], ring_flags [E, T, cap], cursor [E, 4]
@@ -757,6 +789,8 @@ class BatchedEngine:
             self._launch("md_topdown", C.byref(self._td))
         if self._vo is not None:         # the vector scene observation, likewise: a walking env's last frame is traced on the old map
             self._launch("md_vector_obs", C.byref(self._vo))
+        if self._svo is not None:        # scenario mode's: before the walk's swap and the curriculum move an env on to another scene
+            self._launch("md_scenario_vector_obs", C.byref(self._svo))
         # Only now, with the step's observation complete, do the envs whose episode just ended move on: the swap of a walk rewrites
         # MdWorld.env_map, and the detector launches above trace the map of the episode that ended
         if self._cur is not None:        # the scenario walk: the curriculum's step, and the envs whose episode just ended move on
@@ -1077,7 +1111,7 @@ class BatchedEngine:
                    ("protect_flags", self.protect_flags)]
         if self._staged is not None and not self._walk:
             ex.append(("draw_idx", self.draw_idx))
-        if self._vo is not None:
+        if self.vector_obs_rows is not None:
             ex += [("vector_obs_hist", self.vector_obs_hist), ("vector_obs", self.vector_obs_rows)]
         out = []
         for name, t in ex:

@@ -88,6 +88,30 @@ class BatchedScenarioEnv(BatchedEnvBase):
         terminated, truncated = self._done_flags()
         return self.engine.obs[:, 0, :], self.engine.reward[:, 0], terminated, truncated, self._info()
 
+    # -- the vector scene observation (include/md_scenario_vector_obs.h) ----------------------------------------------------------
+    def _vector_obs_config(self, what):
+        vo = self.config.get("scenario_vector_obs")
+        if vo is None:
+            raise RuntimeError("{}(): config['scenario_vector_obs'] is None; give it a dict ({{}} takes the defaults) to turn the "
+                               "vector scene observation on".format(what))
+        return vo
+
+    def vector_obs_spec(self):
+        """{name: (shape, numpy dtype)} of vector_obs()'s tensors, leading axis [E]"""
+        outs = abi.scenario_vector_obs_blocks(self._vector_obs_config("vector_obs_spec"), 1)[0]
+        return {name: ((self.num_envs, ) + tuple(shape), dt.type) for name, (_, shape, dt) in outs.items()}
+
+    def vector_obs(self):
+        """The vector scene observation of the state the last step() / reset() left, a dict of device tensors in the ego frame, metres:
+        agents [E, K, T, 4] (x, y, cos, sin per frame, frame 0 = now), agents_mask, agents_meta [E, K, 4] (length, width, speed, kind),
+        ego [E, T, 4], ego_mask, route [E, M, 4] (x, y, dx, dy of the recorded trajectory ahead), route_mask, map [E, P, S, 2] (the
+        nearest map polyline pieces), map_mask [E, P, S], map_meta [E, P, 4] (class 0 lane / 1 line / 2 edge, type code -- the index
+        into scenario.MAP_FEATURE_TYPES --, points, squared distance).  Views of the engine's buffers, valid until the next step() /
+        reset(); no host sync."""
+        self._vector_obs_config("vector_obs")
+        self._require_engine("vector_obs")
+        return dict(self.engine.vector_obs_out)
+
     # -- checkpoints (envs/base_env.py:775-836 get_state / set_state through the managers): a dict of numpy arrays; the routes the
     #    device cut at later spawn frames are state too and travel with it -----------------------------------------------------
     def get_state(self):
@@ -109,6 +133,7 @@ class BatchedScenarioEnv(BatchedEnvBase):
         self.engine.upload_state(arrays)
         if "scene_of" in arrays:     # the walk: each env's line map is its scene
             self.engine.world_dev["env_map"].copy_(self.engine.state_dev["scene_of"])
+        self.engine.vector_obs_forget()     # a checkpoint does not carry the vector observation's history
 
     def _info(self):
         e = self.engine

@@ -47,6 +47,10 @@ SCENARIO_DEFAULT_CONFIG = dict(
     scenario_pool_max_bytes=64 << 30,   # a walk's scene pool larger than this (device bytes) is refused
     # ScenarioEnv's curriculum (envs/scenario_env.py:31-33), per env of a walk (include/md_curriculum.h, curriculum_params)
     curriculum_level=1, episodes_to_evaluate_curriculum=None, target_success_rate=0.8,
+    # the vector scene observation of scenario mode (include/md_scenario_vector_obs.h; no key of the reference's): None = off, no
+    # launch and no array; a dict (an empty one too) is laid over config.SCENARIO_VECTOR_OBS_DEFAULT_CONFIG and env.vector_obs()
+    # returns the blocks
+    scenario_vector_obs=None,
 )
 SCENARIO_VEHICLE_CONFIG = dict(lidar=dict(num_lasers=120, distance=50), lane_line_detector=dict(num_lasers=0, distance=50),
                                side_detector=dict(num_lasers=12, distance=50))
@@ -56,7 +60,7 @@ _ONLY_SCENARIO_KEYS = ("data_directory", "start_scenario_index", "sequential_see
                        "steering_range_penalty", "heading_penalty", "lateral_penalty", "max_lateral_dist",
                        "no_negative_reward", "crash_human_cost", "relax_out_of_road_done", "allowed_more_steps",
                        "walk_scenarios", "walk_stride", "scenario_pool_max_bytes", "curriculum_level",
-                       "episodes_to_evaluate_curriculum", "target_success_rate")
+                       "episodes_to_evaluate_curriculum", "target_success_rate", "scenario_vector_obs")
 
 STATIC_THRESHOLD = 3.0        # ScenarioTrafficManager.STATIC_THRESHOLD
 IDM_CREATE_MIN_LENGTH = 5.0   # ScenarioTrafficManager.IDM_CREATE_MIN_LENGTH
@@ -108,6 +112,9 @@ def make_scenario_config(user=None):
     cfg = make_config(base)
     cfg.update(own)
     cfg["scenario_mode"] = True
+    if cfg["scenario_vector_obs"] is not None:
+        from metadrive_ped_amd.config import check_scenario_vector_obs
+        cfg["scenario_vector_obs"] = check_scenario_vector_obs(cfg["scenario_vector_obs"])
     if ego_replay:
         cfg["agent_policy"] = "ReplayEgoCarPolicy"
     if cfg["agent_policy"] == "IDMPolicy":
@@ -387,6 +394,95 @@ def scene_line_quads(map_features, map_region_size):
     return quads, kinds
 
 
+# The map polylines the vector scene observation reads (include/md_scenario_vector_obs.h).  A feature's type code is its index here;
+# the names are those of the reference's MetaDriveType.is_lane / is_road_line / is_road_boundary_line (type.py:109-154), in that order.
+MAP_LANE_TYPES = ("LANE_SURFACE_STREET", "LANE_SURFACE_UNSTRUCTURE", "LANE_UNKNOWN", "LANE_BIKE_LANE", "LANE_FREEWAY")
+MAP_LINE_TYPES = ("UNKNOWN_LINE", "ROAD_LINE_BROKEN_SINGLE_WHITE", "ROAD_LINE_SOLID_SINGLE_WHITE", "ROAD_LINE_SOLID_DOUBLE_WHITE",
+                  "ROAD_LINE_BROKEN_SINGLE_YELLOW", "ROAD_LINE_BROKEN_DOUBLE_YELLOW", "ROAD_LINE_SOLID_SINGLE_YELLOW",
+                  "ROAD_LINE_SOLID_DOUBLE_YELLOW", "ROAD_LINE_PASSING_DOUBLE_YELLOW")
+MAP_EDGE_TYPES = ("UNKNOWN", "ROAD_EDGE_BOUNDARY", "ROAD_EDGE_MEDIAN")
+MAP_FEATURE_TYPES = MAP_LANE_TYPES + MAP_LINE_TYPES + MAP_EDGE_TYPES
+MAP_CLASS_LANE, MAP_CLASS_LINE, MAP_CLASS_EDGE = 0, 1, 2
+
+
+def map_feature_class(type_code):
+    return MAP_CLASS_LANE if type_code < len(MAP_LANE_TYPES) else \
+        MAP_CLASS_LINE if type_code < len(MAP_LANE_TYPES) + len(MAP_LINE_TYPES) else MAP_CLASS_EDGE
+
+
+def resample_polyline(polyline, spacing):
+    """A feature's polyline at every `spacing` metres of its arc length and at its end: zero-length steps dropped, the arc length in
+    float64, samples at k * spacing for k < ceil(L / spacing) and at L, linear interpolation, float32 [n, 2]; None when L < 1e-6."""
+    pts = np.asarray(polyline, dtype=np.float64)[:, :2]
+    step = np.hypot(*np.diff(pts, axis=0).T)
+    keep = np.concatenate([[True], step > 0.0])
+    pts = pts[keep]
+    arc = np.concatenate([[0.0], np.cumsum(step[step > 0.0])])
+    L = float(arc[-1])
+    if L < 1e-6:
+        return None
+    at = np.concatenate([np.arange(int(math.ceil(L / spacing)), dtype=np.float64) * spacing, [L]])
+    return np.stack([np.interp(at, arc, pts[:, 0]), np.interp(at, arc, pts[:, 1])], 1).astype(np.float32)
+
+
+def scene_map_pieces(map_features, spacing, S):
+    """The piece table of one scene: every lane / road line / road boundary feature with a polyline of at least two points, in the
+    order of the dict, resampled (resample_polyline) and cut into pieces of S samples -- piece q holds samples q (S - 1) ..
+    q (S - 1) + S - 1 while q (S - 1) < n - 1, so neighbours share an end point; the last one holds n_pts >= 2 samples and is padded
+    with its last point.  -> (xy [pieces, S, 2] float32, info [pieces, 4] int32: class, type code, n_pts, the feature's ordinal among
+    the dict's features).  Polygons (crosswalks, sidewalks, speed bumps), stop signs and driveways are skipped."""
+    xy, info = [], []
+    for ordinal, f in enumerate((map_features or {}).values()):
+        typ = f.get("type")
+        if typ not in MAP_FEATURE_TYPES or "polyline" not in f or len(f["polyline"]) < 2:
+            continue
+        pts = resample_polyline(f["polyline"], spacing)
+        if pts is None:
+            continue
+        code, n = MAP_FEATURE_TYPES.index(typ), len(pts)
+        q = 0
+        while q * (S - 1) < n - 1:
+            piece = pts[q * (S - 1):q * (S - 1) + S]
+            n_pts = len(piece)
+            xy.append(np.concatenate([piece, np.repeat(piece[-1:], S - n_pts, axis=0)]))
+            info.append((map_feature_class(code), code, n_pts, ordinal))
+            q += 1
+    return (np.asarray(xy, np.float32).reshape(-1, S, 2), np.asarray(info, np.int32).reshape(-1, 4))
+
+
+def map_piece_balls(xy, info):
+    """[pieces, 4] float32: a circle around every piece's n_pts points, as _poly_balls makes them -- the centre the middle of the
+    points' bounding box, the radius the farthest point in float64, stored as float32 with the radius rounded UP past the centre's
+    rounding and a 1e-3 m margin -- the kernel's exact cull."""
+    out = np.zeros((len(xy), 4), np.float32)
+    if len(xy) == 0:
+        return out
+    p = xy.astype(np.float64)                   # a padded point repeats the last one: it changes neither the box nor the radius
+    cx = (0.5 * (p[:, :, 0].min(1) + p[:, :, 0].max(1))).astype(np.float32)
+    cy = (0.5 * (p[:, :, 1].min(1) + p[:, :, 1].max(1))).astype(np.float32)
+    r = np.hypot(p[:, :, 0] - cx.astype(np.float64)[:, None], p[:, :, 1] - cy.astype(np.float64)[:, None]).max(1)
+    out[:, 0], out[:, 1] = cx, cy
+    out[:, 2] = np.nextafter((r + 1.0e-3 + 1.0e-6 * (np.abs(cx) + np.abs(cy))).astype(np.float32), np.float32(np.inf))
+    return out
+
+
+def map_piece_tables(per_scene, S, max_scene_pieces=None):
+    """The tables of MdScenarioVectorObs over the scenes' (xy, info) pairs: dict(map_off [scenes + 1], map_xy, map_info, map_ball,
+    max_pieces).  A scene with more pieces than MD_SVO_MAX_PIECES is refused."""
+    limit = abi.MD_SVO_MAX_PIECES if max_scene_pieces is None else max_scene_pieces
+    counts = [len(xy) for xy, _ in per_scene]
+    for q, n in enumerate(counts):
+        if n > limit:
+            raise ValueError("scenario_vector_obs: scene {} has {} map polyline pieces, more than MD_SVO_MAX_PIECES={}: raise "
+                             "map_spacing or piece_points".format(q, n, limit))
+    xy = np.concatenate([xy for xy, _ in per_scene]) if sum(counts) else np.zeros((0, S, 2), np.float32)
+    info = np.concatenate([i for _, i in per_scene]) if sum(counts) else np.zeros((0, 4), np.int32)
+    pad = 1 if len(xy) == 0 else 0               # never an empty device array
+    return dict(map_off=np.concatenate([[0], np.cumsum(counts)]).astype(np.int32),
+                map_xy=np.concatenate([xy, np.zeros((pad, S, 2), np.float32)]), map_info=np.concatenate([info, np.zeros((pad, 4), np.int32)]),
+                map_ball=np.concatenate([map_piece_balls(xy, info), np.zeros((pad, 4), np.float32)]), max_pieces=int(max(counts + [0])))
+
+
 def _to_frames(a, T):
     """first T frames of a per-frame array, zero / False padded"""
     a = np.asarray(a)
@@ -401,7 +497,7 @@ def _build_scene(job):
     """One scenario description -> the per-scene arrays (module-level so that a fork pool can run it)."""
     from metadrive_ped_amd.scene import vehicle_param_record
     from metadrive_ped_amd.rng import get_np_random
-    e, sc, cap, T, seed, dt, no_traffic, region = job
+    e, sc, cap, T, seed, dt, no_traffic, region, svo = job
     shape0 = np.zeros(cap, dtype=abi.SHAPE_DT)
     shape0["aux"] = -1
     dyn0 = np.zeros(cap, dtype=abi.DYN_DT)
@@ -521,8 +617,10 @@ def _build_scene(job):
         verts.append(pl.outline() if want_outline else np.zeros((0, 2)))
     from metadrive_ped_amd.mapgen.tables import StaticTables
     static = StaticTables(*scene_line_quads(sc.get("map_features"), region))      # road-line bodies + their grid
+    # the vector scene observation's piece table (svo: None, or its (map_spacing, piece_points))
+    map_pieces = scene_map_pieces(sc.get("map_features"), *svo) if svo is not None else None
     return dict(shape0=shape0, dyn0=dyn0, param=param, fshape=fshape, fdyn=fdyn, meta=meta, order=order, segs=segs, verts=verts, ckpt=ck,
-                static=static, runs=runs, cut_frames=cut_frames, cut_metres=cut_metres)
+                static=static, runs=runs, cut_frames=cut_frames, cut_metres=cut_metres, map_pieces=map_pieces)
 
 
 
@@ -711,10 +809,14 @@ class ScenarioHostScene(HostSceneBase):
         from metadrive_ped_amd import hostpool
         cfg = self.cfg
         fallback = self.seeds if order is None else [int(cfg["start_scenario_index"]) + i for i in order]   # the dataset index
+        vo = cfg.get("scenario_vector_obs")
+        svo = (float(vo["map_spacing"]), int(vo["piece_points"])) if vo is not None and int(vo["num_pieces"]) > 0 else None
         jobs = [(p, sc, self.cap, self.T, int(sc["metadata"].get("seed", fallback[p])), cfg["physics_world_step_size"],
-                 bool(cfg["no_traffic"]), float(cfg["map_region_size"])) for p, sc in enumerate(scenarios)]
+                 bool(cfg["no_traffic"]), float(cfg["map_region_size"]), svo) for p, sc in enumerate(scenarios)]
         built = hostpool.build_all(_build_scene, jobs, workers=int(cfg.get("build_workers", 0)))
         self.track_ids = [b_["order"] for b_ in built]
+        # the vector scene observation's map polyline pieces, per scene (None without the key, or with num_pieces 0)
+        self.map_pieces = map_piece_tables([b_["map_pieces"] for b_ in built], svo[1]) if svo is not None else None
         self.tracks = dict(shape=np.concatenate([b_["fshape"] for b_ in built], axis=1),
                            dyn=np.concatenate([b_["fdyn"] for b_ in built], axis=1), seeds=list(self.seeds), cap=self.cap)
         return built
