@@ -285,6 +285,43 @@ def make_md_scenario_vector_obs(vo_cfg, tensors):
     return v
 
 
+# include/md_traffic_lights.h: the ceilings MD_TL_MAX_*, the status codes, and md_traffic_lights's argument block
+MD_TL_MAX_LIGHTS, MD_TL_MAX_SCENE_LIGHTS = 32, 1024
+TL_UNKNOWN, TL_GREEN, TL_YELLOW, TL_RED = 0, 1, 2, 3
+TL_BIT_GREEN, TL_BIT_YELLOW, TL_BIT_RED = 1, 2, 4
+TRAFFIC_LIGHTS_OUTPUTS = ("agent_light", "lights", "lights_mask", "lights_index")
+TRAFFIC_LIGHTS_TABLES = ("tl_off", "tl_box", "tl_info", "tl_status")
+
+
+class MdTrafficLights(C.Structure):
+    """include/md_traffic_lights.h: L, the radius, the largest scene, the stride, the engine-owned per-scene light tables, the outputs"""
+    _fields_ = [("struct_size", C.c_int32), ("num_lights", C.c_int32), ("radius", C.c_float), ("max_scene_lights", C.c_int32),
+                ("out_stride", C.c_int32), ("reserved", C.c_int32)] + [(k, P) for k in TRAFFIC_LIGHTS_TABLES + TRAFFIC_LIGHTS_OUTPUTS]
+
+
+def traffic_lights_blocks(tl_cfg):
+    """-> (outputs, output row bytes): name -> (byte offset in an env's row, shape after the env axis, numpy dtype), every block
+    16-byte aligned, like scenario_vector_obs_blocks.  agent_light is one byte per env."""
+    L = int(tl_cfg["num_lights"])
+    table, at = {}, 0
+    for name, shape, dt in (("agent_light", (), np.uint8), ("lights", (L, 6), f4), ("lights_mask", (L, ), np.uint8), ("lights_index", (L, ), i4)):
+        table[name] = (at, shape, np.dtype(dt))
+        at = (at + int(np.prod(shape)) * np.dtype(dt).itemsize + 15) // 16 * 16
+    return table, at
+
+
+def make_md_traffic_lights(tl_cfg, tensors):
+    """MdTrafficLights of the finished config["traffic_lights"]; `tensors`: out_stride, max_scene_lights and name -> address of env 0's
+    block / of the table (None / missing: NULL)"""
+    v = MdTrafficLights()
+    v.struct_size = C.sizeof(MdTrafficLights)
+    v.num_lights, v.radius = int(tl_cfg["num_lights"]), float(tl_cfg["radius"])
+    v.max_scene_lights, v.out_stride = int(tensors.get("max_scene_lights", 0)), int(tensors.get("out_stride", 0))
+    for k in TRAFFIC_LIGHTS_TABLES + TRAFFIC_LIGHTS_OUTPUTS:
+        setattr(v, k, tensors.get(k))
+    return v
+
+
 class MdState(C.Structure):
     _fields_ = [
         ("shape", P), ("dyn", P), ("param", P), ("nav", P), ("pid", P), ("action", P), ("route_nodes", P),
@@ -391,6 +428,8 @@ CONTACT_RESPONSE_ENTRY_POINTS = {"md_contact_response": (_i, [_S, _K, C.POINTER(
 VECTOR_OBS_ENTRY_POINTS = {"md_vector_obs": (_i, [_W, _S, _K, C.POINTER(MdVectorObs), P])}
 # include/md_scenario_vector_obs.h: (w, s, c, sv, stream)
 SCENARIO_VECTOR_OBS_ENTRY_POINTS = {"md_scenario_vector_obs": (_i, [_W, _S, _K, C.POINTER(MdScenarioVectorObs), P])}
+# include/md_traffic_lights.h: (w, s, c, tl, stream)
+TRAFFIC_LIGHTS_ENTRY_POINTS = {"md_traffic_lights": (_i, [_W, _S, _K, C.POINTER(MdTrafficLights), P])}
 # declared in no header: the hooks of diagnostic (-DMD_STAMP) builds, and md_localize through the lean step's road-first path
 # (the parity tests call it; a -DMD_LOC_ROAD_FIRST=0 build runs the plain walk under that name)
 OPTIONAL_ENTRY_POINTS = {"md_debug_set_stamp_buffer": (_i, [P]), "md_debug_set_env_order": (_i, [P]),

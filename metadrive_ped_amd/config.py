@@ -232,6 +232,33 @@ def check_scenario_vector_obs(user):
         vo[k] = float(vo[k])
     return vo
 
+
+# BatchedScenarioEnv's traffic lights (config traffic_lights; include/md_traffic_lights.h).  The walls, their statuses and the flags
+# are the reference's; the two numbers of the nearest-lights block are design choices, not values of the reference's.
+TRAFFIC_LIGHTS_DEFAULT_CONFIG = dict(
+    num_lights=8,           # L nearest lights in the observation block, 0 .. 32 (MD_TL_MAX_LIGHTS)
+    radius=80.0,            # m: lights whose stop point is farther from the observer than this are not taken
+)
+TRAFFIC_LIGHTS_RANGES = dict(num_lights=(0, 32))
+
+
+def check_traffic_lights(user):
+    """config["traffic_lights"] (a dict) laid over its defaults -> the finished dict; a ValueError names the key at fault"""
+    known = sorted(TRAFFIC_LIGHTS_DEFAULT_CONFIG)
+    if not isinstance(user, dict):
+        raise ValueError("traffic_lights={!r}: None (off) or a dict of {}".format(user, known))
+    unknown = sorted(set(user) - set(TRAFFIC_LIGHTS_DEFAULT_CONFIG))
+    if unknown:
+        raise ValueError("traffic_lights: unknown key(s) {} (known: {})".format(unknown, known))
+    tl = dict(TRAFFIC_LIGHTS_DEFAULT_CONFIG, **user)
+    for k, (lo, hi) in TRAFFIC_LIGHTS_RANGES.items():
+        if isinstance(tl[k], bool) or not isinstance(tl[k], int) or not lo <= tl[k] <= hi:
+            raise ValueError("traffic_lights['{}']={!r}: an int in [{}, {}]".format(k, tl[k], lo, hi))
+    if isinstance(tl["radius"], bool) or not isinstance(tl["radius"], (int, float)) or not 0 < tl["radius"] <= 1e18:
+        raise ValueError("traffic_lights['radius']={!r}: a positive number of metres".format(tl["radius"]))
+    tl["radius"] = float(tl["radius"])
+    return tl
+
 # The top-down observation envs' own keys (envs/top_down_env.py:12-21,54-61 of the reference): they exist for BatchedTopDownMetaDrive /
 # BatchedTopDownMetaDriveEnvV2 only (make_config(top_down=True)); any other class given one raises KeyError, as the reference's would.
 # norm_pixel is on the cosmetic list below for every other class; for these two it decides the image's dtype.

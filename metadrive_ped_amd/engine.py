@@ -587,6 +587,7 @@ class BatchedEngine:
         self._topdown_setup()
         self._vector_obs_setup()
         self._scenario_vector_obs_setup()
+        self._traffic_lights_setup()
         if getattr(h, "tracks", None) is not None:     # scenario mode: the scenes' recorded frames come with the host scene
             tr = h.tracks
             self.set_tracks(dict(shape=torch.from_numpy(np.ascontiguousarray(tr["shape"]).view(np.uint8).reshape(tr["shape"].shape[0], -1)),
@@ -673,6 +674,32 @@ class BatchedEngine:
         self.vector_obs_out = views
         self._vo_blocks = (outs, hist)
         self._svo = abi.make_md_scenario_vector_obs(vo, ptrs)
+
+    def _traffic_lights_setup(self):
+        """The traffic lights of scenario mode (config traffic_lights; include/md_traffic_lights.h): ONE allocation with one row per env
+        for the four output blocks (self.traffic_lights_out: typed views [E, ...]) and the per-scene light tables the host scene built
+        (ScenarioHostScene.traffic_lights), uploaded once.  md_traffic_lights's arguments, not MdState's or MdWorld's.  self._tl is
+        None, and nothing is allocated, when the key is None."""
+        torch, tl = self.torch, self.cfg.get("traffic_lights")
+        self._tl = self.traffic_lights_rows = self.traffic_lights_out = self.traffic_lights_dev = None
+        if tl is None or not self.cfg.get("scenario_mode"):
+            return
+        tables = getattr(self.host, "traffic_lights", None)
+        if tables is None:
+            raise RuntimeError("traffic_lights: the host scene carries no light tables (it was built without the key)")
+        outs, out_bytes = abi.traffic_lights_blocks(tl)
+        self.traffic_lights_rows = torch.zeros((self.E, out_bytes), dtype=torch.uint8, device=self.device)
+        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32}
+        views, ptrs = OrderedDict(), dict(out_stride=out_bytes, max_scene_lights=tables["max_scene_lights"])
+        for name, (off, shape, dt) in outs.items():
+            n = int(np.prod(shape)) * dt.itemsize
+            if n:                       # L = 0: the lights blocks have no bytes, their pointers stay NULL, their views are empty
+                ptrs[name] = self.traffic_lights_rows.data_ptr() + off
+            views[name] = self.traffic_lights_rows[:, off:off + n].view(tdt[dt]).view((self.E, ) + tuple(shape))
+        self.traffic_lights_dev = {k: self._to_dev(tables[k]) for k in abi.TRAFFIC_LIGHTS_TABLES}
+        ptrs.update({k: t.data_ptr() for k, t in self.traffic_lights_dev.items()})
+        self.traffic_lights_out = views
+        self._tl = abi.make_md_traffic_lights(tl, ptrs)
 
     def vector_obs_history(self):
         """The vector observation's history as host numpy copies: ring_pose [E, T, cap, 4], ring_flags [E, T, cap], cursor [E, 4]
@@ -791,6 +818,8 @@ class BatchedEngine:
             self._launch("md_vector_obs", C.byref(self._vo))
         if self._svo is not None:        # scenario mode's: before the walk's swap and the curriculum move an env on to another scene
             self._launch("md_scenario_vector_obs", C.byref(self._svo))
+        if self._tl is not None:         # the traffic lights, likewise: a walking env's last frame is read on its own scene's lights
+            self._launch("md_traffic_lights", C.byref(self._tl))
         # Only now, with the step's observation complete, do the envs whose episode just ended move on: the swap of a walk rewrites
         # MdWorld.env_map, and the detector launches above trace the map of the episode that ended
         if self._cur is not None:        # the scenario walk: the curriculum's step, and the envs whose episode just ended move on

@@ -112,6 +112,37 @@ class BatchedScenarioEnv(BatchedEnvBase):
         self._require_engine("vector_obs")
         return dict(self.engine.vector_obs_out)
 
+    # -- the traffic lights (include/md_traffic_lights.h) ----------------------------------------------------------------------------
+    def _traffic_lights_config(self, what):
+        tl = self.config.get("traffic_lights")
+        if tl is None:
+            raise RuntimeError("{}(): config['traffic_lights'] is None; give it a dict ({{}} takes the defaults) to turn the traffic "
+                               "lights on".format(what))
+        return tl
+
+    def traffic_lights_spec(self):
+        """{name: (shape, numpy dtype)} of traffic_lights()'s tensors, leading axis [E]"""
+        outs = abi.traffic_lights_blocks(self._traffic_lights_config("traffic_lights_spec"))[0]
+        return {name: ((self.num_envs, ) + tuple(shape), dt.type) for name, (_, shape, dt) in outs.items()}
+
+    def traffic_lights(self):
+        """The traffic lights as the last step() / reset() left them, a dict of device tensors: agent_light [E] uint8 (bit 0 green,
+        bit 1 yellow, bit 2 red: the walls the ego's chassis overlapped in this step, by the status they had during it), lights
+        [E, L, 6] (x, y of the stop point and dx, dy of the lane direction in the ego frame, metres; the status now on show -- 0
+        unknown, 1 green, 2 yellow, 3 red --; the squared distance), lights_mask [E, L], lights_index [E, L] int32 (the light's place
+        in traffic_light_ids(scenario), -1 for an empty rank).  Views of the engine's buffers, valid until the next step() / reset();
+        no host sync."""
+        self._traffic_lights_config("traffic_lights")
+        self._require_engine("traffic_lights")
+        return dict(self.engine.traffic_lights_out)
+
+    def traffic_light_ids(self, scenario_index):
+        """The keys of dynamic_map_states that became lights of scenario `scenario_index` (its position in the batch, or in the walk's
+        pool), in the order lights_index counts them (host list)"""
+        self._traffic_lights_config("traffic_light_ids")
+        self._require_engine("traffic_light_ids")
+        return list(self.engine.host.traffic_light_ids[int(scenario_index)])
+
     # -- checkpoints (envs/base_env.py:775-836 get_state / set_state through the managers): a dict of numpy arrays; the routes the
     #    device cut at later spawn frames are state too and travel with it -----------------------------------------------------
     def get_state(self):
@@ -144,6 +175,10 @@ class BatchedScenarioEnv(BatchedEnvBase):
                  "route_completion": si[:, 6], "action": e.action[:, 0, :], "raw_action": e.action[:, 0, :]}
         lazy = self._flag_info(fl)
         lazy["scenario_index"] = self._scenario_index
+        if e.traffic_lights_out is not None:   # vehicle.red_light / yellow_light / green_light (base_vehicle.py:720-733), device ops only
+            al = e.traffic_lights_out["agent_light"]
+            lazy.update(green_light=lambda: (al & abi.TL_BIT_GREEN) != 0, yellow_light=lambda: (al & abi.TL_BIT_YELLOW) != 0,
+                        red_light=lambda: (al & abi.TL_BIT_RED) != 0)
         if e.host.walk:     # the curriculum's keys (envs/scenario_env.py:279-285), as md_curriculum reported them for this step
             torch = e.torch
             rep_i = e.state_dev["cur_rep_i"].view(torch.int32).view(self.num_envs, 2)

@@ -51,6 +51,11 @@ SCENARIO_DEFAULT_CONFIG = dict(
     # launch and no array; a dict (an empty one too) is laid over config.SCENARIO_VECTOR_OBS_DEFAULT_CONFIG and env.vector_obs()
     # returns the blocks
     scenario_vector_obs=None,
+    # the traffic lights of a description's dynamic_map_states (include/md_traffic_lights.h; the reference's ScenarioLightManager,
+    # which it registers unless no_light): None = off, no table, no launch and no info key -- NOT the reference's default, so that a
+    # batch behaves as it did before the lights were built; a dict (an empty one too) is laid over
+    # config.TRAFFIC_LIGHTS_DEFAULT_CONFIG.  skip_missing_light (envs/scenario_env.py:51) is read only with the key set.
+    traffic_lights=None, skip_missing_light=True,
 )
 SCENARIO_VEHICLE_CONFIG = dict(lidar=dict(num_lasers=120, distance=50), lane_line_detector=dict(num_lasers=0, distance=50),
                                side_detector=dict(num_lasers=12, distance=50))
@@ -60,7 +65,8 @@ _ONLY_SCENARIO_KEYS = ("data_directory", "start_scenario_index", "sequential_see
                        "steering_range_penalty", "heading_penalty", "lateral_penalty", "max_lateral_dist",
                        "no_negative_reward", "crash_human_cost", "relax_out_of_road_done", "allowed_more_steps",
                        "walk_scenarios", "walk_stride", "scenario_pool_max_bytes", "curriculum_level",
-                       "episodes_to_evaluate_curriculum", "target_success_rate", "scenario_vector_obs")
+                       "episodes_to_evaluate_curriculum", "target_success_rate", "scenario_vector_obs",
+                       "traffic_lights", "skip_missing_light")
 
 STATIC_THRESHOLD = 3.0        # ScenarioTrafficManager.STATIC_THRESHOLD
 IDM_CREATE_MIN_LENGTH = 5.0   # ScenarioTrafficManager.IDM_CREATE_MIN_LENGTH
@@ -115,6 +121,12 @@ def make_scenario_config(user=None):
     if cfg["scenario_vector_obs"] is not None:
         from metadrive_ped_amd.config import check_scenario_vector_obs
         cfg["scenario_vector_obs"] = check_scenario_vector_obs(cfg["scenario_vector_obs"])
+    if cfg["traffic_lights"] is not None:
+        from metadrive_ped_amd.config import check_traffic_lights
+        if cfg["no_light"]:
+            raise ValueError("traffic_lights is set together with no_light=True: no_light=True asks for a batch without lights, "
+                             "traffic_lights for their tables and flags; drop one of the two")
+        cfg["traffic_lights"] = check_traffic_lights(cfg["traffic_lights"])
     if ego_replay:
         cfg["agent_policy"] = "ReplayEgoCarPolicy"
     if cfg["agent_policy"] == "IDMPolicy":
@@ -483,6 +495,93 @@ def map_piece_tables(per_scene, S, max_scene_pieces=None):
                 map_ball=np.concatenate([map_piece_balls(xy, info), np.zeros((pad, 4), np.float32)]), max_pieces=int(max(counts + [0])))
 
 
+# The traffic lights of a description's dynamic_map_states (include/md_traffic_lights.h): ScenarioLightManager._get_episode_light_data /
+# after_reset (manager/scenario_light_manager.py:31-52,83-106) and BaseTrafficLight.__init__ (component/traffic_light/
+# base_traffic_light.py:44-60), restated once per scene.
+AIR_WALL_LENGTH = 0.25        # BaseTrafficLight.AIR_WALL_LENGTH: the wall's extent ALONG the lane
+LIGHT_LANE_WIDTH = 6.0        # ScenarioLane.VIS_LANE_WIDTH (component/lane/scenario_lane.py:23,43): width_at(0) of every scenario lane
+PLACE_LONGITUDE = 5.0         # BaseTrafficLight.PLACE_LONGITUDE: the wall's heading is the lane's at 5 m, wherever the wall stands
+_LIGHT_CODES = dict(
+    LANE_STATE_ARROW_STOP=abi.TL_RED, LANE_STATE_STOP=abi.TL_RED, TRAFFIC_LIGHT_RED=abi.TL_RED,
+    LANE_STATE_ARROW_CAUTION=abi.TL_YELLOW, LANE_STATE_CAUTION=abi.TL_YELLOW, LANE_STATE_FLASHING_CAUTION=abi.TL_YELLOW,
+    TRAFFIC_LIGHT_YELLOW=abi.TL_YELLOW,
+    LANE_STATE_ARROW_GO=abi.TL_GREEN, LANE_STATE_GO=abi.TL_GREEN, TRAFFIC_LIGHT_GREEN=abi.TL_GREEN)
+
+
+def light_status_code(status):
+    """MetaDriveType.simplify_light_status (type.py:221-236) as a code: 0 unknown (None, LANE_STATE_UNKNOWN, LANE_STATE_FLASHING_STOP,
+    TRAFFIC_LIGHT_UNKNOWN and any string it does not list), 1 green, 2 yellow, 3 red"""
+    if status is None:
+        return abi.TL_UNKNOWN
+    if isinstance(status, bytes):
+        status = status.decode()
+    return _LIGHT_CODES.get(str(status), abi.TL_UNKNOWN)
+
+
+def _light_position(entry):
+    """_get_episode_light_data's position (scenario_light_manager.py:89-103): the old format keeps a [T, 2] array under
+    state["stop_point"] and takes the row of the first frame whose state["lane"] is not 0 (the last row, first_pos = -1, when there
+    is none); the new format keeps one point at the entry's top level"""
+    state = entry["state"]
+    if "stop_point" in state:
+        rows = np.asarray(state["stop_point"], np.float64)
+        lane = np.asarray(state["lane"])
+        lane = lane.astype(np.float64) if lane.dtype.kind in "biuf" else np.asarray([float(x or 0) for x in lane.ravel()])
+        on = np.nonzero(lane != 0)[0]
+        return rows[int(on[0]) if len(on) else -1][:2]
+    return np.asarray(entry["stop_point"], np.float64)[:2]
+
+
+def scene_traffic_lights(scenario, skip_missing_light=True):
+    """The lights of one scenario description -> (box [n, 8] float32, status: a list of n uint8 arrays, ids: the n kept keys of
+    dynamic_map_states).  One light per key, in the dict's order -- its position among the kept keys is the light's ordinal.  The
+    lane is the map feature str(key), which must be a lane (a type of MAP_LANE_TYPES: the reference looks the key up among the road
+    network's lanes); a light without one is skipped, or refused with skip_missing_light=False.  The wall: centred on the position,
+    AIR_WALL_LENGTH along and the lane's 6 m across the heading the lane has at PLACE_LONGITUDE -- generate_static_box_physics_body
+    (utils/pg/utils.py:315) makes BulletBoxShape(heading_length / 2, side_width / 2, ...), so the SHORT side lies along the heading."""
+    feats = scenario.get("map_features") or {}
+    box, status, ids = [], [], []
+    for key, entry in (scenario.get("dynamic_map_states") or {}).items():
+        if entry.get("type") != "TRAFFIC_LIGHT":
+            raise ValueError("Can not handle {}".format(entry.get("type")))        # the reference's assert, with its message
+        pos = _light_position(entry)
+        lane = feats.get(str(key))
+        if lane is None or lane.get("type") not in MAP_LANE_TYPES or "polyline" not in lane or len(lane["polyline"]) < 2:
+            if skip_missing_light:
+                continue
+            raise ValueError("Can not find lane for this traffic light. Set skip_missing_light=True for skipping missing light!")
+        heading = PolyLine(lane["polyline"]).heading_at(PLACE_LONGITUDE)
+        box.append((pos[0], pos[1], math.cos(heading), math.sin(heading), 0.5 * AIR_WALL_LENGTH, 0.5 * LIGHT_LANE_WIDTH, 0.0, 0.0))
+        codes = [light_status_code(x) for x in np.asarray(entry["state"]["object_state"], dtype=object).ravel()]
+        status.append(np.asarray(codes or [abi.TL_UNKNOWN], np.uint8))              # never an empty array: one unknown frame
+        ids.append(key)
+    return np.asarray(box, np.float32).reshape(-1, 8), status, ids
+
+
+def traffic_light_tables(per_scene, max_scene_lights=None):
+    """The tables of MdTrafficLights over the scenes' (box, status, ids) triples: dict(tl_off [scenes + 1], tl_box [lights, 8],
+    tl_info [lights, 4] (status offset, frames, ordinal, 0), tl_status, max_scene_lights, ids: the kept keys per scene).  A scene
+    with more lights than MD_TL_MAX_SCENE_LIGHTS is refused; one without lights is legal."""
+    limit = abi.MD_TL_MAX_SCENE_LIGHTS if max_scene_lights is None else max_scene_lights
+    counts = [len(box) for box, _, _ in per_scene]
+    for q, n in enumerate(counts):
+        if n > limit:
+            raise ValueError("traffic_lights: scene {} has {} traffic lights, more than MD_TL_MAX_SCENE_LIGHTS={}".format(q, n, limit))
+    box = np.concatenate([b for b, _, _ in per_scene]) if sum(counts) else np.zeros((0, 8), np.float32)
+    info, status, at = [], [], 0
+    for _, st, _ in per_scene:
+        for ordinal, codes in enumerate(st):
+            info.append((at, len(codes), ordinal, 0))
+            status.append(codes)
+            at += len(codes)
+    pad = 1 if len(box) == 0 else 0               # never an empty device array
+    return dict(tl_off=np.concatenate([[0], np.cumsum(counts)]).astype(np.int32),
+                tl_box=np.concatenate([box, np.zeros((pad, 8), np.float32)]),
+                tl_info=np.concatenate([np.asarray(info, np.int32).reshape(-1, 4), np.zeros((pad, 4), np.int32)]),
+                tl_status=np.concatenate(status + [np.zeros(1, np.uint8)]),       # one spare byte: never empty
+                max_scene_lights=int(max(counts + [0])), ids=[list(ids) for _, _, ids in per_scene])
+
+
 def _to_frames(a, T):
     """first T frames of a per-frame array, zero / False padded"""
     a = np.asarray(a)
@@ -497,7 +596,7 @@ def _build_scene(job):
     """One scenario description -> the per-scene arrays (module-level so that a fork pool can run it)."""
     from metadrive_ped_amd.scene import vehicle_param_record
     from metadrive_ped_amd.rng import get_np_random
-    e, sc, cap, T, seed, dt, no_traffic, region, svo = job
+    e, sc, cap, T, seed, dt, no_traffic, region, svo, tl = job
     shape0 = np.zeros(cap, dtype=abi.SHAPE_DT)
     shape0["aux"] = -1
     dyn0 = np.zeros(cap, dtype=abi.DYN_DT)
@@ -619,8 +718,11 @@ def _build_scene(job):
     static = StaticTables(*scene_line_quads(sc.get("map_features"), region))      # road-line bodies + their grid
     # the vector scene observation's piece table (svo: None, or its (map_spacing, piece_points))
     map_pieces = scene_map_pieces(sc.get("map_features"), *svo) if svo is not None else None
+    # the traffic lights' walls and statuses (tl: None, or skip_missing_light)
+    lights = scene_traffic_lights(sc, tl) if tl is not None else None
     return dict(shape0=shape0, dyn0=dyn0, param=param, fshape=fshape, fdyn=fdyn, meta=meta, order=order, segs=segs, verts=verts, ckpt=ck,
-                static=static, runs=runs, cut_frames=cut_frames, cut_metres=cut_metres, map_pieces=map_pieces)
+                static=static, runs=runs, cut_frames=cut_frames, cut_metres=cut_metres, map_pieces=map_pieces,
+                lights=lights)
 
 
 
@@ -811,12 +913,16 @@ class ScenarioHostScene(HostSceneBase):
         fallback = self.seeds if order is None else [int(cfg["start_scenario_index"]) + i for i in order]   # the dataset index
         vo = cfg.get("scenario_vector_obs")
         svo = (float(vo["map_spacing"]), int(vo["piece_points"])) if vo is not None and int(vo["num_pieces"]) > 0 else None
+        tl = bool(cfg.get("skip_missing_light", True)) if cfg.get("traffic_lights") is not None else None
         jobs = [(p, sc, self.cap, self.T, int(sc["metadata"].get("seed", fallback[p])), cfg["physics_world_step_size"],
-                 bool(cfg["no_traffic"]), float(cfg["map_region_size"]), svo) for p, sc in enumerate(scenarios)]
+                 bool(cfg["no_traffic"]), float(cfg["map_region_size"]), svo, tl) for p, sc in enumerate(scenarios)]
         built = hostpool.build_all(_build_scene, jobs, workers=int(cfg.get("build_workers", 0)))
         self.track_ids = [b_["order"] for b_ in built]
         # the vector scene observation's map polyline pieces, per scene (None without the key, or with num_pieces 0)
         self.map_pieces = map_piece_tables([b_["map_pieces"] for b_ in built], svo[1]) if svo is not None else None
+        # the traffic lights' tables, per scene, and the kept keys of dynamic_map_states in ordinal order (None without the key)
+        self.traffic_lights = traffic_light_tables([b_["lights"] for b_ in built]) if tl is not None else None
+        self.traffic_light_ids = self.traffic_lights["ids"] if tl is not None else None
         self.tracks = dict(shape=np.concatenate([b_["fshape"] for b_ in built], axis=1),
                            dyn=np.concatenate([b_["fdyn"] for b_ in built], axis=1), seeds=list(self.seeds), cap=self.cap)
         return built
@@ -945,7 +1051,33 @@ def _track_dict(oid, typ, T, valid, x, y, h, speed, length, width, height):
             "metadata": {"type": typ, "object_id": str(oid), "track_length": int(T)}}
 
 
-def synthetic_scenario(seed, T=200, n_vehicles=18, n_parked=3, n_pedestrians=2, n_cones=4):
+def _synthetic_lights(seed, n_lights, T, sample, ego_s0):
+    """dynamic_map_states with n_lights (0 .. 3) lights, light i on lane "lane<i>" at a stop line 8 .. 32 m ahead of the ego's start,
+    cycling green (1.5 s) -> yellow (0.5 s) -> red (1.5 s) from a drawn phase; everything from a RandomState of its own.  New format
+    (stop_point at the top level); light 1 in the old one: state["stop_point"] [T, 2] and state["lane"] [T], both 0 in the first
+    three frames.  The synthetic ego drives through the stop lines whatever they show."""
+    if not 0 <= n_lights <= 3:
+        raise ValueError("n_lights={}: 0 .. 3, one light per lane of the synthetic road".format(n_lights))
+    rng = np.random.RandomState((int(seed) * 7919 + 104729) % (2 ** 31))
+    out = {}
+    for i in range(n_lights):
+        x, y, _ = sample(np.asarray([ego_s0 + 8.0 + 10.0 * i + rng.uniform(0.0, 4.0)]), (-3.5, 0.0, 3.5)[i])
+        phase = int(rng.randint(0, 35))
+        at = (np.arange(T) + phase) % 35
+        states = np.where(at < 15, "LANE_STATE_GO", np.where(at < 20, "LANE_STATE_CAUTION", "LANE_STATE_STOP")).tolist()
+        entry = {"type": "TRAFFIC_LIGHT", "state": {"object_state": states}, "lane": "lane%d" % i,
+                 "metadata": {"type": "TRAFFIC_LIGHT", "object_id": "lane%d" % i, "track_length": int(T), "dataset": "synthetic"}}
+        if i == 1:
+            on = (np.arange(T) >= 3).astype(np.float32)
+            entry["state"]["stop_point"] = (np.asarray([[float(x[0]), float(y[0])]], np.float32) * on[:, None]).astype(np.float32)
+            entry["state"]["lane"] = on.astype(np.int64)
+        else:
+            entry["stop_point"] = np.asarray([float(x[0]), float(y[0]), 0.0], np.float32)
+        out["lane%d" % i] = entry
+    return out
+
+
+def synthetic_scenario(seed, T=200, n_vehicles=18, n_parked=3, n_pedestrians=2, n_cones=4, n_lights=0):
     rng = np.random.RandomState(seed)
     s_axis, xy, heading = _path(rng, 4000)
     t = np.arange(T) * 0.1
@@ -1020,7 +1152,9 @@ def synthetic_scenario(seed, T=200, n_vehicles=18, n_parked=3, n_pedestrians=2, 
             "length": int(T),
             "metadata": {"ts": t.astype(np.float32), "metadrive_processed": False, "coordinate": "metadrive",
                          "dataset": "synthetic", "seed": int(seed), "sdc_id": "0", "scenario_id": "synthetic-%d" % seed},
-            "tracks": tracks, "dynamic_map_states": {}, "map_features": feats}
+            "tracks": tracks,
+            "dynamic_map_states": _synthetic_lights(seed, n_lights, T, lambda s, lat: _sample(s_axis, xy, heading, s, lat), ego_s0),
+            "map_features": feats}
 
 
 def synthetic_scenarios(n, seed0=0, **kw):
