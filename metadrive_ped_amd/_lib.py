@@ -34,7 +34,7 @@ def load():
     for name, (restype, argtypes) in dict(abi.ENTRY_POINTS, **abi.EXPERT_ENTRY_POINTS, **abi.AI_PROTECT_ENTRY_POINTS,
                                           **abi.EXPERT_SENSE_ENTRY_POINTS, **abi.CURRICULUM_ENTRY_POINTS, **abi.TOPDOWN_ENTRY_POINTS, **abi.RENDER_ENTRY_POINTS,
                                           **abi.BRANCH_ENTRY_POINTS, **abi.PED_ENTRY_POINTS, **abi.VECTOR_OBS_ENTRY_POINTS, **abi.SCENARIO_VECTOR_OBS_ENTRY_POINTS,
-                                          **abi.TRAFFIC_LIGHTS_ENTRY_POINTS,
+                                          **abi.TRAFFIC_LIGHTS_ENTRY_POINTS, **abi.SCENARIO_METRICS_ENTRY_POINTS,
                                           **abi.CONTACT_RESPONSE_ENTRY_POINTS, **optional).items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes

@@ -322,6 +322,57 @@ def make_md_traffic_lights(tl_cfg, tensors):
     return v
 
 
+# include/md_scenario_metrics.h: the ceiling MD_SM_MAX_TTC_SAMPLES, the columns by name, and md_scenario_metrics's argument block
+MD_SM_MAX_TTC_SAMPLES, MD_SM_STEP_COLS, MD_SM_EPISODE_COLS, MD_SM_STATE_COLS = 64, 12, 24, 12
+SCENARIO_METRICS_STEP_COLUMNS = ("log_divergence", "log_heading_error", "speed", "lon_accel", "yaw_rate", "lat_accel", "lon_jerk",
+                                 "yaw_accel", "jerk", "ttc", "on_red", "reserved")
+SCENARIO_METRICS_EPISODE_COLUMNS = ("steps", "ade", "max_divergence", "fde", "max_heading_error", "min_ttc", "ttc_violation_steps",
+                                    "max_lon_accel", "min_lon_accel", "max_abs_lat_accel", "max_abs_lon_jerk", "max_jerk",
+                                    "max_abs_yaw_rate", "max_abs_yaw_accel", "comfort_violation_steps", "red_light_steps",
+                                    "collision_steps", "out_of_road_steps", "route_completion", "arrive_dest") + ("reserved", ) * 4
+SCENARIO_METRICS_HISTORY_COLUMNS = ("v", "h", "lon_accel", "yaw_rate", "lat_accel", "clock", "rates", "latched", "divergence_sum",
+                                    "divergence_steps", "reserved", "reserved")
+SCENARIO_METRICS_BOUNDS = ("max_lon_accel", "min_lon_accel", "max_lat_accel", "max_lon_jerk", "max_jerk", "max_yaw_rate", "max_yaw_accel")
+SCENARIO_METRICS_OUTPUTS = ("step", "step_valid", "ttc_slot", "last_episode", "episodes")
+
+
+class MdScenarioMetrics(C.Structure):
+    """include/md_scenario_metrics.h: the sweep's J and period, the thresholds, the strides, agent_light, the outputs, the state rows"""
+    _fields_ = ([("struct_size", C.c_int32), ("ttc_samples", C.c_int32), ("ttc_dt", C.c_float), ("ttc_threshold", C.c_float)] +
+                [(k, C.c_float) for k in SCENARIO_METRICS_BOUNDS] +
+                [("out_stride", C.c_int32), ("state_stride", C.c_int32), ("light_stride", C.c_int32), ("agent_light", P)] +
+                [(k, P) for k in SCENARIO_METRICS_OUTPUTS + ("state", )])
+
+
+def scenario_metrics_blocks(sm_cfg=None):
+    """-> (outputs, output row bytes, state, state row bytes): name -> (byte offset in an env's row, shape after the env axis, numpy
+    dtype), every block 16-byte aligned.  The layout is the same for every config (`sm_cfg` is taken as the sibling *_blocks take
+    theirs).  step_valid, a uint32 of 11 bits in the header, is viewed as int32, torch's own word type.  The state row is the history
+    (MD_SM_STATE_COLS words) with the running episode behind it."""
+    outs, at = {}, 0
+    for name, shape, dt in (("step", (MD_SM_STEP_COLS, ), f4), ("step_valid", (), i4), ("ttc_slot", (), i4),
+                            ("last_episode", (MD_SM_EPISODE_COLS, ), f4), ("episodes", (), i4)):
+        outs[name] = (at, shape, np.dtype(dt))
+        at = (at + int(np.prod(shape)) * 4 + 15) // 16 * 16
+    state = {"history": (0, (MD_SM_STATE_COLS, ), np.dtype(f4)), "episode": (4 * MD_SM_STATE_COLS, (MD_SM_EPISODE_COLS, ), np.dtype(f4))}
+    return outs, at, state, 4 * (MD_SM_STATE_COLS + MD_SM_EPISODE_COLS)
+
+
+def make_md_scenario_metrics(sm_cfg, tensors):
+    """MdScenarioMetrics of the finished config["scenario_metrics"]; `tensors`: out_stride, state_stride, light_stride and name ->
+    address of env 0's block (None / missing: NULL)"""
+    v = MdScenarioMetrics()
+    v.struct_size = C.sizeof(MdScenarioMetrics)
+    v.ttc_samples, v.ttc_dt, v.ttc_threshold = int(sm_cfg["ttc_samples"]), float(sm_cfg["ttc_dt"]), float(sm_cfg["ttc_threshold"])
+    for k in SCENARIO_METRICS_BOUNDS:
+        setattr(v, k, float(sm_cfg[k]))
+    for k in ("out_stride", "state_stride", "light_stride"):
+        setattr(v, k, int(tensors.get(k, 0)))
+    for k in ("agent_light", "state") + SCENARIO_METRICS_OUTPUTS:
+        setattr(v, k, tensors.get(k))
+    return v
+
+
 class MdState(C.Structure):
     _fields_ = [
         ("shape", P), ("dyn", P), ("param", P), ("nav", P), ("pid", P), ("action", P), ("route_nodes", P),
@@ -430,6 +481,8 @@ VECTOR_OBS_ENTRY_POINTS = {"md_vector_obs": (_i, [_W, _S, _K, C.POINTER(MdVector
 SCENARIO_VECTOR_OBS_ENTRY_POINTS = {"md_scenario_vector_obs": (_i, [_W, _S, _K, C.POINTER(MdScenarioVectorObs), P])}
 # include/md_traffic_lights.h: (w, s, c, tl, stream)
 TRAFFIC_LIGHTS_ENTRY_POINTS = {"md_traffic_lights": (_i, [_W, _S, _K, C.POINTER(MdTrafficLights), P])}
+# include/md_scenario_metrics.h: (w, s, c, sm, stream)
+SCENARIO_METRICS_ENTRY_POINTS = {"md_scenario_metrics": (_i, [_W, _S, _K, C.POINTER(MdScenarioMetrics), P])}
 # declared in no header: the hooks of diagnostic (-DMD_STAMP) builds, and md_localize through the lean step's road-first path
 # (the parity tests call it; a -DMD_LOC_ROAD_FIRST=0 build runs the plain walk under that name)
 OPTIONAL_ENTRY_POINTS = {"md_debug_set_stamp_buffer": (_i, [P]), "md_debug_set_env_order": (_i, [P]),

@@ -259,6 +259,48 @@ def check_traffic_lights(user):
     tl["radius"] = float(tl["radius"])
     return tl
 
+
+# BatchedScenarioEnv's closed-loop driving metrics (config scenario_metrics; include/md_scenario_metrics.h).  The reference has no
+# counterpart: every number here is a design choice -- the sweep's sampling, and comfort bounds as planning benchmarks commonly set them.
+SCENARIO_METRICS_DEFAULT_CONFIG = dict(
+    ttc_samples=30,         # J: the sweep tests the samples 0 .. J, 0 .. 64 (MD_SM_MAX_TTC_SAMPLES)
+    ttc_dt=0.1,             # s between two samples
+    ttc_threshold=0.95,     # s: a step with a smaller time to collision counts in ttc_violation_steps
+    max_lon_accel=2.40, min_lon_accel=-4.05,      # m/s^2
+    max_lat_accel=4.89,     # m/s^2, against |lat_accel|
+    max_lon_jerk=4.13,      # m/s^3, against |lon_jerk|
+    max_jerk=8.37,          # m/s^3
+    max_yaw_rate=0.95,      # rad/s, against |yaw_rate|
+    max_yaw_accel=1.93,     # rad/s^2, against |yaw_accel|
+)
+SCENARIO_METRICS_RANGES = dict(ttc_samples=(0, 64))
+
+
+def check_scenario_metrics(user):
+    """config["scenario_metrics"] (a dict) laid over its defaults -> the finished dict; a ValueError names the key at fault"""
+    known = sorted(SCENARIO_METRICS_DEFAULT_CONFIG)
+    if not isinstance(user, dict):
+        raise ValueError("scenario_metrics={!r}: None (off) or a dict of {}".format(user, known))
+    unknown = sorted(set(user) - set(SCENARIO_METRICS_DEFAULT_CONFIG))
+    if unknown:
+        raise ValueError("scenario_metrics: unknown key(s) {} (known: {})".format(unknown, known))
+    sm = dict(SCENARIO_METRICS_DEFAULT_CONFIG, **user)
+    for k, (lo, hi) in SCENARIO_METRICS_RANGES.items():
+        if isinstance(sm[k], bool) or not isinstance(sm[k], int) or not lo <= sm[k] <= hi:
+            raise ValueError("scenario_metrics['{}']={!r}: an int in [{}, {}]".format(k, sm[k], lo, hi))
+    for k in sorted(set(sm) - set(SCENARIO_METRICS_RANGES)):
+        if isinstance(sm[k], bool) or not isinstance(sm[k], (int, float)) or not -1e18 <= sm[k] <= 1e18:     # a NaN fails both
+            raise ValueError("scenario_metrics['{}']={!r}: a finite number".format(k, sm[k]))
+        sm[k] = float(sm[k])
+    if not 0 < sm["ttc_dt"] <= 1e6:
+        raise ValueError("scenario_metrics['ttc_dt']={!r}: a positive number of seconds (at most 1e6)".format(sm["ttc_dt"]))
+    for k in ("max_lon_accel", "max_lat_accel", "max_lon_jerk", "max_jerk", "max_yaw_rate", "max_yaw_accel"):
+        if sm[k] < 0:
+            raise ValueError("scenario_metrics['{}']={!r}: an upper bound, not negative".format(k, sm[k]))
+    if sm["min_lon_accel"] > 0:
+        raise ValueError("scenario_metrics['min_lon_accel']={!r}: a lower bound, not positive".format(sm["min_lon_accel"]))
+    return sm
+
 # The top-down observation envs' own keys (envs/top_down_env.py:12-21,54-61 of the reference): they exist for BatchedTopDownMetaDrive /
 # BatchedTopDownMetaDriveEnvV2 only (make_config(top_down=True)); any other class given one raises KeyError, as the reference's would.
 # norm_pixel is on the cosmetic list below for every other class; for these two it decides the image's dtype.

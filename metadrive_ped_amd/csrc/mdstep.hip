@@ -43,6 +43,7 @@
 #include "md_vector_obs.h"
 #include "md_scenario_vector_obs.h"
 #include "md_traffic_lights.h"
+#include "md_scenario_metrics.h"
 #include "md_lean_pins.h"
 #include "md_lean_view.h"
 #include "md_write_back_own.h"
@@ -2759,6 +2760,7 @@ void scenario_step_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out, in
 #include "parts/vector_obs.inc"   // vector_obs_kernel; md_vector_obs
 #include "parts/scenario_vector_obs.inc" // scenario_vector_obs_kernel; md_scenario_vector_obs (after vector_obs: it reuses vo_agents_block)
 #include "parts/traffic_lights.inc" // traffic_lights_kernel; md_traffic_lights (after vector_obs: it reuses vo_key)
+#include "parts/scenario_metrics.inc" // scenario_metrics_kernel; md_scenario_metrics
 #include "parts/others.inc"       // others_kernel: the observation's "others" block, launched by md_step
 #include "parts/expert.inc"       // expert_kernel, expert_sense_kernel, ai_protect_kernel; md_expert, md_ai_protect, md_expert_sense
 #include "parts/topdown.inc"      // topdown_kernel (its entry point md_topdown stays below: see DESIGN.md section 4)

@@ -64,7 +64,8 @@ enum When : unsigned {
 };
 constexpr int kLidarEntry = 1 << 9, kDetectorEntry = 1 << 10, kExpertEntry = 1 << 11, kPgWalkEntry = 1 << 12, kProtectEntry = 1 << 13,
               kSenseEntry = 1 << 14, kTopDownEntry = 1 << 15, kRenderEntry = 1 << 16, kPedEntry = 1 << 17, kVectorObsEntry = 1 << 18,
-              kContactResponseEntry = 1 << 19, kScenarioVectorObsEntry = 1 << 21, kTrafficLightsEntry = 1 << 22;   // 1 << 20: PH_LOCALIZE_ROAD_FIRST
+              kContactResponseEntry = 1 << 19, kScenarioVectorObsEntry = 1 << 21, kTrafficLightsEntry = 1 << 22,
+              kScenarioMetricsEntry = 1 << 23;   // 1 << 20: PH_LOCALIZE_ROAD_FIRST
 constexpr int kMapPhases = PH_LOCALIZE | PH_CONTACTS | PH_OBSERVE | PH_IDM | PH_LIFECYCLE;
 constexpr int kTrafficPhases = PH_INTEGRATE | PH_TRAFFIC;
 
@@ -114,6 +115,7 @@ const Need kNeeds[] = {
     {kContactResponseEntry, ALWAYS, {FS(shape), FS(dyn), FS(need_reset)}},
     {kScenarioVectorObsEntry, ALWAYS, {FS(shape), FS(dyn), FS(nav), FW(poly_off), FW(segs)}},
     {kTrafficLightsEntry, ALWAYS, {FS(shape), FS(nav)}},
+    {kScenarioMetricsEntry, ALWAYS, {FS(shape), FS(dyn), FS(nav), FS(flags), FS(step_info), FS(track_shape), FS(track_dyn)}},
 };
 #undef FW
 #undef FS

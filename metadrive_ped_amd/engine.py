@@ -588,6 +588,7 @@ class BatchedEngine:
         self._vector_obs_setup()
         self._scenario_vector_obs_setup()
         self._traffic_lights_setup()
+        self._scenario_metrics_setup()
         if getattr(h, "tracks", None) is not None:     # scenario mode: the scenes' recorded frames come with the host scene
             tr = h.tracks
             self.set_tracks(dict(shape=torch.from_numpy(np.ascontiguousarray(tr["shape"]).view(np.uint8).reshape(tr["shape"].shape[0], -1)),
@@ -700,6 +701,39 @@ class BatchedEngine:
         ptrs.update({k: t.data_ptr() for k, t in self.traffic_lights_dev.items()})
         self.traffic_lights_out = views
         self._tl = abi.make_md_traffic_lights(tl, ptrs)
+
+    def _scenario_metrics_setup(self):
+        """The closed-loop driving metrics of scenario mode (config scenario_metrics; include/md_scenario_metrics.h): ONE allocation with
+        one row per env for the output blocks and ONE for the history with the running episode's accumulators
+        (self.scenario_metrics_out: typed views [E, ...] of both).  md_scenario_metrics's arguments, not MdState's or MdWorld's; it reads
+        md_traffic_lights' agent_light where the lights are configured.  self._sm is None, and nothing is allocated, when the key is
+        None."""
+        torch, sm = self.torch, self.cfg.get("scenario_metrics")
+        self._sm = self.scenario_metrics_rows = self.scenario_metrics_state = self.scenario_metrics_out = None
+        if sm is None or not self.cfg.get("scenario_mode"):
+            return
+        outs, out_bytes, state, state_bytes = abi.scenario_metrics_blocks(sm)
+        self.scenario_metrics_rows = torch.zeros((self.E, out_bytes), dtype=torch.uint8, device=self.device)
+        self.scenario_metrics_state = torch.zeros((self.E, state_bytes), dtype=torch.uint8, device=self.device)
+        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.int32): torch.int32}
+        views, ptrs = OrderedDict(), dict(out_stride=out_bytes, state_stride=state_bytes, state=self.scenario_metrics_state.data_ptr())
+        for rows, table in ((self.scenario_metrics_rows, outs), (self.scenario_metrics_state, state)):
+            for name, (off, shape, dt) in table.items():
+                n = int(np.prod(shape)) * dt.itemsize
+                if rows is self.scenario_metrics_rows:
+                    ptrs[name] = rows.data_ptr() + off
+                views[name] = rows[:, off:off + n].view(tdt[dt]).view((self.E, ) + tuple(shape))
+        if self._tl is not None:
+            ptrs.update(agent_light=self.traffic_lights_out["agent_light"].data_ptr(), light_stride=self._tl.out_stride)
+        self.scenario_metrics_out = views
+        self._sm = abi.make_md_scenario_metrics(sm, ptrs)
+
+    def scenario_metrics_forget(self):
+        """Zero the metrics: the step columns, the history, the accumulators, last_episode and episodes (env.reset; env.set_state: a
+        checkpoint does not carry them)"""
+        if self._sm is not None:
+            self.scenario_metrics_rows.zero_()
+            self.scenario_metrics_state.zero_()
 
     def vector_obs_history(self):
         """The vector observation's history as host numpy copies: ring_pose [E, T, cap, 4], ring_flags [E, T, cap], cursor [E, 4]
@@ -820,6 +854,8 @@ class BatchedEngine:
             self._launch("md_scenario_vector_obs", C.byref(self._svo))
         if self._tl is not None:         # the traffic lights, likewise: a walking env's last frame is read on its own scene's lights
             self._launch("md_traffic_lights", C.byref(self._tl))
+        if self._sm is not None:         # the driving metrics: after the lights (they read agent_light), and before an env moves on, so
+            self._launch("md_scenario_metrics", C.byref(self._sm))     # that its last frame is scored on its own scene's SDC track
         # Only now, with the step's observation complete, do the envs whose episode just ended move on: the swap of a walk rewrites
         # MdWorld.env_map, and the detector launches above trace the map of the episode that ended
         if self._cur is not None:        # the scenario walk: the curriculum's step, and the envs whose episode just ended move on

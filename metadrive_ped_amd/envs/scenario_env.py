@@ -77,6 +77,7 @@ class BatchedScenarioEnv(BatchedEnvBase):
     def reset(self, seed=None):
         self.top_down_renderer = None      # BaseEnv.reset clears the top-down renderer (base_env.py:526-528)
         self.lazy_init()
+        self.engine.scenario_metrics_forget()      # last_episode / episodes too: a reset() starts the evaluation afresh
         self.engine.reset()
         return self.engine.obs[:, 0, :], self._info()
 
@@ -143,6 +144,32 @@ class BatchedScenarioEnv(BatchedEnvBase):
         self._require_engine("traffic_light_ids")
         return list(self.engine.host.traffic_light_ids[int(scenario_index)])
 
+    # -- the closed-loop driving metrics (include/md_scenario_metrics.h) ---------------------------------------------------------------
+    def _scenario_metrics_config(self, what):
+        sm = self.config.get("scenario_metrics")
+        if sm is None:
+            raise RuntimeError("{}(): config['scenario_metrics'] is None; give it a dict ({{}} takes the defaults) to turn the driving "
+                               "metrics on".format(what))
+        return sm
+
+    def scenario_metrics_spec(self):
+        """{name: (shape, numpy dtype)} of scenario_metrics()'s tensors, leading axis [E]"""
+        outs, _, state, _ = abi.scenario_metrics_blocks(self._scenario_metrics_config("scenario_metrics_spec"))
+        return {name: ((self.num_envs, ) + tuple(shape), dt.type) for table in (outs, state) for name, (_, shape, dt) in table.items()}
+
+    def scenario_metrics(self):
+        """The driving metrics as the last step() / reset() left them, a dict of device tensors: step [E, 12] (the columns
+        abi.SCENARIO_METRICS_STEP_COLUMNS: divergence from the recorded drive, speed and its finite differences, time to collision,
+        on_red), step_valid [E] int32 (bit i: column i means something), ttc_slot [E] int32 (the mover of the first overlap, -1
+        without one), episode [E, 24] (abi.SCENARIO_METRICS_EPISODE_COLUMNS over the running episode), last_episode [E, 24] (the same
+        of the env's last finished episode, kept through the auto-reset), episodes [E] int32 (how many it has finished since
+        reset()), history [E, 12] (the kernel's own row).  Views of the engine's buffers, valid until the next step() / reset(); no
+        host sync.  step()'s info carries three of them as lazy [E] tensors: log_divergence and time_to_collision (the step columns;
+        0 where step_valid says the column means nothing) and comfortable (the running episode has no comfort violation so far)."""
+        self._scenario_metrics_config("scenario_metrics")
+        self._require_engine("scenario_metrics")
+        return dict(self.engine.scenario_metrics_out)
+
     # -- checkpoints (envs/base_env.py:775-836 get_state / set_state through the managers): a dict of numpy arrays; the routes the
     #    device cut at later spawn frames are state too and travel with it -----------------------------------------------------
     def get_state(self):
@@ -165,6 +192,7 @@ class BatchedScenarioEnv(BatchedEnvBase):
         if "scene_of" in arrays:     # the walk: each env's line map is its scene
             self.engine.world_dev["env_map"].copy_(self.engine.state_dev["scene_of"])
         self.engine.vector_obs_forget()     # a checkpoint does not carry the vector observation's history
+        self.engine.scenario_metrics_forget()   # ... nor the driving metrics
 
     def _info(self):
         e = self.engine
@@ -179,6 +207,11 @@ class BatchedScenarioEnv(BatchedEnvBase):
             al = e.traffic_lights_out["agent_light"]
             lazy.update(green_light=lambda: (al & abi.TL_BIT_GREEN) != 0, yellow_light=lambda: (al & abi.TL_BIT_YELLOW) != 0,
                         red_light=lambda: (al & abi.TL_BIT_RED) != 0)
+        if self.config.get("scenario_metrics") is not None:  # this step's headline metrics, device ops only (scenario_metrics() has the rest)
+            step, col = e.scenario_metrics_out["step"], abi.SCENARIO_METRICS_STEP_COLUMNS.index
+            comfort = e.scenario_metrics_out["episode"][:, abi.SCENARIO_METRICS_EPISODE_COLUMNS.index("comfort_violation_steps")]
+            lazy.update(log_divergence=lambda: step[:, col("log_divergence")], time_to_collision=lambda: step[:, col("ttc")],
+                        comfortable=lambda: comfort == 0)
         if e.host.walk:     # the curriculum's keys (envs/scenario_env.py:279-285), as md_curriculum reported them for this step
             torch = e.torch
             rep_i = e.state_dev["cur_rep_i"].view(torch.int32).view(self.num_envs, 2)

@@ -56,6 +56,10 @@ SCENARIO_DEFAULT_CONFIG = dict(
     # batch behaves as it did before the lights were built; a dict (an empty one too) is laid over
     # config.TRAFFIC_LIGHTS_DEFAULT_CONFIG.  skip_missing_light (envs/scenario_env.py:51) is read only with the key set.
     traffic_lights=None, skip_missing_light=True,
+    # the closed-loop driving metrics (include/md_scenario_metrics.h; no key of the reference's): None = off, no launch, no array and
+    # no info key; a dict (an empty one too) is laid over config.SCENARIO_METRICS_DEFAULT_CONFIG and env.scenario_metrics() returns
+    # the per-step columns, the running episode's accumulators and the last finished episode's report
+    scenario_metrics=None,
 )
 SCENARIO_VEHICLE_CONFIG = dict(lidar=dict(num_lasers=120, distance=50), lane_line_detector=dict(num_lasers=0, distance=50),
                                side_detector=dict(num_lasers=12, distance=50))
@@ -66,7 +70,7 @@ _ONLY_SCENARIO_KEYS = ("data_directory", "start_scenario_index", "sequential_see
                        "no_negative_reward", "crash_human_cost", "relax_out_of_road_done", "allowed_more_steps",
                        "walk_scenarios", "walk_stride", "scenario_pool_max_bytes", "curriculum_level",
                        "episodes_to_evaluate_curriculum", "target_success_rate", "scenario_vector_obs",
-                       "traffic_lights", "skip_missing_light")
+                       "traffic_lights", "skip_missing_light", "scenario_metrics")
 
 STATIC_THRESHOLD = 3.0        # ScenarioTrafficManager.STATIC_THRESHOLD
 IDM_CREATE_MIN_LENGTH = 5.0   # ScenarioTrafficManager.IDM_CREATE_MIN_LENGTH
@@ -127,6 +131,9 @@ def make_scenario_config(user=None):
             raise ValueError("traffic_lights is set together with no_light=True: no_light=True asks for a batch without lights, "
                              "traffic_lights for their tables and flags; drop one of the two")
         cfg["traffic_lights"] = check_traffic_lights(cfg["traffic_lights"])
+    if cfg["scenario_metrics"] is not None:
+        from metadrive_ped_amd.config import check_scenario_metrics
+        cfg["scenario_metrics"] = check_scenario_metrics(cfg["scenario_metrics"])
     if ego_replay:
         cfg["agent_policy"] = "ReplayEgoCarPolicy"
     if cfg["agent_policy"] == "IDMPolicy":
