@@ -31,6 +31,8 @@ __host__ __device__ constexpr TopdownLds topdown_lds(int R, int staged) {
 __host__ __device__ constexpr int topdown_staged(int R, int frame_stack) {
     return topdown_lds(R, frame_stack - 1).bytes <= 64u * 1024u ? frame_stack - 1 : 0;
 }
+// the two sizes tests/test_gpu_topdown_placed.py stands on: the largest staged image, and the first that reads the ring
+static_assert(topdown_staged(128, 18) == 17 && topdown_staged(128, 19) == 0 && topdown_lds(128, 17).bytes == 64512);
 
 struct TdView { float px, py, hc, hs, m, inv_m, half; int R; };
 struct TdBox { int r0, c0, w, h; };

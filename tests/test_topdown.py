@@ -1,5 +1,6 @@
 """The top-down observation's rules (include/md_topdown.h) on their host build, against a float64 numpy restatement written here:
-the window transform, point in rotated rectangle, strip about a segment, straight lanes only.  The restatement also computes how
+the window transform, point in rotated rectangle, strip about a segment, straight lanes as rectangles and circular lanes as annular
+sectors (no cull: every route lane and line piece against every sample).  The restatement also computes how
 far every sample lies from every primitive edge; a pixel is compared only where all its samples keep more than 1e-3 m, and there
 the float32 image must be equal EXACTLY.  The reference's own numbers (its stack indices, the reset observation, the byte values)
 are checked as they are.  This pins the geometry the reference draws, not pygame's pixels."""
@@ -60,21 +61,42 @@ def _rect(px, py, cx, cy, ux, uy, s0, s1, half):
     return inside, near
 
 
-def _points(st, fr, fc):
+def _sector(px, py, cx, cy, radius, start_phase, dirsign, length, half):
+    """(inside, near an edge) of the points against the annular sector of a circular lane, from the geometry: within `half` of the
+    circle of `radius` about (cx, cy), at a phase between start_phase and start_phase + dirsign * length / radius.  Near: within
+    EPS of either bounding circle or of either end radius"""
+    dx, dy = px - cx, py - cy
+    rho = np.hypot(dx, dy)
+    sweep = length / radius
+    assert 0.0 < sweep < 2.0 * np.pi - 0.1 and radius > half
+    t = np.mod(dirsign * (np.arctan2(dy, dx) - start_phase), 2.0 * np.pi)      # the phase travelled from the start, in [0, 2 pi)
+    inside = (np.abs(rho - radius) <= half) & (t <= sweep)
+    tol = EPS / (radius - half)                                                 # EPS of arc at the inner circle, as an angle
+    near = (np.minimum(np.abs(rho - (radius - half)), np.abs(rho - (radius + half))) < EPS) & ((t <= sweep + tol) | (t >= 2.0 * np.pi - tol))
+    for phi in (start_phase, start_phase + dirsign * sweep):                    # the two end radii, as segments
+        ux, uy = np.cos(phi), np.sin(phi)
+        along, across = dx * ux + dy * uy, dx * uy - dy * ux
+        near |= (np.abs(across) < EPS) & (along >= radius - half - EPS) & (along <= radius + half + EPS)
+    return inside, near
+
+
+def _points(st, fr, fc, R=R, dist=DIST):
     """world points of the image coordinates (fr, fc), float64"""
     sh = st["shape"]
     px, py, hc, hs = (float(sh[k][0]) for k in ("cx", "cy", "c", "s"))
-    m = 2.0 * DIST / R
+    m = 2.0 * dist / R
     fwd, left = (R / 2.0 - fr) * m, (R / 2.0 - fc) * m
     return px + fwd * hc - left * hs, py + fwd * hs + left * hc
 
 
-def _restate(host, st):
-    """-> road sum4 [R, R], traffic mask [R, R], comparable [R, R], in float64"""
+def _restate(host, st, R=R, DIST=DIST, arcs=False):
+    """-> road sum4 [R, R], traffic mask [R, R], comparable [R, R], in float64; with arcs also the sub-samples [2R, 2R] on a
+    circular route lane and the sub-samples set.  No cull: every route lane and every line piece against every sub-sample"""
     a = host.world.arrays
     sub = (np.arange(2 * R) + 0.5) / 2.0
-    x, y = _points(st, sub[:, None], sub[None, :])
+    x, y = _points(st, sub[:, None], sub[None, :], R, DIST)
     nav = np.zeros(x.shape, bool)
+    on_arc = np.zeros(x.shape, bool)
     line = np.zeros(x.shape, bool)
     near = np.zeros(x.shape, bool)
     lanes = a["lanes"][int(a["lane_off"][0]):int(a["lane_off"][1])]
@@ -82,8 +104,13 @@ def _restate(host, st):
     n_route = int(st["nav"]["route_len"][0]) - 1
     for rid in st["route_roads"].reshape(-1, abi.MD_ROUTE_LEN)[0][:n_route]:
         for L in lanes[int(roads[rid]["first_lane"]):int(roads[rid]["first_lane"]) + int(roads[rid]["n_lanes"])]:
-            assert L["type"] == 0, "the restatement knows straight lanes only"
-            i, n = _rect(x, y, float(L["ax"]), float(L["ay"]), float(L["bx"]), float(L["by"]), 0.0, float(L["length"]), float(L["width"]) / 2.0)
+            if L["type"] == 0:
+                i, n = _rect(x, y, float(L["ax"]), float(L["ay"]), float(L["bx"]), float(L["by"]), 0.0, float(L["length"]), float(L["width"]) / 2.0)
+            else:
+                assert arcs and L["type"] == 1, "a circular lane in a scene of straight ones"
+                i, n = _sector(x, y, float(L["ax"]), float(L["ay"]), float(L["bx"]), float(L["by"]), float(L["dirsign"]), float(L["length"]),
+                               float(L["width"]) / 2.0)
+                on_arc |= i
             nav |= i
             near |= n
     hw = max(0.3, (2.0 * DIST / R) / 2.0) / 2.0
@@ -105,7 +132,7 @@ def _restate(host, st):
     near_px = near.reshape(R, 2, R, 2).any(axis=(1, 3))
     # traffic: pixel centres
     ctr = np.arange(R) + 0.5
-    x, y = _points(st, ctr[:, None], ctr[None, :])
+    x, y = _points(st, ctr[:, None], ctr[None, :], R, DIST)
     traffic = np.zeros(x.shape, bool)
     sh = st["shape"]
     for j in range(1, host.cap):
@@ -117,6 +144,8 @@ def _restate(host, st):
         i, n = _rect(x, y, float(sh["cx"][j]), float(sh["cy"][j]), np.cos(hd), np.sin(hd), -float(sh["hl"][j]), float(sh["hl"][j]), float(sh["hw"][j]))
         traffic |= i
         near_px |= n
+    if arcs:
+        return sum4, traffic, ~near_px, on_arc, line | nav
     return sum4, traffic, ~near_px
 
 
@@ -130,6 +159,59 @@ def test_image_equals_the_float64_restatement(scene):
     np.testing.assert_array_equal(img[0, :, :, 0][ok], want_road[ok])
     np.testing.assert_array_equal(img[0, :, :, 2][ok], np.where(traffic, TRAFFIC_F32, np.float32(0))[ok])
     assert 0.0 <= img.min() and img.max() <= 1.0
+
+
+ARC_SCENES = [(m, h, r, d) for m in ("O", "C", "X") for h in (0.3, np.pi / 2, 2.2) for r, d in ((84, 30.0), (128, 60.0), (33, 20.0))]
+
+
+def _arc_scene(map_, h, res, dist):
+    """The default config on `map_` after its reset step; the ego moved to the middle of the longest circular lane of its route,
+    0.137 m off the centre line (outwards), heading h; the two vehicles of _scene around it"""
+    cfg = BatchedTopDownMetaDrive(dict(num_envs=1, map=map_, build_workers=1, resolution_size=res, distance=dist)).config
+    host = HostScene(cfg)
+    o = ob.OracleWorld(host)
+    o.reset()
+    st = o.state
+    a = host.world.arrays
+    lanes = a["lanes"][int(a["lane_off"][0]):int(a["lane_off"][1])]
+    roads = a["roads"][int(a["road_off"][0]):int(a["road_off"][1])]
+    route = st["route_roads"].reshape(-1, abi.MD_ROUTE_LEN)[0][:int(st["nav"]["route_len"][0]) - 1]
+    arcs = [L for rid in route for L in lanes[int(roads[rid]["first_lane"]):int(roads[rid]["first_lane"]) + int(roads[rid]["n_lanes"])] if L["type"] == 1]
+    assert arcs, "no circular lane on the route of map %r" % map_
+    L = max(arcs, key=lambda l: float(l["length"]))
+    phi = float(L["by"]) + float(L["dirsign"]) * 0.5 * float(L["length"]) / float(L["bx"])
+    rad = float(L["bx"]) + 0.137
+    sh = st["shape"]
+    sh["cx"][0], sh["cy"][0], sh["c"][0], sh["s"][0] = float(L["ax"]) + rad * np.cos(phi), float(L["ay"]) + rad * np.sin(phi), np.cos(h), np.sin(h)
+    ego = np.array([sh["cx"][0], sh["cy"][0]], np.float64)
+    fwd, left = np.array([np.cos(h), np.sin(h)]), np.array([-np.sin(h), np.cos(h)])
+    for slot, (f, l), hd in ((1, AHEAD_LEFT, 0.45), (2, (-8.0, -3.0), 0.02)):
+        p = ego + f * fwd + l * left
+        sh["cx"][slot], sh["cy"][slot], sh["c"][slot], sh["s"][slot] = p[0], p[1], np.cos(hd), np.sin(hd)
+        sh["hl"][slot], sh["hw"][slot] = 2.2, 0.9
+        sh["flags"][slot] = abi.KIND_VEHICLE | abi.F_ALIVE
+    sh["flags"][3:] = 0
+    return host, st
+
+
+@pytest.mark.parametrize("map_,h,res,dist", ARC_SCENES, ids=["%s-%.1f-%d" % (m, h, r) for m, h, r, _ in ARC_SCENES])
+def test_image_equals_the_float64_restatement_on_arcs(map_, h, res, dist):
+    """md_td_on_lane of a circular lane (md_lane_local: md_atan2, md_wrap_to_pi, the nearer end's phase) against the annular sector
+    written from the geometry, with the ego mid-arc on a circular route lane.  The host build culls lanes and pieces on their
+    bounding boxes, the restatement culls nothing"""
+    host, st = _arc_scene(map_, h, res, dist)
+    img = th.HostTopDown(host, R=res, distance=dist).observe(st)
+    sum4, traffic, ok, on_arc, drawn = _restate(host, st, res, dist, arcs=True)
+    assert img.shape == (1, res, res, 5) and img.dtype == np.float32
+    assert ok.mean() >= 0.98, ok.mean()
+    assert on_arc.sum() >= 200, on_arc.sum()
+    partial = drawn.reshape(res, 2, res, 2).sum(axis=(1, 3))
+    assert (((partial >= 1) & (partial <= 3)) & ok).sum() >= 10      # partly covered pixels are among the compared ones
+    arc_px = on_arc.reshape(res, 2, res, 2).sum(axis=(1, 3))
+    assert (((arc_px >= 1) & (arc_px <= 3)) & ok).sum() >= 5         # ... and so are pixels an arc's edge runs through
+    want_road = np.clip(np.float32(2) * (sum4.astype(np.float32) * np.float32(0.25)) / np.float32(255), 0, 1).astype(np.float32)
+    np.testing.assert_array_equal(img[0, :, :, 0][ok], want_road[ok])
+    np.testing.assert_array_equal(img[0, :, :, 2][ok], np.where(traffic, TRAFFIC_F32, np.float32(0))[ok])
 
 
 def test_orientation_ahead_left_is_upper_left(scene):

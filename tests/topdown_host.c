@@ -64,7 +64,7 @@ EXPORT void hx_topdown(const MdWorld* w, const MdState* g, const MdConfig* c, co
                 /* MdLane.x0 .. y1 is the AABB of the lane's hull, built (mapgen/lanes.py) from a densely sampled outline with tangent
                  * extensions: chords of an arc miss it by centimetres, so 1.0 m is a wide margin.  The kernel culls on the same AABB
                  * with 1.5 m: should the hull ever be sampled coarsely, BOTH margins have to grow, or the two sides would miss the
-                 * same part of an arc and still agree (the float64 restatement of tests/test_topdown.py knows straight lanes only) */
+                 * same part of an arc and still agree (the float64 restatement of tests/test_topdown.py culls nothing and knows arcs) */
                 Box b = {L->x0 - 1.0f, L->y0 - 1.0f, L->x1 + 1.0f, L->y1 + 1.0f, rd->first_lane + l};
                 if (b.x0 > px + reach || b.x1 < px - reach || b.y0 > py + reach || b.y1 < py - reach) continue;
                 lane_box[n_lane++] = b;
