@@ -44,7 +44,7 @@ FL_TRUNCATED = 0x8000
 
 Q_LINE_WHITE_CONT, Q_LINE_YELLOW_CONT, Q_LINE_BROKEN, Q_SIDEWALK, Q_CROSSWALK = 1, 2, 3, 4, 5
 
-f4, i4 = np.float32, np.int32
+f4, i4, u1 = np.float32, np.int32, np.uint8
 
 SHAPE_DT = np.dtype([("cx", f4), ("cy", f4), ("c", f4), ("s", f4), ("hl", f4), ("hw", f4), ("flags", i4), ("aux", i4)])
 DYN_DT = np.dtype([("heading", f4), ("speed", f4), ("steering", f4), ("throttle", f4), ("last_x", f4),
@@ -188,6 +188,33 @@ def make_md_contact_response(contact_response_config):
     return cr
 
 
+def row_blocks(blocks):
+    """The per-env row layout ("Per-env row blocks"): blocks = (name, shape after the env axis, dtype), ... -> (table, row
+    bytes) with table[name] = (byte offset in an env's row, shape, numpy dtype).  Every block starts 16-byte aligned; a block whose
+    count is 0 has no bytes and shares its offset with its successor."""
+    table, at = {}, 0
+    for name, shape, dt in blocks:
+        table[name] = (at, tuple(shape), np.dtype(dt))
+        at = (at + int(np.prod(shape)) * np.dtype(dt).itemsize + 15) // 16 * 16
+    return table, at
+
+
+def block_bytes(table, name):
+    _, shape, dt = table[name]
+    return int(np.prod(shape)) * dt.itemsize
+
+
+def block_ptrs(table, base):
+    """name -> address of env 0's block in rows that start at `base`; a block without bytes is left out (its pointer stays NULL)"""
+    return {name: base + table[name][0] for name in table if block_bytes(table, name)}
+
+
+def block_of(rows, table, name):
+    """a typed copy [E, ...] of the block `name` of the [E, row bytes] uint8 array `rows`"""
+    off, shape, dt = table[name]
+    return rows[:, off:off + block_bytes(table, name)].copy().view(dt).reshape((rows.shape[0], ) + shape)     # (E = 1: a slice is contiguous)
+
+
 # include/md_vector_obs.h: the ceilings MD_VO_MAX_*, and md_vector_obs's argument block
 MD_VO_MAX_AGENTS, MD_VO_MAX_HISTORY, MD_VO_MAX_ROUTE_POINTS, MD_VO_MAX_LANES, MD_VO_MAX_LANE_POINTS = 16, 8, 32, 16, 16
 VECTOR_OBS_OUTPUTS = ("agents", "agents_mask", "agents_meta", "ego", "ego_mask", "route", "route_mask", "lanes", "lanes_meta", "lanes_mask")
@@ -203,23 +230,19 @@ class MdVectorObs(C.Structure):
         [(k, P) for k in VECTOR_OBS_OUTPUTS + VECTOR_OBS_HISTORY]
 
 
+def _history_blocks(T, cap):
+    """the engine-owned history both vector observations keep: the pose ring, the flag ring, the cursor"""
+    return [("ring_pose", (T, cap, 4), f4), ("ring_flags", (T, cap), i4), ("cursor", (4, ), i4)]
+
+
 def vector_obs_blocks(vo_cfg, A, cap):
     """-> (outputs, output row bytes, history, history row bytes); outputs / history: name -> (byte offset in an env's row, shape
-    after the env axis, numpy dtype).  One row per env, every block 16-byte aligned; a block whose count is 0 has no bytes."""
+    after the env axis, numpy dtype), laid out by row_blocks.  One output row and one history row per env."""
     K, T, M, Pn, S = (int(vo_cfg[k]) for k in ("num_agents", "history", "route_points", "num_lanes", "lane_points"))
-    u1 = np.uint8
     outs = [("agents", (A, K, T, 4), f4), ("agents_mask", (A, K, T), u1), ("agents_meta", (A, K, 4), f4), ("ego", (A, T, 4), f4),
             ("ego_mask", (A, T), u1), ("route", (A, M, 4), f4), ("route_mask", (A, M), u1), ("lanes", (A, Pn, S, 2), f4),
             ("lanes_meta", (A, Pn, 4), f4), ("lanes_mask", (A, Pn), u1)]
-    hist = [("ring_pose", (T, cap, 4), f4), ("ring_flags", (T, cap), i4), ("cursor", (4, ), i4)]
-    tables = []
-    for blocks in (outs, hist):
-        table, at = {}, 0
-        for name, shape, dt in blocks:
-            table[name] = (at, shape, np.dtype(dt))
-            at = (at + int(np.prod(shape)) * np.dtype(dt).itemsize + 15) // 16 * 16
-        tables += [table, at]
-    return tuple(tables)
+    return row_blocks(outs) + row_blocks(_history_blocks(T, cap))
 
 
 def make_md_vector_obs(vo_cfg, tensors):
@@ -256,18 +279,9 @@ def scenario_vector_obs_blocks(vo_cfg, cap):
     """-> (outputs, output row bytes, history, history row bytes), like vector_obs_blocks: name -> (byte offset in an env's row, shape
     after the env axis, numpy dtype).  One observer per env, so the shapes have no agent axis."""
     K, T, M, Pn, S = (int(vo_cfg[k]) for k in ("num_agents", "history", "route_points", "num_pieces", "piece_points"))
-    u1 = np.uint8
     outs = [("agents", (K, T, 4), f4), ("agents_mask", (K, T), u1), ("agents_meta", (K, 4), f4), ("ego", (T, 4), f4), ("ego_mask", (T, ), u1),
             ("route", (M, 4), f4), ("route_mask", (M, ), u1), ("map", (Pn, S, 2), f4), ("map_mask", (Pn, S), u1), ("map_meta", (Pn, 4), f4)]
-    hist = [("ring_pose", (T, cap, 4), f4), ("ring_flags", (T, cap), i4), ("cursor", (4, ), i4)]
-    tables = []
-    for blocks in (outs, hist):
-        table, at = {}, 0
-        for name, shape, dt in blocks:
-            table[name] = (at, shape, np.dtype(dt))
-            at = (at + int(np.prod(shape)) * np.dtype(dt).itemsize + 15) // 16 * 16
-        tables += [table, at]
-    return tuple(tables)
+    return row_blocks(outs) + row_blocks(_history_blocks(T, cap))
 
 
 def make_md_scenario_vector_obs(vo_cfg, tensors):
@@ -300,14 +314,10 @@ class MdTrafficLights(C.Structure):
 
 
 def traffic_lights_blocks(tl_cfg):
-    """-> (outputs, output row bytes): name -> (byte offset in an env's row, shape after the env axis, numpy dtype), every block
-    16-byte aligned, like scenario_vector_obs_blocks.  agent_light is one byte per env."""
+    """-> (outputs, output row bytes): name -> (byte offset in an env's row, shape after the env axis, numpy dtype), laid out by
+    row_blocks.  agent_light is one byte per env."""
     L = int(tl_cfg["num_lights"])
-    table, at = {}, 0
-    for name, shape, dt in (("agent_light", (), np.uint8), ("lights", (L, 6), f4), ("lights_mask", (L, ), np.uint8), ("lights_index", (L, ), i4)):
-        table[name] = (at, shape, np.dtype(dt))
-        at = (at + int(np.prod(shape)) * np.dtype(dt).itemsize + 15) // 16 * 16
-    return table, at
+    return row_blocks([("agent_light", (), u1), ("lights", (L, 6), f4), ("lights_mask", (L, ), u1), ("lights_index", (L, ), i4)])
 
 
 def make_md_traffic_lights(tl_cfg, tensors):
@@ -346,16 +356,13 @@ class MdScenarioMetrics(C.Structure):
 
 def scenario_metrics_blocks(sm_cfg=None):
     """-> (outputs, output row bytes, state, state row bytes): name -> (byte offset in an env's row, shape after the env axis, numpy
-    dtype), every block 16-byte aligned.  The layout is the same for every config (`sm_cfg` is taken as the sibling *_blocks take
+    dtype), the outputs laid out by row_blocks.  The layout is the same for every config (`sm_cfg` is taken as the sibling *_blocks take
     theirs).  step_valid, a uint32 of 11 bits in the header, is viewed as int32, torch's own word type.  The state row is the history
     (MD_SM_STATE_COLS words) with the running episode behind it."""
-    outs, at = {}, 0
-    for name, shape, dt in (("step", (MD_SM_STEP_COLS, ), f4), ("step_valid", (), i4), ("ttc_slot", (), i4),
-                            ("last_episode", (MD_SM_EPISODE_COLS, ), f4), ("episodes", (), i4)):
-        outs[name] = (at, shape, np.dtype(dt))
-        at = (at + int(np.prod(shape)) * 4 + 15) // 16 * 16
+    outs = [("step", (MD_SM_STEP_COLS, ), f4), ("step_valid", (), i4), ("ttc_slot", (), i4), ("last_episode", (MD_SM_EPISODE_COLS, ), f4),
+            ("episodes", (), i4)]
     state = {"history": (0, (MD_SM_STATE_COLS, ), np.dtype(f4)), "episode": (4 * MD_SM_STATE_COLS, (MD_SM_EPISODE_COLS, ), np.dtype(f4))}
-    return outs, at, state, 4 * (MD_SM_STATE_COLS + MD_SM_EPISODE_COLS)
+    return row_blocks(outs) + (state, 4 * (MD_SM_STATE_COLS + MD_SM_EPISODE_COLS))
 
 
 def make_md_scenario_metrics(sm_cfg, tensors):

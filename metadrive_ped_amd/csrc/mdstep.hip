@@ -28,6 +28,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <initializer_list>
 #include <type_traits>
 
 #include "md_curriculum.h"
@@ -3115,10 +3116,7 @@ __attribute__((visibility("default"))) int md_step(const MdWorld* w, const MdSta
 __attribute__((visibility("default"))) int md_topdown(const MdWorld* w, const MdState* s, const MdConfig* c, const MdTopDown* td, void* stream) {
     TRY(check_common(w, s, c));
     NEED(td);
-    if (td->struct_size != (int32_t)sizeof(MdTopDown)) {
-        snprintf(g_err, sizeof g_err, "MdTopDown.struct_size=%d, library expects %d", td->struct_size, (int)sizeof(MdTopDown));
-        return MD_EABI;
-    }
+    TRY(check_arg_size("MdTopDown", td->struct_size, sizeof(MdTopDown)));
     NEED(td->out); NEED(td->ring_traffic); NEED(td->ring_pos); NEED(td->cursor);
     TRY(need_fields(kTopDownEntry, ALWAYS, w, s, c));
     if (td->frame_stack < 1 || td->post_stack < 1 || td->frame_skip < 1 || !(td->distance > 0.0f) || td->resolution < 1) {

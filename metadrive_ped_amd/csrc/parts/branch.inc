@@ -61,10 +61,7 @@ extern "C" {
 __attribute__((visibility("default"))) int md_branch(const MdState* dst, const MdState* src, const MdConfig* c, const MdBranch* b, void* stream) {
     NEED(dst); NEED(src); NEED(c); NEED(b);
     TRY(check_struct_size(c));
-    if (b->struct_size != (int32_t)sizeof(MdBranch)) {
-        snprintf(g_err, sizeof g_err, "MdBranch.struct_size=%d, library expects %d", b->struct_size, (int)sizeof(MdBranch));
-        return MD_EABI;
-    }
+    TRY(check_arg_size("MdBranch", b->struct_size, sizeof(MdBranch)));
     NEED(b->src_row); NEED(b->dst_row);
     if (c->cap <= 0 || c->cap > MD_MAX_CAP || c->agents_per_env <= 0 || c->agents_per_env > c->cap || c->obs_dim < 0 ||
         c->route_seg_cap < 0 || c->route_vert_cap < 0) {
@@ -80,10 +77,7 @@ __attribute__((visibility("default"))) int md_branch(const MdState* dst, const M
         snprintf(g_err, sizeof g_err, "md_branch: src_n_envs=%d and dst_n_envs=%d must be positive", b->src_n_envs, b->dst_n_envs);
         return MD_EINVAL;
     }
-    if (b->n_extras < 0 || b->n_extras > MD_BR_MAX_EXTRAS) {
-        snprintf(g_err, sizeof g_err, "md_branch: n_extras=%d must lie in [0, MD_BR_MAX_EXTRAS=%d]", b->n_extras, MD_BR_MAX_EXTRAS);
-        return MD_EINVAL;
-    }
+    TRY(check_counts("md_branch", {{"n_extras", b->n_extras, 0, MD_BR_MAX_EXTRAS, "MD_BR_MAX_EXTRAS"}}));
     for (int k = 0; k < b->n_extras; ++k) {
         if (!b->extra[k].dst || !b->extra[k].src) {
             snprintf(g_err, sizeof g_err, "required pointer b->extra[%d].%s is null", k, b->extra[k].dst ? "src" : "dst");

@@ -111,10 +111,7 @@ extern "C" {
 __attribute__((visibility("default"))) int md_contact_response(const MdState* s, const MdConfig* c, const MdContactResponse* cr, void* stream) {
     NEED(s); NEED(c); NEED(cr);
     TRY(check_struct_size(c));
-    if (cr->struct_size != (int32_t)sizeof(MdContactResponse)) {
-        snprintf(g_err, sizeof g_err, "MdContactResponse.struct_size=%d, library expects %d", cr->struct_size, (int)sizeof(MdContactResponse));
-        return MD_EABI;
-    }
+    TRY(check_arg_size("MdContactResponse", cr->struct_size, sizeof(MdContactResponse)));
     if (c->n_envs <= 0 || c->cap <= 0 || c->cap > MD_MAX_CAP) {
         snprintf(g_err, sizeof g_err, "md_contact_response: bad sizes: n_envs=%d cap=%d (cap<=%d)", c->n_envs, c->cap, MD_MAX_CAP);
         return MD_EINVAL;

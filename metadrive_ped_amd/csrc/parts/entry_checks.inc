@@ -1,24 +1,28 @@
 // parts/entry_checks.inc -- part of mdstep.hip, included there and not compiled on its own.
-// Provides (host only): what every entry point checks its arguments with -- TRY / NEED, check_struct_size, check_common, need,
-// the ONE requirement table kNeeds (a row per entry point and condition) with need_fields -- and launch_status.  It stands before
-// the side features so that each of them keeps its entry point beside its kernel.
+// Provides (host only): what every entry point checks its arguments with -- TRY / NEED, check_arg_size, check_struct_size,
+// check_common, need, the side features' argument-block checks (check_counts, check_lengths, check_stride(s),
+// check_scenario_observer, check_word_aligned), the ONE requirement table kNeeds (a row per entry point and condition) with
+// need_fields -- and launch_status.  It stands before the side features so that each of them keeps its entry point beside its kernel.
 // Relies on: mdstep.hip (g_err, the PH_* bits).
 
 namespace {
 
 // return from the calling entry point unless x is MD_OK
-#define TRY(x)                       \
-    do {                             \
-        const int _r = (x);          \
-        if (_r != MD_OK) return _r;  \
+#define TRY(...)                       \
+    do {                               \
+        const int _r = (__VA_ARGS__);  \
+        if (_r != MD_OK) return _r;    \
     } while (0)
 #define NEED(p) TRY(need((const void*)(p), #p))
 
-int check_struct_size(const MdConfig* c) {
-    if (c->struct_size == (int32_t)sizeof(MdConfig)) return MD_OK;
-    snprintf(g_err, sizeof g_err, "MdConfig.struct_size=%d, library expects %d", c->struct_size, (int)sizeof(MdConfig));
+// an argument block's struct_size against the library's sizeof: `what` is the struct as the message spells it
+int check_arg_size(const char* what, int32_t got, size_t want) {
+    if (got == (int32_t)want) return MD_OK;
+    snprintf(g_err, sizeof g_err, "%s.struct_size=%d, library expects %d", what, got, (int)want);
     return MD_EABI;
 }
+
+int check_struct_size(const MdConfig* c) { return check_arg_size("MdConfig", c->struct_size, sizeof(MdConfig)); }
 
 int check_common(const MdWorld* w, const MdState* s, const MdConfig* c) {
     if (!w || !s || !c) {
@@ -50,6 +54,64 @@ int need(const void* p, const char* name) {
     if (p) return MD_OK;
     snprintf(g_err, sizeof g_err, "required pointer %s is null", name);
     return MD_EINVAL;
+}
+
+// ---- a side feature's own argument block: per-env rows cut into blocks (DESIGN.md, "Per-env row blocks") ----
+// Each returns MD_OK or MD_EINVAL with the first failing row in g_err; `entry` is the entry point's name as the message spells it.
+struct Count { const char* name; int v, lo, hi; const char* limit; };   // lo <= v <= hi, `limit` the ceiling's macro by name
+int check_counts(const char* entry, std::initializer_list<Count> rows) {
+    for (const Count& r : rows)
+        if (r.v < r.lo || r.v > r.hi) {
+            snprintf(g_err, sizeof g_err, "%s: %s=%d must lie in [%d, %s=%d]", entry, r.name, r.v, r.lo, r.limit, r.hi);
+            return MD_EINVAL;
+        }
+    return MD_OK;
+}
+
+struct Length { const char* name; float v; };
+int check_lengths(const char* entry, std::initializer_list<Length> rows) {
+    for (const Length& r : rows)
+        if (!(r.v > 0.0f) || !(r.v <= 1.0e18f)) {      // its square stays finite
+            snprintf(g_err, sizeof g_err, "%s: %s=%g must be positive (and at most 1e18)", entry, r.name, (double)r.v);
+            return MD_EINVAL;
+        }
+    return MD_OK;
+}
+
+// the per-env stride of one row allocation / of the output and history rows of the two vector observations
+int check_stride(const char* entry, int out_stride) {
+    if (out_stride > 0 && out_stride % 16 == 0) return MD_OK;
+    snprintf(g_err, sizeof g_err, "%s: out_stride=%d must be a positive multiple of 16", entry, out_stride);
+    return MD_EINVAL;
+}
+int check_strides(const char* entry, int out_stride, int hist_stride) {
+    if (out_stride > 0 && out_stride % 16 == 0 && hist_stride > 0 && hist_stride % 16 == 0) return MD_OK;
+    snprintf(g_err, sizeof g_err, "%s: out_stride=%d and hist_stride=%d must be positive multiples of 16", entry, out_stride, hist_stride);
+    return MD_EINVAL;
+}
+
+// scenario mode, and its one agent in slot 0 as the observer; `tail` ends the first message
+int check_scenario_observer(const char* entry, const MdConfig* c, const char* tail = "") {
+    if (c->traffic_mode != 4) {
+        snprintf(g_err, sizeof g_err, "%s: only in scenario mode (traffic_mode 4), got traffic_mode %d%s", entry, c->traffic_mode, tail);
+        return MD_EINVAL;
+    }
+    if (c->agents_per_env != 1 || c->is_multi_agent) {
+        snprintf(g_err, sizeof g_err, "%s: agents_per_env=%d is_multi_agent=%d: the observer is the one agent in slot 0", entry,
+                 c->agents_per_env, c->is_multi_agent);
+        return MD_EINVAL;
+    }
+    return MD_OK;
+}
+
+// the arrays the kernel reads or writes by 32-bit words; `what` names them in the message (NULL passes: its block has no bytes)
+int check_word_aligned(const char* entry, const char* what, std::initializer_list<const void*> ptrs) {
+    for (const void* p : ptrs)
+        if ((uintptr_t)p & 3) {
+            snprintf(g_err, sizeof g_err, "%s: %s must be 4-byte aligned", entry, what);
+            return MD_EINVAL;
+        }
+    return MD_OK;
 }
 
 // ---- the MdWorld / MdState pointers each entry point requires ----

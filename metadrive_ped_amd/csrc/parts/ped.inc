@@ -87,10 +87,7 @@ extern "C" {
 __attribute__((visibility("default"))) int md_ped(const MdState* s, const MdConfig* c, const MdPed* p, void* stream) {
     NEED(s); NEED(c); NEED(p);
     TRY(check_struct_size(c));
-    if (p->struct_size != (int32_t)sizeof(MdPed)) {
-        snprintf(g_err, sizeof g_err, "MdPed.struct_size=%d, library expects %d", p->struct_size, (int)sizeof(MdPed));
-        return MD_EABI;
-    }
+    TRY(check_arg_size("MdPed", p->struct_size, sizeof(MdPed)));
     if (c->n_envs <= 0 || c->cap <= 0 || c->cap > MD_MAX_CAP || c->substeps <= 0 || !(c->dt > 0.0f)) {
         snprintf(g_err, sizeof g_err, "md_ped: bad sizes: n_envs=%d cap=%d substeps=%d dt=%g (cap<=%d)", c->n_envs, c->cap, c->substeps,
                  (double)c->dt, MD_MAX_CAP);

@@ -229,10 +229,7 @@ extern "C" {
 __attribute__((visibility("default"))) int md_render(const MdWorld* w, const MdState* s, const MdConfig* c, const MdRender* r, void* stream) {
     TRY(check_common(w, s, c));
     NEED(r);
-    if (r->struct_size != (int32_t)sizeof(MdRender)) {
-        snprintf(g_err, sizeof g_err, "MdRender.struct_size=%d, library expects %d", r->struct_size, (int)sizeof(MdRender));
-        return MD_EABI;
-    }
+    TRY(check_arg_size("MdRender", r->struct_size, sizeof(MdRender)));
     NEED(r->env_ids); NEED(r->out); NEED(r->ring); NEED(r->cursor);
     TRY(need_fields(kRenderEntry, ALWAYS | MULTI, w, s, c));
     if (r->n_render < 1 || r->n_render > 65535) {

@@ -94,16 +94,9 @@ __attribute__((visibility("default"))) int md_scenario_metrics(const MdWorld* w,
                                                               const MdScenarioMetrics* sm, void* stream) {
     NEED(w); NEED(s); NEED(c); NEED(sm);
     TRY(check_struct_size(c));
-    if (sm->struct_size != (int32_t)sizeof(MdScenarioMetrics)) {
-        snprintf(g_err, sizeof g_err, "MdScenarioMetrics.struct_size=%d, library expects %d", sm->struct_size, (int)sizeof(MdScenarioMetrics));
-        return MD_EABI;
-    }
+    TRY(check_arg_size("MdScenarioMetrics", sm->struct_size, sizeof(MdScenarioMetrics)));
     TRY(check_common(w, s, c));
-    if (sm->ttc_samples < 0 || sm->ttc_samples > MD_SM_MAX_TTC_SAMPLES) {
-        snprintf(g_err, sizeof g_err, "md_scenario_metrics: ttc_samples=%d must lie in [0, MD_SM_MAX_TTC_SAMPLES=%d]", sm->ttc_samples,
-                 MD_SM_MAX_TTC_SAMPLES);
-        return MD_EINVAL;
-    }
+    TRY(check_counts("md_scenario_metrics", {{"ttc_samples", sm->ttc_samples, 0, MD_SM_MAX_TTC_SAMPLES, "MD_SM_MAX_TTC_SAMPLES"}}));
     if (!(sm->ttc_dt > 0.0f) || !(sm->ttc_dt <= 1.0e6f)) {
         snprintf(g_err, sizeof g_err, "md_scenario_metrics: ttc_dt=%g must be positive (and at most 1e6)", (double)sm->ttc_dt);
         return MD_EINVAL;
@@ -113,36 +106,21 @@ __attribute__((visibility("default"))) int md_scenario_metrics(const MdWorld* w,
                  c->substeps);
         return MD_EINVAL;
     }
-    if (sm->out_stride <= 0 || sm->out_stride % 16) {
-        snprintf(g_err, sizeof g_err, "md_scenario_metrics: out_stride=%d must be a positive multiple of 16", sm->out_stride);
-        return MD_EINVAL;
-    }
+    TRY(check_stride("md_scenario_metrics", sm->out_stride));
     const int row = 4 * (MD_SM_STATE_COLS + MD_SM_EPISODE_COLS);
     if (sm->state_stride < row || sm->state_stride % 16) {
         snprintf(g_err, sizeof g_err, "md_scenario_metrics: state_stride=%d must be a multiple of 16, at least %d", sm->state_stride, row);
         return MD_EINVAL;
     }
-    if (c->traffic_mode != 4) {
-        snprintf(g_err, sizeof g_err, "md_scenario_metrics: only in scenario mode (traffic_mode 4), got traffic_mode %d", c->traffic_mode);
-        return MD_EINVAL;
-    }
-    if (c->agents_per_env != 1 || c->is_multi_agent) {
-        snprintf(g_err, sizeof g_err, "md_scenario_metrics: agents_per_env=%d is_multi_agent=%d: the observer is the one agent in slot 0",
-                 c->agents_per_env, c->is_multi_agent);
-        return MD_EINVAL;
-    }
+    TRY(check_scenario_observer("md_scenario_metrics", c));
     TRY(need_fields(kScenarioMetricsEntry, ALWAYS, w, s, c));
     NEED(sm->step); NEED(sm->step_valid); NEED(sm->ttc_slot); NEED(sm->last_episode); NEED(sm->episodes); NEED(sm->state);
     if (sm->agent_light && sm->light_stride <= 0) {
         snprintf(g_err, sizeof g_err, "md_scenario_metrics: light_stride=%d must be positive with agent_light set", sm->light_stride);
         return MD_EINVAL;
     }
-    const void* const words[] = {sm->step, sm->step_valid, sm->ttc_slot, sm->last_episode, sm->episodes};
-    for (const void* p : words)
-        if ((uintptr_t)p & 3) {
-            snprintf(g_err, sizeof g_err, "md_scenario_metrics: the output arrays of MdScenarioMetrics must be 4-byte aligned");
-            return MD_EINVAL;
-        }
+    TRY(check_word_aligned("md_scenario_metrics", "the output arrays of MdScenarioMetrics",
+                           {sm->step, sm->step_valid, sm->ttc_slot, sm->last_episode, sm->episodes}));
     if ((uintptr_t)sm->state & 15) {
         snprintf(g_err, sizeof g_err, "md_scenario_metrics: state must be 16-byte aligned");
         return MD_EINVAL;

@@ -172,76 +172,37 @@ __attribute__((visibility("default"))) int md_scenario_vector_obs(const MdWorld*
                                                                  const MdScenarioVectorObs* sv, void* stream) {
     NEED(w); NEED(s); NEED(c); NEED(sv);
     TRY(check_struct_size(c));
-    if (sv->struct_size != (int32_t)sizeof(MdScenarioVectorObs)) {
-        snprintf(g_err, sizeof g_err, "MdScenarioVectorObs.struct_size=%d, library expects %d", sv->struct_size, (int)sizeof(MdScenarioVectorObs));
-        return MD_EABI;
-    }
+    TRY(check_arg_size("MdScenarioVectorObs", sv->struct_size, sizeof(MdScenarioVectorObs)));
     const MdVectorObs* vo = &sv->vo;
-    if (vo->struct_size != (int32_t)sizeof(MdVectorObs)) {
-        snprintf(g_err, sizeof g_err, "MdScenarioVectorObs.vo.struct_size=%d, library expects %d", vo->struct_size, (int)sizeof(MdVectorObs));
-        return MD_EABI;
-    }
+    TRY(check_arg_size("MdScenarioVectorObs.vo", vo->struct_size, sizeof(MdVectorObs)));
     TRY(check_common(w, s, c));
-    const struct { const char* name; int v, lo, hi; const char* limit; } counts[] = {
-        {"num_agents", vo->num_agents, 1, MD_VO_MAX_AGENTS, "MD_VO_MAX_AGENTS"},
-        {"history", vo->history, 1, MD_VO_MAX_HISTORY, "MD_VO_MAX_HISTORY"},
-        {"route_points", vo->route_points, 0, MD_VO_MAX_ROUTE_POINTS, "MD_VO_MAX_ROUTE_POINTS"},
-        {"num_pieces", sv->num_pieces, 0, MD_SVO_MAX_MAP_PIECES, "MD_SVO_MAX_MAP_PIECES"},
-        {"piece_points", sv->piece_points, 2, MD_SVO_MAX_PIECE_POINTS, "MD_SVO_MAX_PIECE_POINTS"},
-    };
-    for (const auto& r : counts)
-        if (r.v < r.lo || r.v > r.hi) {
-            snprintf(g_err, sizeof g_err, "md_scenario_vector_obs: %s=%d must lie in [%d, %s=%d]", r.name, r.v, r.lo, r.limit, r.hi);
-            return MD_EINVAL;
-        }
+    TRY(check_counts("md_scenario_vector_obs", {{"num_agents", vo->num_agents, 1, MD_VO_MAX_AGENTS, "MD_VO_MAX_AGENTS"},
+                             {"history", vo->history, 1, MD_VO_MAX_HISTORY, "MD_VO_MAX_HISTORY"},
+                             {"route_points", vo->route_points, 0, MD_VO_MAX_ROUTE_POINTS, "MD_VO_MAX_ROUTE_POINTS"},
+                             {"num_pieces", sv->num_pieces, 0, MD_SVO_MAX_MAP_PIECES, "MD_SVO_MAX_MAP_PIECES"},
+                             {"piece_points", sv->piece_points, 2, MD_SVO_MAX_PIECE_POINTS, "MD_SVO_MAX_PIECE_POINTS"}}));
     if (vo->num_lanes != 0) {
         snprintf(g_err, sizeof g_err, "md_scenario_vector_obs: vo.num_lanes=%d must be 0 (a scenario has no lane table)", vo->num_lanes);
         return MD_EINVAL;
     }
-    const struct { const char* name; float v; } lengths[] = {{"radius", vo->radius}, {"max_jump", vo->max_jump},
-                                                             {"route_spacing", vo->route_spacing}, {"map_radius", sv->map_radius}};
-    for (const auto& r : lengths)
-        if (!(r.v > 0.0f) || !(r.v <= 1.0e18f)) {      // its square stays finite
-            snprintf(g_err, sizeof g_err, "md_scenario_vector_obs: %s=%g must be positive (and at most 1e18)", r.name, (double)r.v);
-            return MD_EINVAL;
-        }
-    if (vo->out_stride <= 0 || vo->out_stride % 16 || vo->hist_stride <= 0 || vo->hist_stride % 16) {
-        snprintf(g_err, sizeof g_err, "md_scenario_vector_obs: out_stride=%d and hist_stride=%d must be positive multiples of 16", vo->out_stride,
-                 vo->hist_stride);
-        return MD_EINVAL;
-    }
-    if (c->traffic_mode != 4) {
-        snprintf(g_err, sizeof g_err, "md_scenario_vector_obs: only in scenario mode (traffic_mode 4), got traffic_mode %d: md_vector_obs "
-                 "serves the other modes", c->traffic_mode);
-        return MD_EINVAL;
-    }
-    if (c->agents_per_env != 1 || c->is_multi_agent) {
-        snprintf(g_err, sizeof g_err, "md_scenario_vector_obs: agents_per_env=%d is_multi_agent=%d: the observer is the one agent in slot 0",
-                 c->agents_per_env, c->is_multi_agent);
-        return MD_EINVAL;
-    }
+    TRY(check_lengths("md_scenario_vector_obs", {{"radius", vo->radius}, {"max_jump", vo->max_jump}, {"route_spacing", vo->route_spacing},
+                              {"map_radius", sv->map_radius}}));
+    TRY(check_strides("md_scenario_vector_obs", vo->out_stride, vo->hist_stride));
+    TRY(check_scenario_observer("md_scenario_vector_obs", c, ": md_vector_obs serves the other modes"));
     TRY(need_fields(kScenarioVectorObsEntry, ALWAYS, w, s, c));
     NEED(vo->agents); NEED(vo->agents_mask); NEED(vo->agents_meta); NEED(vo->ego); NEED(vo->ego_mask);
     if (vo->route_points > 0) { NEED(vo->route); NEED(vo->route_mask); }
     if (sv->num_pieces > 0) { NEED(sv->map); NEED(sv->map_mask); NEED(sv->map_meta); }
     NEED(vo->ring_pose); NEED(vo->ring_flags); NEED(vo->cursor);
     if (sv->num_pieces > 0) { NEED(sv->map_off); NEED(sv->map_xy); NEED(sv->map_info); NEED(sv->map_ball); }
-    const void* const words[] = {vo->agents, vo->agents_meta, vo->ego, vo->route, sv->map, sv->map_meta, vo->ring_pose, vo->ring_flags,
-                                 vo->cursor, sv->map_off, sv->map_xy, sv->map_info};
-    for (const void* p : words)
-        if ((uintptr_t)p & 3) {
-            snprintf(g_err, sizeof g_err, "md_scenario_vector_obs: the float and int32 arrays of MdScenarioVectorObs must be 4-byte aligned");
-            return MD_EINVAL;
-        }
+    TRY(check_word_aligned("md_scenario_vector_obs", "the float and int32 arrays of MdScenarioVectorObs",
+                           {vo->agents, vo->agents_meta, vo->ego, vo->route, sv->map, sv->map_meta, vo->ring_pose, vo->ring_flags, vo->cursor,
+                            sv->map_off, sv->map_xy, sv->map_info}));
     if ((uintptr_t)sv->map_ball & 15) {
         snprintf(g_err, sizeof g_err, "md_scenario_vector_obs: map_ball must be 16-byte aligned (its records are read whole)");
         return MD_EINVAL;
     }
-    if (sv->max_pieces < 0 || sv->max_pieces > MD_SVO_MAX_PIECES) {
-        snprintf(g_err, sizeof g_err, "md_scenario_vector_obs: max_pieces=%d must lie in [0, MD_SVO_MAX_PIECES=%d]", sv->max_pieces,
-                 MD_SVO_MAX_PIECES);
-        return MD_EINVAL;
-    }
+    TRY(check_counts("md_scenario_vector_obs", {{"max_pieces", sv->max_pieces, 0, MD_SVO_MAX_PIECES, "MD_SVO_MAX_PIECES"}}));
     const size_t lds = scenario_vector_obs_lds(sv->max_pieces).bytes;
     if (lds > 64 * 1024) {
         snprintf(g_err, sizeof g_err, "md_scenario_vector_obs: the candidate lists need %zu B of LDS (max_pieces=%d); limit 65536", lds,

@@ -94,46 +94,17 @@ __attribute__((visibility("default"))) int md_traffic_lights(const MdWorld* w, c
                                                             void* stream) {
     NEED(w); NEED(s); NEED(c); NEED(tl);
     TRY(check_struct_size(c));
-    if (tl->struct_size != (int32_t)sizeof(MdTrafficLights)) {
-        snprintf(g_err, sizeof g_err, "MdTrafficLights.struct_size=%d, library expects %d", tl->struct_size, (int)sizeof(MdTrafficLights));
-        return MD_EABI;
-    }
+    TRY(check_arg_size("MdTrafficLights", tl->struct_size, sizeof(MdTrafficLights)));
     TRY(check_common(w, s, c));
-    const struct { const char* name; int v, hi; const char* limit; } counts[] = {
-        {"num_lights", tl->num_lights, MD_TL_MAX_LIGHTS, "MD_TL_MAX_LIGHTS"},
-        {"max_scene_lights", tl->max_scene_lights, MD_TL_MAX_SCENE_LIGHTS, "MD_TL_MAX_SCENE_LIGHTS"},
-    };
-    for (const auto& r : counts)
-        if (r.v < 0 || r.v > r.hi) {
-            snprintf(g_err, sizeof g_err, "md_traffic_lights: %s=%d must lie in [0, %s=%d]", r.name, r.v, r.limit, r.hi);
-            return MD_EINVAL;
-        }
-    if (!(tl->radius > 0.0f) || !(tl->radius <= 1.0e18f)) {      // its square stays finite
-        snprintf(g_err, sizeof g_err, "md_traffic_lights: radius=%g must be positive (and at most 1e18)", (double)tl->radius);
-        return MD_EINVAL;
-    }
-    if (tl->out_stride <= 0 || tl->out_stride % 16) {
-        snprintf(g_err, sizeof g_err, "md_traffic_lights: out_stride=%d must be a positive multiple of 16", tl->out_stride);
-        return MD_EINVAL;
-    }
-    if (c->traffic_mode != 4) {
-        snprintf(g_err, sizeof g_err, "md_traffic_lights: only in scenario mode (traffic_mode 4), got traffic_mode %d", c->traffic_mode);
-        return MD_EINVAL;
-    }
-    if (c->agents_per_env != 1 || c->is_multi_agent) {
-        snprintf(g_err, sizeof g_err, "md_traffic_lights: agents_per_env=%d is_multi_agent=%d: the observer is the one agent in slot 0",
-                 c->agents_per_env, c->is_multi_agent);
-        return MD_EINVAL;
-    }
+    TRY(check_counts("md_traffic_lights", {{"num_lights", tl->num_lights, 0, MD_TL_MAX_LIGHTS, "MD_TL_MAX_LIGHTS"},
+                                           {"max_scene_lights", tl->max_scene_lights, 0, MD_TL_MAX_SCENE_LIGHTS, "MD_TL_MAX_SCENE_LIGHTS"}}));
+    TRY(check_lengths("md_traffic_lights", {{"radius", tl->radius}}));
+    TRY(check_stride("md_traffic_lights", tl->out_stride));
+    TRY(check_scenario_observer("md_traffic_lights", c));
     TRY(need_fields(kTrafficLightsEntry, ALWAYS, w, s, c));
     NEED(tl->tl_off); NEED(tl->tl_box); NEED(tl->tl_info); NEED(tl->tl_status); NEED(tl->agent_light);
     if (tl->num_lights > 0) { NEED(tl->lights); NEED(tl->lights_mask); NEED(tl->lights_index); }
-    const void* const words[] = {tl->tl_off, tl->lights, tl->lights_index};
-    for (const void* p : words)
-        if ((uintptr_t)p & 3) {
-            snprintf(g_err, sizeof g_err, "md_traffic_lights: the float and int32 arrays of MdTrafficLights must be 4-byte aligned");
-            return MD_EINVAL;
-        }
+    TRY(check_word_aligned("md_traffic_lights", "the float and int32 arrays of MdTrafficLights", {tl->tl_off, tl->lights, tl->lights_index}));
     if (((uintptr_t)tl->tl_box & 15) || ((uintptr_t)tl->tl_info & 15)) {
         snprintf(g_err, sizeof g_err, "md_traffic_lights: %s must be 16-byte aligned (its records are read whole)",
                  ((uintptr_t)tl->tl_box & 15) ? "tl_box" : "tl_info");

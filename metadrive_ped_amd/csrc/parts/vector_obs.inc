@@ -201,35 +201,15 @@ __attribute__((visibility("default"))) int md_vector_obs(const MdWorld* w, const
                                                         void* stream) {
     NEED(w); NEED(s); NEED(c); NEED(vo);
     TRY(check_struct_size(c));
-    if (vo->struct_size != (int32_t)sizeof(MdVectorObs)) {
-        snprintf(g_err, sizeof g_err, "MdVectorObs.struct_size=%d, library expects %d", vo->struct_size, (int)sizeof(MdVectorObs));
-        return MD_EABI;
-    }
+    TRY(check_arg_size("MdVectorObs", vo->struct_size, sizeof(MdVectorObs)));
     TRY(check_common(w, s, c));
-    const struct { const char* name; int v, lo, hi; const char* limit; } counts[] = {
-        {"num_agents", vo->num_agents, 1, MD_VO_MAX_AGENTS, "MD_VO_MAX_AGENTS"},
-        {"history", vo->history, 1, MD_VO_MAX_HISTORY, "MD_VO_MAX_HISTORY"},
-        {"route_points", vo->route_points, 0, MD_VO_MAX_ROUTE_POINTS, "MD_VO_MAX_ROUTE_POINTS"},
-        {"num_lanes", vo->num_lanes, 0, MD_VO_MAX_LANES, "MD_VO_MAX_LANES"},
-        {"lane_points", vo->lane_points, 2, MD_VO_MAX_LANE_POINTS, "MD_VO_MAX_LANE_POINTS"},
-    };
-    for (const auto& r : counts)
-        if (r.v < r.lo || r.v > r.hi) {
-            snprintf(g_err, sizeof g_err, "md_vector_obs: %s=%d must lie in [%d, %s=%d]", r.name, r.v, r.lo, r.limit, r.hi);
-            return MD_EINVAL;
-        }
-    const struct { const char* name; float v; } lengths[] = {{"radius", vo->radius}, {"max_jump", vo->max_jump},
-                                                             {"route_spacing", vo->route_spacing}};
-    for (const auto& r : lengths)
-        if (!(r.v > 0.0f) || !(r.v <= 1.0e18f)) {      // its square stays finite
-            snprintf(g_err, sizeof g_err, "md_vector_obs: %s=%g must be positive (and at most 1e18)", r.name, (double)r.v);
-            return MD_EINVAL;
-        }
-    if (vo->out_stride <= 0 || vo->out_stride % 16 || vo->hist_stride <= 0 || vo->hist_stride % 16) {
-        snprintf(g_err, sizeof g_err, "md_vector_obs: out_stride=%d and hist_stride=%d must be positive multiples of 16", vo->out_stride,
-                 vo->hist_stride);
-        return MD_EINVAL;
-    }
+    TRY(check_counts("md_vector_obs", {{"num_agents", vo->num_agents, 1, MD_VO_MAX_AGENTS, "MD_VO_MAX_AGENTS"},
+                                       {"history", vo->history, 1, MD_VO_MAX_HISTORY, "MD_VO_MAX_HISTORY"},
+                                       {"route_points", vo->route_points, 0, MD_VO_MAX_ROUTE_POINTS, "MD_VO_MAX_ROUTE_POINTS"},
+                                       {"num_lanes", vo->num_lanes, 0, MD_VO_MAX_LANES, "MD_VO_MAX_LANES"},
+                                       {"lane_points", vo->lane_points, 2, MD_VO_MAX_LANE_POINTS, "MD_VO_MAX_LANE_POINTS"}}));
+    TRY(check_lengths("md_vector_obs", {{"radius", vo->radius}, {"max_jump", vo->max_jump}, {"route_spacing", vo->route_spacing}}));
+    TRY(check_strides("md_vector_obs", vo->out_stride, vo->hist_stride));
     if (c->traffic_mode == 4) {
         snprintf(g_err, sizeof g_err, "md_vector_obs: not in scenario mode (traffic_mode 4): it has no lane table and its routes are polylines");
         return MD_EINVAL;
@@ -239,13 +219,8 @@ __attribute__((visibility("default"))) int md_vector_obs(const MdWorld* w, const
     if (vo->route_points > 0) { NEED(vo->route); NEED(vo->route_mask); }
     if (vo->num_lanes > 0) { NEED(vo->lanes); NEED(vo->lanes_meta); NEED(vo->lanes_mask); }
     NEED(vo->ring_pose); NEED(vo->ring_flags); NEED(vo->cursor);
-    const void* const words[] = {vo->agents, vo->agents_meta, vo->ego, vo->route, vo->lanes, vo->lanes_meta, vo->ring_pose, vo->ring_flags,
-                                 vo->cursor};
-    for (const void* p : words)
-        if ((uintptr_t)p & 3) {
-            snprintf(g_err, sizeof g_err, "md_vector_obs: the float and int32 arrays of MdVectorObs must be 4-byte aligned");
-            return MD_EINVAL;
-        }
+    TRY(check_word_aligned("md_vector_obs", "the float and int32 arrays of MdVectorObs",
+                           {vo->agents, vo->agents_meta, vo->ego, vo->route, vo->lanes, vo->lanes_meta, vo->ring_pose, vo->ring_flags, vo->cursor}));
     if (w->n_maps <= 0 || w->max_lanes <= 0) {
         snprintf(g_err, sizeof g_err, "md_vector_obs: MdWorld.n_maps=%d max_lanes=%d", w->n_maps, w->max_lanes);
         return MD_EINVAL;

@@ -418,6 +418,8 @@ class _NullCtx:
 
 
 _NULL_CTX = _NullCtx()
+# the row blocks' numpy dtypes -> the torch dtype of their views, by name (torch is imported with the first engine)
+_TORCH_DTYPE = {np.dtype(np.float32): "float32", np.dtype(np.int32): "int32", np.dtype(np.uint8): "uint8"}
 
 
 def _ptr(t):
@@ -619,60 +621,51 @@ class BatchedEngine:
             setattr(td, k, t.data_ptr())
         self._td = td
 
+    def _row_blocks(self, table, row_bytes):
+        """One zeroed [E, row_bytes] uint8 device tensor laid out by `table` (abi.row_blocks) -> (the tensor, name -> typed view
+        [E, ...] of its block, name -> device address of env 0's block).  A block without bytes has an empty view and no address."""
+        rows = self.torch.zeros((self.E, row_bytes), dtype=self.torch.uint8, device=self.device)
+        views = OrderedDict()
+        for name, (off, shape, dt) in table.items():
+            block = rows[:, off:off + abi.block_bytes(table, name)]
+            views[name] = block.view(getattr(self.torch, _TORCH_DTYPE[dt])).view((self.E, ) + shape)
+        return rows, views, abi.block_ptrs(table, rows.data_ptr())
+
     def _vector_obs_setup(self):
         """The vector scene observation (config vector_obs; include/md_vector_obs.h): TWO allocations with one row per env -- the ten
         output blocks, and the engine-owned history (pose ring, flag ring, cursor) -- md_vector_obs's arguments, not MdState's.
         self.vector_obs_out holds the blocks as typed views [E, A, ...] of the output rows.  All None when the key is None."""
-        torch, vo = self.torch, self.cfg.get("vector_obs")
+        vo = self.cfg.get("vector_obs")
         self._vo = self.vector_obs_out = self.vector_obs_rows = self.vector_obs_hist = None
         if vo is None:
             return
         if self.cfg.get("scenario_mode"):
             raise NotImplementedError("vector_obs is not built for BatchedScenarioEnv")
         outs, out_bytes, hist, hist_bytes = abi.vector_obs_blocks(vo, self.A, self.cap)
-        self.vector_obs_rows = torch.zeros((self.E, out_bytes), dtype=torch.uint8, device=self.device)
-        self.vector_obs_hist = torch.zeros((self.E, hist_bytes), dtype=torch.uint8, device=self.device)
-        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32}
-        views, ptrs = OrderedDict(), dict(out_stride=out_bytes, hist_stride=hist_bytes)
-        for table, rows, into in ((outs, self.vector_obs_rows, views), (hist, self.vector_obs_hist, None)):
-            for name, (off, shape, dt) in table.items():
-                n = int(np.prod(shape)) * dt.itemsize
-                if n:                       # a block whose count is 0 has no bytes: its pointer stays NULL, its view is empty
-                    ptrs[name] = rows.data_ptr() + off
-                if into is not None:
-                    into[name] = rows[:, off:off + n].view(tdt[dt]).view((self.E, ) + tuple(shape))
-        self.vector_obs_out = views
+        self.vector_obs_rows, self.vector_obs_out, ptrs = self._row_blocks(outs, out_bytes)
+        self.vector_obs_hist, _, hist_ptrs = self._row_blocks(hist, hist_bytes)
         self._vo_blocks = (outs, hist)
-        self._vo = abi.make_md_vector_obs(vo, ptrs)
+        self._vo = abi.make_md_vector_obs(vo, dict(ptrs, out_stride=out_bytes, hist_stride=hist_bytes, **hist_ptrs))
 
     def _scenario_vector_obs_setup(self):
         """The vector scene observation of scenario mode (config scenario_vector_obs; include/md_scenario_vector_obs.h): the same TWO
         allocations with one row per env as _vector_obs_setup makes -- the ten output blocks (self.vector_obs_out: typed views [E, ...]),
         and the engine-owned history -- plus the per-scene map piece table the host scene built (ScenarioHostScene.map_pieces),
         uploaded once.  md_scenario_vector_obs's arguments, not MdState's or MdWorld's.  self._svo is None when the key is None."""
-        torch, vo = self.torch, self.cfg.get("scenario_vector_obs")
+        vo = self.cfg.get("scenario_vector_obs")
         self._svo = self.scenario_map_dev = None
         if vo is None:
             return
         outs, out_bytes, hist, hist_bytes = abi.scenario_vector_obs_blocks(vo, self.cap)
-        self.vector_obs_rows = torch.zeros((self.E, out_bytes), dtype=torch.uint8, device=self.device)
-        self.vector_obs_hist = torch.zeros((self.E, hist_bytes), dtype=torch.uint8, device=self.device)
-        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32}
-        views, ptrs = OrderedDict(), dict(out_stride=out_bytes, hist_stride=hist_bytes, max_pieces=0)
-        for table, rows, into in ((outs, self.vector_obs_rows, views), (hist, self.vector_obs_hist, None)):
-            for name, (off, shape, dt) in table.items():
-                n = int(np.prod(shape)) * dt.itemsize
-                if n:                       # a block whose count is 0 has no bytes: its pointer stays NULL, its view is empty
-                    ptrs[name] = rows.data_ptr() + off
-                if into is not None:
-                    into[name] = rows[:, off:off + n].view(tdt[dt]).view((self.E, ) + tuple(shape))
+        self.vector_obs_rows, self.vector_obs_out, ptrs = self._row_blocks(outs, out_bytes)
+        self.vector_obs_hist, _, hist_ptrs = self._row_blocks(hist, hist_bytes)
+        ptrs.update(hist_ptrs, out_stride=out_bytes, hist_stride=hist_bytes, max_pieces=0)
         pieces = getattr(self.host, "map_pieces", None)
         if int(vo["num_pieces"]) > 0:
             if pieces is None:
                 raise RuntimeError("scenario_vector_obs: the host scene carries no map piece table (it was built without the key)")
             self.scenario_map_dev = {k: self._to_dev(pieces[k]) for k in abi.SCENARIO_VECTOR_OBS_TABLES}
             ptrs.update({k: t.data_ptr() for k, t in self.scenario_map_dev.items()}, max_pieces=pieces["max_pieces"])
-        self.vector_obs_out = views
         self._vo_blocks = (outs, hist)
         self._svo = abi.make_md_scenario_vector_obs(vo, ptrs)
 
@@ -681,7 +674,7 @@ class BatchedEngine:
         for the four output blocks (self.traffic_lights_out: typed views [E, ...]) and the per-scene light tables the host scene built
         (ScenarioHostScene.traffic_lights), uploaded once.  md_traffic_lights's arguments, not MdState's or MdWorld's.  self._tl is
         None, and nothing is allocated, when the key is None."""
-        torch, tl = self.torch, self.cfg.get("traffic_lights")
+        tl = self.cfg.get("traffic_lights")
         self._tl = self.traffic_lights_rows = self.traffic_lights_out = self.traffic_lights_dev = None
         if tl is None or not self.cfg.get("scenario_mode"):
             return
@@ -689,17 +682,10 @@ class BatchedEngine:
         if tables is None:
             raise RuntimeError("traffic_lights: the host scene carries no light tables (it was built without the key)")
         outs, out_bytes = abi.traffic_lights_blocks(tl)
-        self.traffic_lights_rows = torch.zeros((self.E, out_bytes), dtype=torch.uint8, device=self.device)
-        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32}
-        views, ptrs = OrderedDict(), dict(out_stride=out_bytes, max_scene_lights=tables["max_scene_lights"])
-        for name, (off, shape, dt) in outs.items():
-            n = int(np.prod(shape)) * dt.itemsize
-            if n:                       # L = 0: the lights blocks have no bytes, their pointers stay NULL, their views are empty
-                ptrs[name] = self.traffic_lights_rows.data_ptr() + off
-            views[name] = self.traffic_lights_rows[:, off:off + n].view(tdt[dt]).view((self.E, ) + tuple(shape))
+        self.traffic_lights_rows, self.traffic_lights_out, ptrs = self._row_blocks(outs, out_bytes)
         self.traffic_lights_dev = {k: self._to_dev(tables[k]) for k in abi.TRAFFIC_LIGHTS_TABLES}
-        ptrs.update({k: t.data_ptr() for k, t in self.traffic_lights_dev.items()})
-        self.traffic_lights_out = views
+        ptrs.update({k: t.data_ptr() for k, t in self.traffic_lights_dev.items()}, out_stride=out_bytes,
+                    max_scene_lights=tables["max_scene_lights"])
         self._tl = abi.make_md_traffic_lights(tl, ptrs)
 
     def _scenario_metrics_setup(self):
@@ -708,24 +694,17 @@ class BatchedEngine:
         (self.scenario_metrics_out: typed views [E, ...] of both).  md_scenario_metrics's arguments, not MdState's or MdWorld's; it reads
         md_traffic_lights' agent_light where the lights are configured.  self._sm is None, and nothing is allocated, when the key is
         None."""
-        torch, sm = self.torch, self.cfg.get("scenario_metrics")
+        sm = self.cfg.get("scenario_metrics")
         self._sm = self.scenario_metrics_rows = self.scenario_metrics_state = self.scenario_metrics_out = None
         if sm is None or not self.cfg.get("scenario_mode"):
             return
         outs, out_bytes, state, state_bytes = abi.scenario_metrics_blocks(sm)
-        self.scenario_metrics_rows = torch.zeros((self.E, out_bytes), dtype=torch.uint8, device=self.device)
-        self.scenario_metrics_state = torch.zeros((self.E, state_bytes), dtype=torch.uint8, device=self.device)
-        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.int32): torch.int32}
-        views, ptrs = OrderedDict(), dict(out_stride=out_bytes, state_stride=state_bytes, state=self.scenario_metrics_state.data_ptr())
-        for rows, table in ((self.scenario_metrics_rows, outs), (self.scenario_metrics_state, state)):
-            for name, (off, shape, dt) in table.items():
-                n = int(np.prod(shape)) * dt.itemsize
-                if rows is self.scenario_metrics_rows:
-                    ptrs[name] = rows.data_ptr() + off
-                views[name] = rows[:, off:off + n].view(tdt[dt]).view((self.E, ) + tuple(shape))
+        self.scenario_metrics_rows, self.scenario_metrics_out, ptrs = self._row_blocks(outs, out_bytes)
+        self.scenario_metrics_state, state_views, _ = self._row_blocks(state, state_bytes)
+        self.scenario_metrics_out.update(state_views)
+        ptrs.update(out_stride=out_bytes, state_stride=state_bytes, state=self.scenario_metrics_state.data_ptr())
         if self._tl is not None:
             ptrs.update(agent_light=self.traffic_lights_out["agent_light"].data_ptr(), light_stride=self._tl.out_stride)
-        self.scenario_metrics_out = views
         self._sm = abi.make_md_scenario_metrics(sm, ptrs)
 
     def scenario_metrics_forget(self):
@@ -739,8 +718,7 @@ class BatchedEngine:
         """The vector observation's history as host numpy copies: ring_pose [E, T, cap, 4], ring_flags [E, T, cap], cursor [E, 4]
         (the tests compare them)"""
         rows = self.vector_obs_hist.cpu().numpy()
-        return {name: rows[:, off:off + int(np.prod(shape)) * dt.itemsize].copy().view(dt).reshape((self.E, ) + tuple(shape))
-                for name, (off, shape, dt) in self._vo_blocks[1].items()}
+        return {name: abi.block_of(rows, self._vo_blocks[1], name) for name in self._vo_blocks[1]}
 
     def vector_obs_forget(self):
         """Empty every env's history (env.set_state: a checkpoint does not carry it, like the renderer's)"""

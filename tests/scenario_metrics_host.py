@@ -7,10 +7,9 @@ import math
 import numpy as np
 
 import hostlib
+from hostlib import put     # noqa: F401  (the tests reach it through this module)
 from metadrive_ped_amd import abi
 from metadrive_ped_amd.config import check_scenario_metrics
-from scenario_vector_obs_host import put     # noqa: F401  (a mover into a slot of a hand-built state)
-from scenario_vector_obs_host import structs_of as _structs_of
 
 _W, _S, _K, _M = C.POINTER(abi.MdWorld), C.POINTER(abi.MdState), C.POINTER(abi.MdConfig), C.POINTER(abi.MdScenarioMetrics)
 OUTPUTS = abi.SCENARIO_METRICS_OUTPUTS
@@ -34,24 +33,18 @@ class HostScenarioMetrics:
     def __init__(self, sm_cfg, E, lights=False):
         self.cfg = check_scenario_metrics(dict(sm_cfg))
         self.E = E
-        self.outs, out_bytes, self.state_blocks, state_bytes = abi.scenario_metrics_blocks(self.cfg)
-        self.rows = np.zeros((E, out_bytes), np.uint8)
-        self.state = np.zeros((E, state_bytes), np.uint8)
+        outs, out_bytes, state, state_bytes = abi.scenario_metrics_blocks(self.cfg)
+        self._out, self._state = hostlib.HostRows(outs, out_bytes, E), hostlib.HostRows(state, state_bytes, E)
+        self.rows, self.state = self._out.rows, self._state.rows
         self.agent_light = np.zeros(E, np.uint8)
-        ptrs = dict(out_stride=out_bytes, state_stride=state_bytes, state=self.state.ctypes.data)
-        ptrs.update({name: self.rows.ctypes.data + off for name, (off, _, _) in self.outs.items()})
+        ptrs = dict(self._out.ptrs(), out_stride=out_bytes, state_stride=state_bytes, state=self.state.ctypes.data)
         if lights:
             ptrs.update(agent_light=self.agent_light.ctypes.data, light_stride=1)
         self.sm = abi.make_md_scenario_metrics(self.cfg, ptrs)
 
-    def _block(self, rows, table, name):
-        off, shape, dt = table[name]
-        n = int(np.prod(shape)) * dt.itemsize
-        return rows[:, off:off + n].copy().view(dt).reshape((self.E, ) + tuple(shape))      # (one env's slice is contiguous as it is)
-
     def out(self, name):
         """a copy of the block `name`, [E, ...]: an output, or "episode" / "history" of the state rows"""
-        return self._block(self.rows, self.outs, name) if name in self.outs else self._block(self.state, self.state_blocks, name)
+        return (self._out if name in self._out.table else self._state).out(name)
 
     def outputs(self):
         return {name: self.out(name) for name in OUTPUTS + ("episode", "history")}
@@ -70,7 +63,7 @@ def structs_of(host, state):
     the walk in MdState as the engine sets them"""
     tr = host.tracks
     seen = dict(state, track_shape=np.ascontiguousarray(tr["shape"]), track_dyn=np.ascontiguousarray(tr["dyn"], np.float32))
-    w, s, k, keep = _structs_of(host, seen)
+    w, s, k, keep = hostlib.structs_of(host, seen)
     s.walk = abi.MdWalk(*host.walk_params)
     assert k.track_len == tr["shape"].shape[0]
     return w, s, k, keep
@@ -81,15 +74,7 @@ def metrics_world(cap=8, T=16):
     st = dict(shape=np.zeros(cap, abi.SHAPE_DT), dyn=np.zeros(cap, abi.DYN_DT), nav=np.zeros(cap, abi.NAV_DT), flags=np.zeros(cap, np.uint32),
               step_info=np.zeros((1, 8), np.float32), track_shape=np.zeros((T, cap), abi.SHAPE_DT), track_dyn=np.zeros((T, cap, 2), np.float32))
     st["nav"]["lane"] = -1
-    w = abi.MdWorld()
-    w.n_maps, w.n_envs = 1, 1
-    s = abi.MdState()
-    for k, v in st.items():
-        setattr(s, k, hostlib.ptr(v))
-    k = abi.MdConfig()
-    k.struct_size, k.n_envs, k.agents_per_env, k.cap, k.traffic_mode = C.sizeof(abi.MdConfig), 1, 1, cap, 4
-    k.dt, k.substeps, k.scenario_length, k.track_len = DT, SUBSTEPS, T, T
-    s.keep_alive = st       # the struct holds bare addresses
+    w, s, k = hostlib.hand_built_structs({}, st, cap=cap, traffic_mode=4, dt=DT, substeps=SUBSTEPS, scenario_length=T, track_len=T)
     return w, s, k, st
 
 

@@ -3,11 +3,11 @@ include/md_scenario_vector_obs.h) on numpy arrays, and what the scenario vector-
 rows with the piece tables, the structs over a host scene, hand-built one-trajectory worlds for the known answers, and a numpy float32
 restatement of the map selection.  TEST INFRASTRUCTURE."""
 import ctypes as C
-import math
 
 import numpy as np
 
 import hostlib
+from hostlib import put, structs_of     # noqa: F401  (the tests reach them through this module)
 from metadrive_ped_amd import abi
 from metadrive_ped_amd.config import check_scenario_vector_obs
 from metadrive_ped_amd.scenario import map_piece_tables
@@ -33,50 +33,30 @@ class HostScenarioVectorObs:
     def __init__(self, vo_cfg, E, cap, pieces=None):
         self.cfg = check_scenario_vector_obs(dict(vo_cfg))
         self.E = E
-        self.outs, out_bytes, self.hists, hist_bytes = abi.scenario_vector_obs_blocks(self.cfg, cap)
-        self.rows = np.zeros((E, out_bytes), np.uint8)
-        self.hist = np.zeros((E, hist_bytes), np.uint8)
-        ptrs = dict(out_stride=out_bytes, hist_stride=hist_bytes, max_pieces=0)
-        for table, rows in ((self.outs, self.rows), (self.hists, self.hist)):
-            for name, (off, shape, dt) in table.items():
-                if int(np.prod(shape)):
-                    ptrs[name] = rows.ctypes.data + off
+        outs, out_bytes, hists, hist_bytes = abi.scenario_vector_obs_blocks(self.cfg, cap)
+        self._out, self._hist = hostlib.HostRows(outs, out_bytes, E), hostlib.HostRows(hists, hist_bytes, E)
+        self.rows, self.hist = self._out.rows, self._hist.rows
+        ptrs = dict(self._out.ptrs(), out_stride=out_bytes, hist_stride=hist_bytes, max_pieces=0, **self._hist.ptrs())
         self.pieces = pieces
         if pieces is not None and self.cfg["num_pieces"] > 0:
             self._keep = {k: np.ascontiguousarray(pieces[k]) for k in abi.SCENARIO_VECTOR_OBS_TABLES}
             ptrs.update({k: v.ctypes.data for k, v in self._keep.items()}, max_pieces=pieces["max_pieces"])
         self.sv = abi.make_md_scenario_vector_obs(self.cfg, ptrs)
 
-    @staticmethod
-    def _block(rows, table, name):
-        off, shape, dt = table[name]
-        n = int(np.prod(shape)) * dt.itemsize
-        return np.ascontiguousarray(rows[:, off:off + n]).view(dt).reshape((rows.shape[0], ) + tuple(shape))
-
     def out(self, name):
         """a copy of the block `name`, [E, ...]"""
-        return self._block(self.rows, self.outs, name)
+        return self._out.out(name)
 
     def outputs(self):
-        return {name: self.out(name) for name in OUTPUTS}
+        return self._out.outs()
 
     def history(self):
-        return {name: self._block(self.hist, self.hists, name) for name in HISTORY}
+        return self._hist.outs()
 
     def run(self, w, s, k):
         """one md_scenario_vector_obs call on host arrays"""
         assert lib().hx_scenario_vector_obs(C.byref(w), C.byref(s), C.byref(k), C.byref(self.sv)) == 0
         return self
-
-
-def structs_of(host, state):
-    """(MdWorld, MdState, MdConfig, keep-alive) over the host scene's tables and the numpy state `state` (the oracle's, or one
-    downloaded from the device)"""
-    from metadrive_ped_amd.engine import make_structs
-    wa = dict(host.world.arrays, **host.world_scalars())
-    state = {k: np.ascontiguousarray(v) for k, v in state.items()}
-    w, s, k = make_structs(wa, state, host.md_config, host.world.n_maps, host.E, hostlib.ptr)
-    return w, s, k, (wa, state)
 
 
 # -- hand-built worlds: ONE env whose reference trajectory is the polyline through `points`, the observer in slot 0 ------------------
@@ -86,24 +66,8 @@ def trajectory_world(points, cap=8):
     world = dict(poly_off=np.asarray([0, len(segs)] + [len(segs)] * (cap - 1), np.int32), segs=segs)
     st = dict(shape=np.zeros(cap, abi.SHAPE_DT), dyn=np.zeros(cap, abi.DYN_DT), nav=np.zeros(cap, abi.NAV_DT))
     st["nav"]["lane"] = -1
-    w = abi.MdWorld()
-    w.n_maps, w.n_envs = 1, 1
-    for k, v in world.items():
-        setattr(w, k, hostlib.ptr(v))
-    s = abi.MdState()
-    for k, v in st.items():
-        setattr(s, k, hostlib.ptr(v))
-    k = abi.MdConfig()
-    k.struct_size, k.n_envs, k.agents_per_env, k.cap, k.traffic_mode = C.sizeof(abi.MdConfig), 1, 1, cap, 4
-    w.keep_alive, s.keep_alive = world, st       # the structs hold bare addresses
+    w, s, k = hostlib.hand_built_structs(world, st, cap=cap, traffic_mode=4)
     return w, s, k, st, world
-
-
-def put(st, slot, x, y, heading=0.0, kind=abi.KIND_VEHICLE, flags=abi.F_ALIVE, hl=2.25, hw=0.9, speed=0.0):
-    sh = st["shape"][slot]
-    sh["cx"], sh["cy"], sh["c"], sh["s"], sh["hl"], sh["hw"] = x, y, math.cos(heading), math.sin(heading), hl, hw
-    sh["flags"], sh["aux"] = kind | flags, -1
-    st["dyn"][slot]["heading"], st["dyn"][slot]["speed"] = heading, speed
 
 
 def pieces_of(features, spacing, S):

@@ -9,10 +9,10 @@ import numpy as np
 
 import contact_ref as cr
 import hostlib
+from hostlib import structs_of     # noqa: F401  (the tests reach it through this module)
 from metadrive_ped_amd import abi
 from metadrive_ped_amd.config import check_traffic_lights
 from metadrive_ped_amd.scenario import traffic_light_tables
-from scenario_vector_obs_host import structs_of     # noqa: F401  (MdWorld, MdState, MdConfig over a host scene and a downloaded state)
 
 _W, _S, _K, _T = C.POINTER(abi.MdWorld), C.POINTER(abi.MdState), C.POINTER(abi.MdConfig), C.POINTER(abi.MdTrafficLights)
 OUTPUTS = abi.TRAFFIC_LIGHTS_OUTPUTS
@@ -35,25 +35,21 @@ class HostTrafficLights:
     def __init__(self, tl_cfg, E, tables):
         self.cfg = check_traffic_lights(dict(tl_cfg))
         self.E = E
-        self.outs, out_bytes = abi.traffic_lights_blocks(self.cfg)
-        self.rows = np.zeros((E, out_bytes), np.uint8)
-        ptrs = dict(out_stride=out_bytes, max_scene_lights=tables["max_scene_lights"])
-        for name, (off, shape, dt) in self.outs.items():
-            if int(np.prod(shape)):
-                ptrs[name] = self.rows.ctypes.data + off
+        outs, out_bytes = abi.traffic_lights_blocks(self.cfg)
+        self._out = hostlib.HostRows(outs, out_bytes, E)
+        self.rows = self._out.rows
         self.tables = tables
         self._keep = {k: np.ascontiguousarray(tables[k]) for k in abi.TRAFFIC_LIGHTS_TABLES}
+        ptrs = dict(self._out.ptrs(), out_stride=out_bytes, max_scene_lights=tables["max_scene_lights"])
         ptrs.update({k: v.ctypes.data for k, v in self._keep.items()})
         self.tl = abi.make_md_traffic_lights(self.cfg, ptrs)
 
     def out(self, name):
         """a copy of the block `name`, [E, ...]"""
-        off, shape, dt = self.outs[name]
-        n = int(np.prod(shape)) * dt.itemsize
-        return np.ascontiguousarray(self.rows[:, off:off + n]).view(dt).reshape((self.E, ) + tuple(shape))
+        return self._out.out(name)
 
     def outputs(self):
-        return {name: self.out(name) for name in OUTPUTS}
+        return self._out.outs()
 
     def run(self, w, s, k):
         """one md_traffic_lights call on host arrays"""
@@ -71,14 +67,7 @@ def light_tables(lights):
 def light_world(cap=8):
     st = dict(shape=np.zeros(cap, abi.SHAPE_DT), dyn=np.zeros(cap, abi.DYN_DT), nav=np.zeros(cap, abi.NAV_DT))
     st["nav"]["lane"] = -1
-    w = abi.MdWorld()
-    w.n_maps, w.n_envs = 1, 1
-    s = abi.MdState()
-    for k, v in st.items():
-        setattr(s, k, hostlib.ptr(v))
-    k = abi.MdConfig()
-    k.struct_size, k.n_envs, k.agents_per_env, k.cap, k.traffic_mode = C.sizeof(abi.MdConfig), 1, 1, cap, 4
-    s.keep_alive = st       # the struct holds bare addresses
+    w, s, k = hostlib.hand_built_structs({}, st, cap=cap, traffic_mode=4)
     return w, s, k, st
 
 

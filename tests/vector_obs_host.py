@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 import hostlib
+from hostlib import clear, put, structs_of     # noqa: F401  (the tests reach them through this module)
 from metadrive_ped_amd import abi
 from metadrive_ped_amd.config import check_vector_obs
 
@@ -30,36 +31,23 @@ class HostVectorObs:
     def __init__(self, vo_cfg, E, A, cap):
         self.cfg = check_vector_obs(dict(vo_cfg))
         self.E = E
-        self.outs, out_bytes, self.hists, hist_bytes = abi.vector_obs_blocks(self.cfg, A, cap)
-        self.rows = np.zeros((E, out_bytes), np.uint8)
-        self.hist = np.zeros((E, hist_bytes), np.uint8)
-        ptrs = dict(out_stride=out_bytes, hist_stride=hist_bytes)
-        for table, rows in ((self.outs, self.rows), (self.hists, self.hist)):
-            for name, (off, shape, dt) in table.items():
-                if int(np.prod(shape)):
-                    ptrs[name] = rows.ctypes.data + off
-        self.vo = abi.make_md_vector_obs(self.cfg, ptrs)
-
-    @staticmethod
-    def _block(rows, table, name):
-        off, shape, dt = table[name]
-        n = int(np.prod(shape)) * dt.itemsize
-        return np.ascontiguousarray(rows[:, off:off + n]).view(dt).reshape((rows.shape[0], ) + tuple(shape))
+        outs, out_bytes, hists, hist_bytes = abi.vector_obs_blocks(self.cfg, A, cap)
+        self._out, self._hist = hostlib.HostRows(outs, out_bytes, E), hostlib.HostRows(hists, hist_bytes, E)
+        self.rows, self.hist = self._out.rows, self._hist.rows
+        self.vo = abi.make_md_vector_obs(self.cfg, dict(self._out.ptrs(), out_stride=out_bytes, hist_stride=hist_bytes, **self._hist.ptrs()))
 
     def out(self, name):
         """a copy of the block `name`, [E, A, ...]"""
-        return self._block(self.rows, self.outs, name)
+        return self._out.out(name)
 
     def outputs(self):
-        return {name: self.out(name) for name in abi.VECTOR_OBS_OUTPUTS}
+        return self._out.outs()
 
     def history(self):
-        return {name: self._block(self.hist, self.hists, name) for name in abi.VECTOR_OBS_HISTORY}
+        return self._hist.outs()
 
     def set_history(self, name, value):
-        off, shape, dt = self.hists[name]
-        n = int(np.prod(shape)) * dt.itemsize
-        self.hist[:, off:off + n] = np.ascontiguousarray(value, dt).reshape(self.E, -1).view(np.uint8)
+        self._hist.set(name, value)
 
     def run(self, w, s, k):
         """one md_vector_obs call on host arrays"""
@@ -69,18 +57,6 @@ class HostVectorObs:
     def push(self, s, k):
         assert lib().hx_vo_push(C.byref(s), C.byref(k), C.byref(self.vo)) == 0
         return self
-
-
-def structs_of(host, state, env_map=None):
-    """(MdWorld, MdState, MdConfig, keep-alive) over the host scene's tables and the numpy state `state` (the oracle's, or one
-    downloaded from the device); env_map: the envs' maps when they are not the scene's own (a walking batch)"""
-    from metadrive_ped_amd.engine import make_structs
-    wa = dict(host.world.arrays, **host.world_scalars())
-    if env_map is not None:
-        wa["env_map"] = np.ascontiguousarray(env_map, np.int32)
-    state = {k: np.ascontiguousarray(v) for k, v in state.items()}
-    w, s, k = make_structs(wa, state, host.md_config, host.world.n_maps, host.E, hostlib.ptr)
-    return w, s, k, (wa, state)
 
 
 def lane_local(lane_record, x, y):
@@ -113,25 +89,5 @@ def straight_world(E=1, cap=8, n_lanes=1, length=200.0, width=3.5, multi=False):
         nav = st["nav"][e * cap]
         nav["lane"], nav["ck0"], nav["ck1"], nav["route_len"], nav["road0"], nav["road1"] = 0, 0, 0, 2, 0, 0
         st["route_roads"][e * cap, 0] = 0
-    w = abi.MdWorld()
-    w.n_maps, w.n_envs, w.max_lanes, w.max_roads = 1, E, n_lanes, 1
-    for k, v in world.items():
-        setattr(w, k, hostlib.ptr(v))
-    s = abi.MdState()
-    for k, v in st.items():
-        setattr(s, k, hostlib.ptr(v))
-    k = abi.MdConfig()
-    k.struct_size, k.n_envs, k.agents_per_env, k.cap, k.is_multi_agent = C.sizeof(abi.MdConfig), E, 1, cap, int(multi)
+    w, s, k = hostlib.hand_built_structs(dict(world, max_lanes=n_lanes, max_roads=1), st, n_envs=E, cap=cap, is_multi_agent=int(multi))
     return w, s, k, st, world
-
-
-def put(st, slot, x, y, heading=0.0, kind=abi.KIND_VEHICLE, flags=abi.F_ALIVE, hl=2.25, hw=0.9, speed=0.0):
-    import math
-    sh = st["shape"][slot]
-    sh["cx"], sh["cy"], sh["c"], sh["s"], sh["hl"], sh["hw"] = x, y, math.cos(heading), math.sin(heading), hl, hw
-    sh["flags"], sh["aux"] = kind | flags, -1
-    st["dyn"][slot]["heading"], st["dyn"][slot]["speed"] = heading, speed
-
-
-def clear(st, slot):
-    st["shape"][slot]["flags"] = 0
