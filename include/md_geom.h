@@ -109,6 +109,63 @@ MD_HD float md_ray_shape(float ox, float oy, float dirx, float diry, float cx, f
     return md_ray_box(lox, loy, ldx, ldy, hl, hw);
 }
 
+/* The beams of a uniform fan (beam i at 2 pi i / n_beams in the ego frame: MdWorld.beam_cs) whose ray can come within the bounding
+ * radius of mover `o`: the cyclic range [*first, *first + *count) mod n_beams.  count = 0: out of reach, or no beam points at it;
+ * count = n_beams: the ego lies inside the radius.  The radius is hl for the circle kinds and sqrt(hl^2 + hw^2) for boxes, plus
+ * MD_LIDAR_SPAN_PAD.  Only ever CONSERVATIVE: a beam outside the span is one for which md_ray_shape returns no hit below 1 (proved on
+ * the host over seeded placements, tests/test_lidar_span_host.py).  Correctly rounded operations and this header's polynomials
+ * only, so the device computes the span the host test saw.
+ *
+ * A ray from the ego meets the disc of radius r around a centre at distance dist > r only within asin(r / dist) of the centre's
+ * direction.  The two error budgets:
+ *   PAD (metres on the radius): covers everything that scales with the scene -- the rounding of the ray tests themselves (a few
+ *   2^-24 of the coordinates: below 1e-3 m at |x|, |y| < 2000 m) and of rb / dist ahead of the asin, whose slope is unbounded at 1:
+ *   with the pad the quotient exceeds the true one by 0.01 / dist >= 1e-5 relative, a hundred roundings.
+ *   SLACK (beams on each side): covers what does not -- md_atan2 and md_asin (below 5e-7 rad each), the rotation into the ego frame
+ *   (3 roundings of 2^-24 relative to |d|: 2e-7 rad), the beam table's float32 cos / sin (6e-8 rad) and the scale n / 2 pi (2
+ *   roundings on a value below n): in all under 1.3e-6 rad n / 2 pi + 2.4e-7 n beams, 8.4e-4 beams at n = 2048.  1 / 64 holds for
+ *   every fan up to 2^15 beams. */
+#define MD_LIDAR_SPAN_PAD 0.01f
+#define MD_LIDAR_SPAN_SLACK 0.015625f
+MD_HD void md_lidar_beam_span(float ex, float ey, float ec, float es, float range, int n_beams, const MdShape* o, int* first,
+                              int* count) {
+    int kind = o->flags & MD_KIND_MASK;
+    int circle = kind == MD_KIND_CONE || kind == MD_KIND_WARNING || kind == MD_KIND_PEDESTRIAN;
+    float dx = o->cx - ex, dy = o->cy - ey;
+    float d2 = dx * dx + dy * dy;
+    float rb = (circle ? o->hl : md_sqrt(o->hl * o->hl + o->hw * o->hw)) + MD_LIDAR_SPAN_PAD;
+    float reach = range + rb;
+    *first = 0;
+    *count = 0;
+    if (d2 > reach * reach * 1.0001f) return;
+    if (!(d2 > rb * rb)) { /* inside the radius (or a NaN pose): every beam */
+        *count = n_beams;
+        return;
+    }
+    float lx = dx * ec + dy * es; /* the centre in the ego frame (scaled like the beams if (c, s) is not a unit vector) */
+    float ly = dy * ec - dx * es;
+    float scale = (float)n_beams * 0.15915494309189535f;
+    float mid = md_atan2(ly, lx) * scale;
+    float half = md_asin(md_min(rb / md_sqrt(d2), 1.0f)) * scale + MD_LIDAR_SPAN_SLACK;
+    float lo = -md_floor(-(mid - half)); /* ceil */
+    float hi = md_floor(mid + half);
+    if (!(lo - hi <= 1.0f)) { /* a NaN ego heading: every beam (none of them hits) */
+        *count = n_beams;
+        return;
+    }
+    int n = (int)hi - (int)lo + 1;
+    if (n <= 0) return; /* between two beams */
+    int f = (int)lo;
+    if (f < 0) f += n_beams; /* mid - half > -(n / 2 + n / 4 + 1) */
+    if (f >= n_beams) f -= n_beams;
+    if (n >= n_beams) {
+        n = n_beams;
+        f = 0;
+    }
+    *first = f;
+    *count = n;
+}
+
 /* ------------------------------------------------------------------------------------------
  * Overlap tests (2-D restatement of Bullet contactTest between chassis box and other bodies:
  * base_vehicle.py:704-746, engine/core/collision_callback.py:5-42).

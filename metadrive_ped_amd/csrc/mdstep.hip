@@ -346,6 +346,119 @@ __device__ __forceinline__ void phase_lidar(const MdWorld& w, const MdState& s, 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Lidar for one agent's WHOLE cloud by one wave, FLAT over the (mover, beam) pairs that can meet: the two lean non-staged workgroup
+// kernels (no detected sets, the cloud goes to HBM).  lidar_item casts all 64 beams of a sector at every mover its cone cull keeps,
+// and derives the cull once per sector; a vehicle 20 m away meets a dozen of 240 beams.  Here:
+//   (1) lanes = slots: md_lidar_beam_span gives each present mover the cyclic range of beams that can come within its bounding
+//       radius (correctly rounded, conservative: tests/test_lidar_span_host.py), once per cloud;
+//   (2) lanes = pairs: lane t of a pass takes pair t of the movers' spans laid end to end.  The owner is found by walking the
+//       movers' ballot with a running count in scalar registers (a handful of movers: cheaper than a prefix scan and a search
+//       through ds_bpermute); movers that lie wholly before or behind the pass are stepped over;
+//   (3) the lane casts its beam at its mover with the same md_ray_shape and, under lidar_item's predicate t < 1.0f, lowers the
+//       beam's word in `row` (LDS, n_beams words of this wave, set to the bits of 1.0f) with atomicMin on the float's bits: t lies
+//       in (0, 1), where unsigned order is float order; a NaN fails the predicate in both forms.
+// A beam's value is the minimum of the same fractions over a superset of the movers that can hit it, and a minimum does not depend
+// on the order: the same bits as lidar_item's.
+// ------------------------------------------------------------------------------------------------
+#ifndef MD_LIDAR_FLAT
+#define MD_LIDAR_FLAT 1
+#endif
+__device__ __forceinline__ void lidar_agent_flat(const MdWorld& w, const MdState& s, const MdConfig& c, int a, int lane,
+                                                 float* __restrict__ out_row, uint32_t* row) {
+    const MdShape me = s.shape[a];  // wave-uniform
+    const int nb = c.n_beams;
+    if (!md_present(me.flags)) {
+        for (int b = lane; b < nb; b += 64) st_stream_f(&out_row[b], 1.0f);
+        return;
+    }
+    for (int b = lane; b < nb; b += 64) row[b] = 0x3f800000u;
+    wave_lds_sync();
+    for (int j0 = 0; j0 < c.cap; j0 += 64) {
+        const int j = j0 + lane;
+        int first = 0, cnt = 0;
+        if (j < c.cap && j != a) {
+            const MdShape o = s.shape[j];
+            if (md_present(o.flags)) md_lidar_beam_span(me.cx, me.cy, me.c, me.s, c.lidar_range, nb, &o, &first, &cnt);
+        }
+        const unsigned long long movers = __ballot(cnt > 0);
+#if MD_LIDAR_FLAT == 2
+        // the other form: one pass per mover that can be met, over its own span alone -- no owner search, and since a pass holds a
+        // beam once, a plain read-min-write of the row's words
+        for (unsigned long long m = movers; m;) {
+            const int k = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            const int ck = __builtin_amdgcn_readlane(cnt, k), fk = __builtin_amdgcn_readlane(first, k);
+            const MdShape o = s.shape[j0 + k];
+            for (int i = lane; i < ck; i += 64) {
+                int beam = fk + i;
+                if (beam >= nb) beam -= nb;
+                const float bc = w.beam_cs[2 * beam], bs = w.beam_cs[2 * beam + 1];
+                const float dirx = (bc * me.c - bs * me.s) * c.lidar_range;
+                const float diry = (bs * me.c + bc * me.s) * c.lidar_range;
+                const float tt = md_ray_shape(me.cx, me.cy, dirx, diry, o.cx, o.cy, o.c, o.s, o.hl, o.hw, md_kind_of(o.flags));
+                if (tt < 1.0f && __float_as_uint(tt) < row[beam]) row[beam] = __float_as_uint(tt);
+            }
+            wave_lds_sync();
+        }
+#else
+        int total = 1;   // wave-uniform; known after the first pass
+        for (int t0 = 0; t0 < total; t0 += 64) {
+            const int t = t0 + lane;
+            int owner = -1, beam = 0;
+            int run = 0;   // pairs of the movers before this one
+            for (unsigned long long m = movers; m;) {
+                const int k = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const int ck = __builtin_amdgcn_readlane(cnt, k);
+                const int at = run;
+                run += ck;
+                if (run <= t0 || at >= t0 + 64) continue;   // wholly before / behind this pass (the count goes on for `total`)
+                const int fk = __builtin_amdgcn_readlane(first, k);
+                if ((unsigned)(t - at) < (unsigned)ck) {
+                    owner = k;
+                    beam = fk + (t - at);
+                }
+            }
+            total = run;
+            if (owner >= 0) {
+                if (beam >= nb) beam -= nb;
+                const MdShape o = s.shape[j0 + owner];
+                const float bc = w.beam_cs[2 * beam], bs = w.beam_cs[2 * beam + 1];
+                const float dirx = (bc * me.c - bs * me.s) * c.lidar_range;
+                const float diry = (bs * me.c + bc * me.s) * c.lidar_range;
+                const float tt = md_ray_shape(me.cx, me.cy, dirx, diry, o.cx, o.cy, o.c, o.s, o.hl, o.hw, md_kind_of(o.flags));
+                if (tt < 1.0f) atomicMin(&row[beam], __float_as_uint(tt));
+            }
+        }
+#endif
+    }
+    wave_lds_sync();
+    for (int b = lane; b < nb; b += 64) st_stream_f(&out_row[b], __uint_as_float(row[b]));
+    __builtin_amdgcn_wave_barrier();   // the row is free again
+}
+
+// The waves take the AGENTS as they get free (`tickets`: LDS counter, zeroed by the caller behind a barrier); `rows`: n_beams words
+// of LDS per wave (env_lds_lidar_rows).
+__device__ __forceinline__ void phase_lidar_flat(const MdWorld& w, const MdState& s, const MdConfig& c, int e, int tid, float* out,
+                                                 int out_stride, int out_offset, int* tickets, uint32_t* rows) {
+    // the wave's number is made again from an opaque copy of tid, in a scalar register: carried from the kernel's entry it is one
+    // more VGPR live across every stage, and the lean kernels have none to spare (narrow: v3 and 16 B of scratch instead of v2 and
+    // 12 B).  This steers the register allocator of ONE compiler: after a toolchain change read the two lean kernels' lines of
+    // tools/kernel_regs.sh again -- nothing else guards the register rule here.
+    int tid_here = tid;
+    asm("" : "+v"(tid_here));
+    const int wave = __builtin_amdgcn_readfirstlane(tid_here >> 6), lane = tid & 63;
+    for (int guard = 0; guard < c.agents_per_env; ++guard) {
+        int a = 0;
+        if (lane == 0) a = atomicAdd(tickets, 1);
+        a = __builtin_amdgcn_readfirstlane(a);
+        if (a < 0 || a >= c.agents_per_env) break;
+        float* row = out + (size_t)(e * c.agents_per_env + a) * out_stride + out_offset;
+        lidar_agent_flat(w, s, c, a, lane, row, rows + (size_t)wave * c.n_beams);
+    }
+}
+
 // The detectors' cull record of quad q: centre, radius of a circle around it, kind -- from MdWorld.quad_ball (16 bytes) or,
 // without that table, from the quad itself.
 struct QuadBall { float mx, my, rr; int kind; };
@@ -882,6 +995,11 @@ __host__ __device__ inline EnvLds env_lds(int cap, int agents, int n_lanes, int 
     return L;
 }
 
+// The result words of the flat lidar pass (lidar_agent_flat): n_beams words per wave BEHIND the image -- in the dynamic size of the
+// launches that use them (launch<PH_ALL>, behind its fit check), not in env_lds().bytes, which the entry points' messages quote.
+// -> their offset.  The entry checks bound n_beams by 1024: four waves' words are at most 16 KB.
+__host__ __device__ inline uint32_t env_lds_lidar_rows(uint32_t image_bytes) { return align_up(image_bytes, 16); }
+
 // BLK: threads of the workgroup (MD_ENV_BLOCK; multi-agent batches small enough to stay resident are also instantiated with 512:
 // eight waves share an env's 20-40 agents -- lifecycle search, contacts, observe groups, lidar sectors -- instead of four).
 // NARROW: the lean non-staged kernel of a batch that holds the size pins too (lean_size_pins_fold): one agent, at most 64 slots.
@@ -1360,7 +1478,12 @@ void env_kernel(MdWorld w, MdState g, MdConfig c, float* lidar_out,
             lidar_stride = LEAN_ARG(kl, lidar_stride);
             lidar_offset = LEAN_ARG(kl, lidar_offset);
         }
-        if (c.n_beams > 0) phase_lidar(w, s, c_scan, e, tid, kWaves, lidar_out, lidar_stride, lidar_offset, track_det ? l_det : nullptr, PH == PH_ALL ? &l_tk[2] : nullptr);
+        // the two lean non-staged kernels: one wave per agent, flat over the (mover, beam) pairs (lidar_agent_flat)
+        constexpr bool kLidarFlat = MD_LIDAR_FLAT && PH == PH_ALL && kIdmKeys;
+        if constexpr (kLidarFlat) {
+            const uint32_t rows_at = env_lds_lidar_rows(env_lds(cap, c.agents_per_env, 0, 0, kWaves, false, false).bytes);
+            if (c.n_beams > 0) phase_lidar_flat(w, s, c_scan, e, tid, lidar_out, lidar_stride, lidar_offset, &l_tk[2], reinterpret_cast<uint32_t*>(smem + rows_at));
+        } else if (c.n_beams > 0) phase_lidar(w, s, c_scan, e, tid, kWaves, lidar_out, lidar_stride, lidar_offset, track_det ? l_det : nullptr, PH == PH_ALL ? &l_tk[2] : nullptr);
     }
 
     MD_STAMP_AT(9);
@@ -2870,14 +2993,22 @@ int launch(const MdWorld* w, const MdState* s, const MdConfig* c, float* lidar_o
                  lds, c->cap, w->max_lanes, w->max_roads);
         return MD_EINVAL;
     }
+    size_t lds_launch = lds;   // the lean non-staged kernels' flat lidar pass: its result words behind the image, where they fit
+    if (PH == PH_ALL && MD_LIDAR_FLAT && !v.stage && !v.multi && !v.respawn) {
+        if (c->n_beams > 0) lds_launch = env_lds_lidar_rows((uint32_t)lds) + (size_t)(MD_ENV_BLOCK / 64) * c->n_beams * sizeof(uint32_t);
+        if (lds_launch > 64 * 1024) {
+            snprintf(g_err, sizeof g_err, "LDS image of one env and its lidar rows need %zu B (cap=%d, n_beams=%d); limit 65536", lds_launch, c->cap, c->n_beams);
+            return MD_EINVAL;
+        }
+    }
     // the instantiations: PH_ALL all four; the phases that can be multi-agent or respawn two; the others one (per stage)
     constexpr bool kAll = PH == PH_ALL, kMulti = (PH & (PH_LIFECYCLE | PH_RESET)) != 0;
     constexpr bool kRespawn = (PH & (PH_TRAFFIC | PH_RESET | PH_INTEGRATE)) != 0;
     if (v.wide) launch_env<PH, false, kAll, kAll ? 512 : MD_ENV_BLOCK>(v.stage, lds, st, w, s, c, lidar_out, stride, offset);
     else if (v.multi) launch_env<PH, false, kMulti>(v.stage, lds, st, w, s, c, lidar_out, stride, offset);
     else if (v.respawn) launch_env<PH, kRespawn, false>(v.stage, lds, st, w, s, c, lidar_out, stride, offset);
-    else if (kAll && v.narrow) launch_narrow<PH>(lds, st, w, s, c, lidar_out, stride, offset);
-    else launch_env<PH, false, false>(v.stage, lds, st, w, s, c, lidar_out, stride, offset);
+    else if (kAll && v.narrow) launch_narrow<PH>(lds_launch, st, w, s, c, lidar_out, stride, offset);
+    else launch_env<PH, false, false>(v.stage, lds_launch, st, w, s, c, lidar_out, stride, offset);
     return launch_status();
 }
 
